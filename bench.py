@@ -10,6 +10,10 @@ One process per GPU (torch.distributed / RCCL when launched with --nproc-per-nod
 sequences of a fraction are independent, so ranks take disjoint sequences (weak scaling: PS per GPU
 is fixed) and meet only in one all-reduce(SUM) of the flat weightUpdates arena.
 Rank 0 prints ONE JSON line.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times exactly N steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints the line.  --deterministic picks how the steps sum gradients (see its help).  --full adds everything else this file measures or checks: repetitions
+for a median, the roofline pass, the host-buffer load path, the extra workloads, the C++ driver leg, the CPU baseline.
 """
 import argparse
 import json
@@ -37,6 +41,19 @@ WORKLOADS = {
     "longutt_5x1024_blstm": dict(P=39, hidden=[("blstm", 1024)] * 5, C=183, PS=16, tmin=2000, tmax=2000),
 }
 PEAK_HBM_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E peak
+DUMP_MAX_ELEMENTS = 1 << 22  # --dump-outputs: 4 M elements (16 MB of fp32) per array, three large arrays stay under 64 MB
+
+
+def dump_arrays(directory, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float64 kept, everything else as float32; an array of more than
+    DUMP_MAX_ELEMENTS is flattened and cut to that many distinct elements at a fixed stride (the same indices every run)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.arange(DUMP_MAX_ELEMENTS, dtype=np.int64) * a.size // DUMP_MAX_ELEMENTS]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def pmc_bytes_per_launch(kernel):
@@ -297,17 +314,36 @@ def main():
     ap.add_argument("--tmax", type=int, default=None)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32", "bf16x3"],
                     help="bf16: throughput mode; f32: exact-fp32 MFMA parity mode; bf16x3: split-bf16 parity mode (fp32 tolerance at a third of the bf16 MFMA rate)")
-    ap.add_argument("--no-also", action="store_true", help="skip the informational extra workloads of the default run")
-    ap.add_argument("--no-driver-leg", action="store_true", help="skip the end-to-end run of the C++ driver on a synthetic NetCDF file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repetitions of the timed steps until CN_BENCH_MIN_SECONDS (default 0.5 s) and "
+                         "their median, the event-timed roofline pass, the host-buffer load path, the extra workloads and precisions, the C++ "
+                         "driver leg and the CPU baseline with its parity records; the --no-* switches below drop parts of it.  Without "
+                         "--full: warm-up, ONE pass of exactly --steps timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64): the "
+                         "posteriors of its real frames, the weights after its update and its weight gradients, and the CUMULATIVE loss "
+                         "sums (error, correct frames) over the warm-up and every timed step; arrays over 4 M elements are cut to 4 M "
+                         "elements at a fixed stride (<= 64 MB in all)")
+    ap.add_argument("--deterministic", choices=["auto", "on", "off"], default="auto",
+                    help="how the timed steps sum gradients over patterns (library option \"deterministic\"; the result line reports it as "
+                         "config.deterministic_sums).  on: in a fixed order, two runs compute the same bits; off: with fp32 atomics in arrival "
+                         "order, the bf16 default, whose runs drift apart by more than rounding; auto (default): on with --dump-outputs, so "
+                         "that dumps of two runs or two builds can be compared, otherwise the library's default for --precision (off in "
+                         "bf16, on in f32 / bf16x3).  Fixed-order sums cost the bf16 step a few percent: DESIGN.md section 5, and the "
+                         "`deterministic` record of --full")
+    ap.add_argument("--no-also", action="store_true", help="(--full) skip the informational extra workloads")
+    ap.add_argument("--no-driver-leg", action="store_true", help="(--full) skip the end-to-end run of the C++ driver on a synthetic NetCDF file")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--momentum", type=float, default=0.9)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline-pass", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and its parity records")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="(--full) skip the event-timed pass behind the roofline records")
     ap.add_argument("--also", default="", help="comma list of extra workloads (name or name:precision) measured and reported under 'also'")
     args = ap.parse_args()
     launched = "WORLD_SIZE" in os.environ
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if not launched and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes BEFORE torch is
         # imported or any GPU call is made here (a process that has initialised the GPU must not exec), relay
@@ -405,8 +441,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return [float(x) for x in t]
 
-    def run_workload(name, steps, warmup, precision, roofline_pass=False, host_pass=False, min_seconds=0.5, deterministic=None):
-        """-> (result dict, workload): `steps` timed steps per repetition (median of enough repetitions for min_seconds)"""
+    def run_workload(name, steps, warmup, precision, roofline_pass=False, host_pass=False, min_seconds=0.5, deterministic=None, dump_dir=None):
+        """-> (result dict, workload): `steps` timed steps per repetition (median of enough repetitions for min_seconds;
+        min_seconds = 0: exactly one repetition)"""
         wl = WORKLOADS[name]
         PS = args.parallel_sequences if name == args.workload else wl.get("PS", 50)
         tmin = args.tmin if name == args.workload else wl.get("tmin", 250)
@@ -516,6 +553,16 @@ def main():
                 dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             torch.cuda.synchronize(dev)
             res["replicas_identical"] = bool(torch.equal(lo, hi))
+        if dump_dir is not None and rank == 0:
+            # what the LAST timed step hands its caller, before any further pass moves the weights: the posteriors of its
+            # fraction's real frames, the weights after its update, its weight gradients; and the CUMULATIVE loss sums read above
+            # (error and correct frames over the warm-up and every timed step: the path adds each step's loss on the device)
+            net.synchronize()
+            real = np.asarray(fracs[(warmup + steps - 1) % nfrac]["patTypes"]).reshape(-1) != 0
+            grad_view = torch.as_tensor(pkg.parallel.DeviceArray(gptr, count), device=dev)
+            dump_arrays(dump_dir, {"posteriors": net.outputs().reshape(-1, C)[real], "weights": wts.cpu().numpy(),
+                                   "weight_gradients": grad_view.cpu().numpy(),
+                                   "cumulative_loss_sums": np.array([err_sum, correct], np.float64)})
         if host_pass:
             # the same steps with the fractions handed over as host buffers (cn_fraction_load: packed into pinned memory,
             # one upload on a copy stream under the previous fraction's compute, then the re-layout kernel)
@@ -538,15 +585,20 @@ def main():
         del keep
         return res, wl
 
-    min_seconds = float(os.environ.get("CN_BENCH_MIN_SECONDS", "0.5"))
-    res, wl = run_workload(args.workload, args.steps, args.warmup, args.precision, roofline_pass=not args.no_roofline_pass,
-                           host_pass=(world == 1), min_seconds=min_seconds)
+    # a plain run times ONE pass of exactly --steps steps; --full repeats them until min_seconds and reports the median
+    min_seconds = float(os.environ.get("CN_BENCH_MIN_SECONDS", "0.5")) if args.full else 0.0
+    # --deterministic auto: fixed-order gradient sums when the outputs are dumped (the bf16 default's arrival-order atomics make two
+    # runs drift apart), the library's default for the precision otherwise; what was timed is config.deterministic_sums
+    deterministic = {"on": True, "off": False}.get(args.deterministic, True if args.dump_outputs else None)
+    res, wl = run_workload(args.workload, args.steps, args.warmup, args.precision, roofline_pass=args.full and not args.no_roofline_pass,
+                           host_pass=args.full and world == 1, min_seconds=min_seconds, dump_dir=args.dump_outputs,
+                           deterministic=deterministic)
     seconds, frames = res["seconds"], res["frames"]
     value = frames / seconds
 
     # informational extra lines: the Graves-literal reading of "3x250" and the parity (fp32-tolerance) arithmetic mode
     also_spec = [a for a in args.also.split(",") if a]
-    if not args.also and world == 1 and args.workload == "timit_3x250_blstm_H125" and not args.no_also:
+    if not args.also and world == 1 and args.workload == "timit_3x250_blstm_H125" and args.full and not args.no_also:
         also_spec = (["timit_3x500_blstm_H250"] + (["timit_3x250_blstm_H125:bf16x3", "timit_3x500_blstm_H250:bf16x3"] if "bf16x3" in PRECISIONS else [])
                      + ["timit_3x250_blstm_H125:f32"])
         # BASELINE.json configs[3] and configs[4] as written (one GPU's share of the 8-GPU configs: PS per GPU as in WORKLOADS)
@@ -592,7 +644,9 @@ def main():
                        "parallel_sequences_per_gpu": args.parallel_sequences, "seq_len": "U[%d,%d]" % (args.tmin, args.tmax),
                        "weights": res["weights"], "update": "stochastic momentum SGD every fraction",
                        "parallelism": "dp%d over sequences" % world, "inputs": "fractions resident in HBM (cn_fraction_load_resident)"},
-            "timing": {"repeats": res["repeats"], "reported": "median repetition of `steps` steps, each bracketed by barrier + synchronize, max over ranks",
+            "timing": {"repeats": res["repeats"],
+                       "reported": ("median repetition of `steps` steps, each bracketed by barrier + synchronize, max over ranks" if args.full else
+                                    "one pass of `steps` steps, bracketed by barrier + synchronize, max over ranks"),
                        "ms_per_step_min": 1e3 * res["seconds_min"] / args.steps, "ms_per_step_max": 1e3 * res["seconds_max"] / args.steps,
                        "timed_total_s": res["timed_total_s"]},
         }
@@ -638,9 +692,9 @@ def main():
                 # ... and once more as flat scalars (round 4's driver record kept only the scalar entries of `config`)
                 for k, v in other.items():
                     out["config"]["frames_per_s_" + k] = round(v["value"])
-        if world == 1 and not args.no_driver_leg:
+        if world == 1 and args.full and not args.no_driver_leg:
             out["driver_leg"] = driver_leg(wl, args)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, wl, args, PRECISIONS)
         print(json.dumps(out))
     if use_comm and dist.is_initialized():

@@ -19,7 +19,7 @@ for n in $counts; do
   for backend in nccl p2p; do
     log=$(mktemp /tmp/first_contact_${n}_${backend}.XXXX)
     echo "== $n ranks, exchange backend $backend (log: $log)"
-    CN_BENCH_BACKEND=$backend CN_P2P_VERBOSE=1 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline --no-driver-leg --no-also > $log 2> $log.err
+    CN_BENCH_BACKEND=$backend CN_P2P_VERBOSE=1 python3 bench.py --gpus $n --full --steps 10 --warmup 3 --no-cpu-baseline --no-driver-leg --no-also > $log 2> $log.err
     code=$?
     if [ $code -ne 0 ]; then echo "   FAILED with exit code $code"; tail -5 $log.err | sed 's/^/   /'; rc=1; continue; fi
     grep -h "first-contact\|falling back" $log.err | sed 's/^/   /'
