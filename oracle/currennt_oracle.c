@@ -32,8 +32,17 @@
  * Build: gcc -O2 -ffp-contract=off -shared -fPIC (oracle/Makefile).
  * -ffp-contract=off keeps `x += a*b` a separate multiply and add like the
  * reference's x86-64 host build (no FMA target feature).
+ *
+ * DOUBLE BUILD: the same source with -DORC_DOUBLE is libcurrennt_oracle64.so (oracle.real64() in the python front end):
+ * real_t is double and expf / logf / sqrtf become exp / log / sqrt; every statement, sum order and clip is the fp32
+ * library's.  It states the TRUE result of the path to ~1e-15, so that tests can measure the reference's own fp32 rounding
+ * noise (fp32 library against this one) and hold the HIP parity modes to a multiple of it instead of to 1e-4
+ * (tests/test_oracle_fp64.py, tests/test_gpu_long_fp64.py).  Without the switch nothing changes: tests/test_oracle_ref.py
+ * keeps the fp32 library bit-equal to oracle/_ref.  The split-operand model of CN_PREC_BF16X3 ("operand rounding" modes 2
+ * and 3 below) is meant for the double build, where the model's dropped terms are the only error.
  */
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -55,7 +64,18 @@ int orc_get_threads(void) { return g_threads; }
 #define ORC_PAR(work) const long orc_work_ = (long)(work); (void)orc_work_; \
     _Pragma("omp parallel for schedule(static) if (g_threads > 1 && orc_work_ > 400000)")
 
+#ifdef ORC_DOUBLE
+typedef double real_t;
+#define R_EXP  exp
+#define R_LOG  log
+#define R_SQRT sqrt
+#else
 typedef float real_t;
+#define R_EXP  expf
+#define R_LOG  logf
+#define R_SQRT sqrtf
+#endif
+int orc_real_bytes(void) { return (int)sizeof(real_t); }
 
 #define PATTYPE_NONE 0
 
@@ -77,10 +97,31 @@ typedef float real_t;
  */
 #include <stdint.h>
 static int g_opround = 0;
-void orc_set_operand_rounding(int mode) { g_opround = mode ? 1 : 0; }
+/*
+ * Modes 2 and 3: a MODEL of CN_PREC_BF16X3 (split operands), meant for the double build.  (python: "bf16x3",
+ * "bf16x3_minus_one".)  At exactly the call sites mode 1 rounds, each product term a*b becomes
+ *     ah*bh + ah*bl + al*bh,   ah = bf16(a32), al = bf16(a32 - ah), a32 = (float)a   (same for b),
+ * which is what split_bf16 / mma16_x3 of the HIP library compute (cn_lstm_device.h): the operands the kernels see are the
+ * fp32 values in memory, hi and lo are rounded to nearest even, al*bl and the two residuals a32 - ah - al are dropped.
+ * Modelling choices, all taken from what CN_PREC_BF16X3 keeps in fp32 (cn_internal.h P_X3):
+ *   - LSTM outputs, pre-activations, deltas and weights stay unrounded in memory (the HIP library keeps them in fp32 in this
+ *     mode; STORE_Y rounds in mode 1 only).  The only rounding the model applies to a stored value is the (float) cast in
+ *     front of the split, i.e. the 2^-24 the fp32 storage costs an operand; the value itself is carried on in real_t.
+ *   - Accumulation, cell states, activations, bias / peephole terms and their gradient sums, the clip, softmax and the loss
+ *     are real_t (double in the double build): the model isolates the error of the dropped product terms.  What the HIP
+ *     path adds on top -- fp32 accumulation in blocked order, v_exp_f32 / v_rcp_f32 -- is of the size of the fp32
+ *     reference's own noise and is measured as such by the tests (D_ref), not modelled.
+ *   - The sum of the three terms is taken in real_t as ah*(bh + bl) + al*bh; bh + bl is exact in double (two 8-bit
+ *     significands at most 2^9 apart), so in the double build this is the three-term sum to 1e-16.
+ * Mode 3 (test only) additionally omits ah*bl in the RECURRENT products (LstmLayer.cu:815-818,850-853,939-942,973-976: a =
+ * W_rec, b = y[t-1] or the deltas of the neighbouring step), i.e. a kernel that lost one of its three MFMAs there: 2^-9
+ * relative on that product.  tests/test_oracle_fp64.py uses it to show that the fp64-relative bound notices such a kernel.
+ */
+static int g_x3_recurrent = 0;     /* set around the recurrent products of the time loops (mode 3 looks at it) */
+void orc_set_operand_rounding(int mode) { g_opround = (mode >= 0 && mode <= 3) ? mode : 0; }
 int orc_get_operand_rounding(void) { return g_opround; }
 /*
- * orc_set_preact_rounding(1) (round 6; only looked at in operand-rounding mode, by the NEXT orc_lstm_forward calls): the gate
+ * orc_set_preact_rounding(1) (round 6; only looked at in operand-rounding mode 1, by the NEXT orc_lstm_forward calls): the gate
  * pre-activations of the input projection (LstmLayer.cu:771-786) are kept in bf16 WITH the bias term the product's epilogue adds
  * (x W_in + bias w_b, rounded to nearest even) -- what CN_PREC_BF16 stores between its input-projection GEMM and the recurrent
  * kernels of the layers that take them in that form (cn_layer_recurrent_kernel: the "_s2_" forward kernels).  The functor
@@ -91,15 +132,17 @@ static int g_preround = 0;
 void orc_set_preact_rounding(int on) { g_preround = on ? 1 : 0; }
 int orc_get_preact_rounding(void) { return g_preround; }
 
+/* bf16 (round to nearest even) of the value AS A FLOAT: the double build rounds (float)v, the fp32 build v itself */
 static real_t bf16_rne(real_t v)
 {
+    float f = (float)v;
     uint32_t u;
-    memcpy(&u, &v, 4);
+    memcpy(&u, &f, 4);
     if ((u & 0x7f800000u) == 0x7f800000u) return v;              /* inf / nan: as is */
     u += 0x7fffu + ((u >> 16) & 1u);
     u &= 0xffff0000u;
-    memcpy(&v, &u, 4);
-    return v;
+    memcpy(&f, &u, 4);
+    return f;
 }
 static real_t *rounded_copy(const real_t *src, size_t n)
 {
@@ -107,11 +150,63 @@ static real_t *rounded_copy(const real_t *src, size_t n)
     for (size_t i = 0; i < n; ++i) q[i] = bf16_rne(src[i]);
     return q;
 }
-/* operands of one product: rounded copies in mode 1, the caller's arrays otherwise */
+/* modes 2 / 3: hi[i] = bf16(x32), lo[i] = bf16(x32 - hi) with x32 = (float)src[i]; the difference is taken in fp32 like
+ * split_bf16 (it is exact there) */
+static void split_copy(const real_t *src, size_t n, real_t **hi, real_t **lo)
+{
+    real_t *h = (real_t *)malloc(sizeof(real_t) * (n ? n : 1)), *l = (real_t *)malloc(sizeof(real_t) * (n ? n : 1));
+    for (size_t i = 0; i < n; ++i) {
+        float f = (float)src[i];
+        float fh = (float)bf16_rne((real_t)f);
+        h[i] = fh;
+        l[i] = bf16_rne((real_t)(f - fh));
+    }
+    *hi = h; *lo = l;
+}
+/* the second factor of a split product: bh + bl (all three terms), or bh alone where mode 3 drops ah*bl */
+static void split_copy_b(const real_t *src, size_t n, real_t **hi, real_t **sum)
+{
+    split_copy(src, n, hi, sum);
+    if (g_opround == 3 && g_x3_recurrent)
+        memcpy(*sum, *hi, sizeof(real_t) * n);
+    else
+        for (size_t i = 0; i < n; ++i) (*sum)[i] += (*hi)[i];
+}
+/* The recurrent products split the same W_rec sub-matrix at every time step; the planes are kept for the duration of one
+ * orc_lstm_forward / orc_lstm_backward call (weights do not change inside one) and released by x3_cache_release(). */
+static struct { const real_t *src; size_t n; real_t *hi, *lo; } g_x3_cache[8];
+static int g_x3_cached = 0;
+static void split_cached(const real_t *src, size_t n, real_t **hi, real_t **lo)
+{
+    for (int i = 0; i < g_x3_cached; ++i)
+        if (g_x3_cache[i].src == src && g_x3_cache[i].n == n) { *hi = g_x3_cache[i].hi; *lo = g_x3_cache[i].lo; return; }
+    split_copy(src, n, hi, lo);
+    if (g_x3_cached < 8) {
+        g_x3_cache[g_x3_cached].src = src; g_x3_cache[g_x3_cached].n = n;
+        g_x3_cache[g_x3_cached].hi = *hi; g_x3_cache[g_x3_cached].lo = *lo; ++g_x3_cached;
+    }
+}
+static int x3_is_cached(const real_t *hi)
+{
+    for (int i = 0; i < g_x3_cached; ++i) if (g_x3_cache[i].hi == hi) return 1;
+    return 0;
+}
+static void x3_cache_release(void)
+{
+    for (int i = 0; i < g_x3_cached; ++i) { free(g_x3_cache[i].hi); free(g_x3_cache[i].lo); }
+    g_x3_cached = 0;
+}
+/* operands of one product: rounded copies in mode 1; in modes 2 and 3 a and b become the hi planes and al_ / bs_ the lo plane
+ * of a and the plane bh + bl of b (same layouts as a and b; NULL in modes 0 and 1), the caller's arrays otherwise.  The loops
+ * below take the reference's a*b in modes 0 and 1 and ah*(bh + bl) + al*bh where al_ is set. */
 #define MM_OPERANDS(na, nb) \
-    real_t *aq_ = NULL, *bq_ = NULL; \
-    if (g_opround) { aq_ = rounded_copy(a, (size_t)(na)); bq_ = rounded_copy(b, (size_t)(nb)); a = aq_; b = bq_; }
-#define MM_RELEASE() do { free(aq_); free(bq_); } while (0)
+    real_t *aq_ = NULL, *bq_ = NULL, *al_ = NULL, *bs_ = NULL; \
+    if (g_opround == 1) { aq_ = rounded_copy(a, (size_t)(na)); bq_ = rounded_copy(b, (size_t)(nb)); a = aq_; b = bq_; } \
+    else if (g_opround >= 2) { \
+        if (g_x3_recurrent) split_cached(a, (size_t)(na), &aq_, &al_); else split_copy(a, (size_t)(na), &aq_, &al_); \
+        split_copy_b(b, (size_t)(nb), &bq_, &bs_); a = aq_; b = bq_; \
+    }
+#define MM_RELEASE() do { if (!aq_ || !x3_is_cached(aq_)) { free(aq_); free(al_); } free(bq_); free(bs_); } while (0)
 
 /* helpers/NumericLimits.cuh:39-43 */
 #define NL_MIN      1.1754944e-038f
@@ -129,7 +224,7 @@ static real_t logistic_fn(real_t x)
 {
     if (x < NL_EXPLIMIT) {
         if (x > -NL_EXPLIMIT)
-            return (real_t)1.0 / ((real_t)1.0 + expf(-x));
+            return (real_t)1.0 / ((real_t)1.0 + R_EXP(-x));
         else
             return 0;
     }
@@ -159,7 +254,7 @@ static real_t safe_exp(real_t x)
     else if (x >= NL_EXPLIMIT)
         return NL_MAX;
     else
-        return expf(x);
+        return R_EXP(x);
 }
 
 /* activation ids shared with the python wrapper */
@@ -198,8 +293,14 @@ static void mm_nn(real_t *c, const real_t *a, int rowsA, int colsA,
         const real_t *offRowA = a + (idx % rowsA);
         const real_t *offColB = b + (idx / rowsA) * rowsB;
         real_t x = 0;
-        for (int i = 0; i < colsA; ++i)
-            x += offRowA[i * rowsA] * offColB[i];
+        if (al_) {
+            const real_t *loRowA = al_ + (idx % rowsA), *sumColB = bs_ + (idx / rowsA) * rowsB;
+            for (int i = 0; i < colsA; ++i)
+                x += offRowA[i * rowsA] * sumColB[i] + loRowA[i * rowsA] * offColB[i];
+        } else {
+            for (int i = 0; i < colsA; ++i)
+                x += offRowA[i * rowsA] * offColB[i];
+        }
         c[idx] = add ? c[idx] + x : x;
     }
     MM_RELEASE();
@@ -217,8 +318,14 @@ static void mm_tn(real_t *c, const real_t *a, int rowsA, int colsA,
         const real_t *offColA = a + (idx % colsA) * rowsA;
         const real_t *offColB = b + (idx / colsA) * rowsB;
         real_t x = 0;
-        for (int i = 0; i < rowsA; ++i)
-            x += offColA[i] * offColB[i];
+        if (al_) {
+            const real_t *loColA = al_ + (idx % colsA) * rowsA, *sumColB = bs_ + (idx / colsA) * rowsB;
+            for (int i = 0; i < rowsA; ++i)
+                x += offColA[i] * sumColB[i] + loColA[i] * offColB[i];
+        } else {
+            for (int i = 0; i < rowsA; ++i)
+                x += offColA[i] * offColB[i];
+        }
         c[idx] = add ? c[idx] + x : x;
     }
     MM_RELEASE();
@@ -237,10 +344,16 @@ static void mm_nt(real_t *c, const real_t *a, int rowsA, int colsA,
         const real_t *offRowA = a + (idx % rowsA);
         const real_t *offRowB = b + (idx / rowsA);
         real_t x = 0;
-        for (int i = 0; i < colsA; ++i) {
-            x += *offRowA * *offRowB;
-            offRowA += rowsA;
-            offRowB += rowsB;
+        if (al_) {
+            const real_t *loRowA = al_ + (idx % rowsA), *sumRowB = bs_ + (idx / rowsA);
+            for (int i = 0; i < colsA; ++i)
+                x += offRowA[(size_t)i * rowsA] * sumRowB[(size_t)i * rowsB] + loRowA[(size_t)i * rowsA] * offRowB[(size_t)i * rowsB];
+        } else {
+            for (int i = 0; i < colsA; ++i) {
+                x += *offRowA * *offRowB;
+                offRowA += rowsA;
+                offRowB += rowsB;
+            }
         }
         c[idx] = add ? c[idx] + x : x;
     }
@@ -284,7 +397,10 @@ typedef struct {
     const char *patTypes;
     const real_t *w;          /* flat weights, LstmLayer.hpp:36-55 */
     real_t *dir[2][B_COUNT];  /* per-direction internals */
-    real_t *dq[2][4];         /* operand rounding mode: bf16 copies of the four delta vectors (NULL otherwise) */
+    real_t *dq[2][4];         /* operand rounding mode 1: bf16 copies of the four delta vectors; modes 2 / 3: their hi planes */
+    real_t *dl[2][4];         /* modes 2 / 3: lo planes of the deltas (NULL otherwise) */
+    real_t *yh[2], *ys[2];    /* modes 2 / 3: hi and hi + lo planes of tmpOutputs per direction (NULL otherwise) */
+    const real_t *xbase, *xh, *xs;   /* modes 2 / 3: the preceding layer's outputs and their hi / hi + lo planes */
 } lstm_t;
 
 static void lstm_bind(lstm_t *l, int P, int L, int bidir, real_t bias, int PS, int maxT,
@@ -293,7 +409,8 @@ static void lstm_bind(lstm_t *l, int P, int L, int bidir, real_t bias, int PS, i
     l->P = P; l->L = L; l->dirs = bidir ? 2 : 1; l->H = L / l->dirs;
     l->PS = PS; l->T = T; l->Tmin = Tmin; l->bias = bias;
     l->patTypes = patTypes; l->w = w;
-    memset(l->dq, 0, sizeof l->dq);
+    memset(l->dq, 0, sizeof l->dq); memset(l->dl, 0, sizeof l->dl);
+    l->yh[0] = l->yh[1] = l->ys[0] = l->ys[1] = NULL; l->xbase = l->xh = l->xs = NULL;
     size_t per = (size_t)PS * maxT * l->H;     /* LstmLayer.cu:554 */
     for (int d = 0; d < l->dirs; ++d)
         for (int b = 0; b < B_COUNT; ++b)
@@ -365,8 +482,8 @@ static real_t block_output(const lstm_t *l, int d, int prevOutputDistance,
     return tanh_fn(cellState) * ogAct;
 }
 
-/* the value of a block output as the layer keeps it: fp32, or bf16 in the operand rounding mode */
-#define STORE_Y(v) (g_opround ? bf16_rne(v) : (v))
+/* the value of a block output as the layer keeps it: unrounded, or bf16 in operand rounding mode 1 (CN_PREC_BF16) */
+#define STORE_Y(v) (g_opround == 1 ? bf16_rne(v) : (v))
 
 /*
  * LstmLayer<Cpu>::computeForwardPass, LstmLayer.cu:763-886.
@@ -387,7 +504,7 @@ void orc_lstm_forward(int P, int L, int bidir, real_t bias, int PS, int maxT, in
     for (int d = 0; d < l.dirs; ++d)
         for (int g = 0; g < 4; ++g)
             mm_tn(l.dir[d][actBuf[g]], w_input(&l, w, g, d), P, H, x, P, N, 0);
-    if (g_opround && g_preround)               /* model only: pre-activations (bias term included) stored in bf16 */
+    if (g_opround == 1 && g_preround)               /* model only: pre-activations (bias term included) stored in bf16 */
         for (int d = 0; d < l.dirs; ++d)
             for (int g = 0; g < 4; ++g) {
                 real_t *a = l.dir[d][actBuf[g]];
@@ -401,9 +518,12 @@ void orc_lstm_forward(int P, int L, int bidir, real_t bias, int PS, int maxT, in
     /* :812-829 forward states */
     for (int t = 0; t < T; ++t) {
         if (t != 0)
-            for (int g = 0; g < 4; ++g)        /* :815-818 addProduct(W, true, y[t-1], false) */
+            for (int g = 0; g < 4; ++g) {      /* :815-818 addProduct(W, true, y[t-1], false) */
+                g_x3_recurrent = 1;
                 mm_tn(l.dir[0][actBuf[g]] + (size_t)t * n, w_internal(&l, w, g, 0), H, H,
                       l.dir[0][B_TMPOUT] + (size_t)(t - 1) * n, H, PS, 1);
+                g_x3_recurrent = 0;
+            }
         for (int i = 0; i < n; ++i)            /* :822-828 */
             l.dir[0][B_TMPOUT][(size_t)n * t + i] =
                 STORE_Y(block_output(&l, 0, -n, n * t + i, t == 0, t >= Tmin));
@@ -413,9 +533,12 @@ void orc_lstm_forward(int P, int L, int bidir, real_t bias, int PS, int maxT, in
     if (bidir) {
         for (int t = T - 1; t >= 0; --t) {
             if (t != T - 1)
-                for (int g = 0; g < 4; ++g)    /* :850-853 */
+                for (int g = 0; g < 4; ++g) {  /* :850-853 */
+                    g_x3_recurrent = 1;
                     mm_tn(l.dir[1][actBuf[g]] + (size_t)t * n, w_internal(&l, w, g, 1), H, H,
                           l.dir[1][B_TMPOUT] + (size_t)(t + 1) * n, H, PS, 1);
+                    g_x3_recurrent = 0;
+                }
             for (int i = 0; i < n; ++i)        /* :857-863 */
                 l.dir[1][B_TMPOUT][(size_t)n * t + i] =
                     STORE_Y(block_output(&l, 1, +n, n * t + i, t == T - 1, t >= Tmin));
@@ -433,6 +556,7 @@ void orc_lstm_forward(int P, int L, int bidir, real_t bias, int PS, int maxT, in
     } else {
         memcpy(y, l.dir[0][B_TMPOUT], sizeof(real_t) * (size_t)N * L);
     }
+    x3_cache_release();
 }
 
 /* ComputeBlockErrorsFn::operator(), LstmLayer.cu:213-286 */
@@ -589,6 +713,27 @@ static real_t weight_update(const lstm_t *l, const real_t *plOutputs, int weight
      * tmpOutputs are stored rounded); the bias / peephole sums read the unrounded deltas */
     if (l->dq[0][0] && (weightTypeX == 0x0 || weightTypeX == 0x8))
         offDeltas = &l->dq[isBwStateWeight ? 1 : 0][weightTypeY][tgtBlockIdx];
+    /* modes 2 / 3: the same two cases as split products, sum over patterns of oh*(dh + dl) + ol*dh = oh*dh + oh*dl + ol*dh
+     * (o = the preceding layer's output or y[t -+ 1], d = the delta); hi and hi + lo planes prepared by orc_lstm_backward */
+    if (l->dl[0][0] && (weightTypeX == 0x0 || weightTypeX == 0x8)) {
+        int dd = isBwStateWeight ? 1 : 0;
+        const real_t *base = weightTypeX == 0x0 ? l->xbase : l->dir[dd][B_TMPOUT];
+        const real_t *oh = (weightTypeX == 0x0 ? l->xh : l->yh[dd]) + (offOutputs - base);
+        const real_t *os = (weightTypeX == 0x0 ? l->xs : l->ys[dd]) + (offOutputs - base);
+        const real_t *dh = offDeltas, *dlo = &l->dl[dd][weightTypeY][tgtBlockIdx];
+        if (skipFirstPattern) {
+            oh += parallelSequences * offOutputsInc; os += parallelSequences * offOutputsInc;
+            dh += parallelSequences * effLayerSize;  dlo += parallelSequences * effLayerSize;
+        }
+        int np3 = patternsCount - ((skipFirstPattern || skipLastPattern) ? parallelSequences : 0);
+        real_t wu3 = 0;
+        for (int i = 0; i < np3; ++i) {
+            /* os = oh + ol, so oh*dh + oh*dl + ol*dh = os*dh + oh*dl */
+            wu3 += *os * *dh + *oh * *dlo;
+            oh += offOutputsInc; os += offOutputsInc; dh += effLayerSize; dlo += effLayerSize;
+        }
+        return wu3;
+    }
 
     if (skipFirstPattern) {
         offOutputs += parallelSequences * offOutputsInc;
@@ -639,9 +784,12 @@ void orc_lstm_backward(int P, int L, int bidir, real_t bias, int PS, int maxT, i
     /* :936-951 forward states, t = T-1 .. 0 */
     for (int t = T - 1; t >= 0; --t) {
         if (t != T - 1)
-            for (int g = 0; g < 4; ++g)        /* :939-942 addProduct(W, false, delta[t+1], false) */
+            for (int g = 0; g < 4; ++g) {      /* :939-942 addProduct(W, false, delta[t+1], false) */
+                g_x3_recurrent = 1;
                 mm_nn(l.dir[0][B_TMPERR] + (size_t)t * n, w_internal(&l, w, g, 0), H, H,
                       l.dir[0][deltaBuf[g]] + (size_t)(t + 1) * n, H, PS, 1);
+                g_x3_recurrent = 0;
+            }
         for (int i = 0; i < n; ++i)            /* :946-950 */
             block_errors(&l, 0, -n, n * t + i, t == T - 1, t == 0, t >= Tmin);
     }
@@ -650,9 +798,12 @@ void orc_lstm_backward(int P, int L, int bidir, real_t bias, int PS, int maxT, i
     if (bidir) {
         for (int t = 0; t < T; ++t) {
             if (t != 0)
-                for (int g = 0; g < 4; ++g)    /* :973-976 */
+                for (int g = 0; g < 4; ++g) {  /* :973-976 */
+                    g_x3_recurrent = 1;
                     mm_nn(l.dir[1][B_TMPERR] + (size_t)t * n, w_internal(&l, w, g, 1), H, H,
                           l.dir[1][deltaBuf[g]] + (size_t)(t - 1) * n, H, PS, 1);
+                    g_x3_recurrent = 0;
+                }
             for (int i = 0; i < n; ++i)        /* :980-984 */
                 block_errors(&l, 1, +n, n * t + i, t == 0, t == T - 1, t >= Tmin);
         }
@@ -671,19 +822,31 @@ void orc_lstm_backward(int P, int L, int bidir, real_t bias, int PS, int maxT, i
     /* :1012-1044 weight updates */
     int nw = orc_lstm_weight_count(P, L, bidir);
     real_t *xq = NULL;
-    if (g_opround) {
+    real_t *xh = NULL, *xs = NULL;
+    if (g_opround == 1) {
         xq = rounded_copy(x, (size_t)N * P); x = xq;
         for (int d = 0; d < l.dirs; ++d)
             for (int g = 0; g < 4; ++g) l.dq[d][g] = rounded_copy(l.dir[d][deltaBuf[g]], (size_t)N * H);
+    } else if (g_opround >= 2) {
+        /* (the weight-update products are not recurrent products: g_x3_recurrent is 0 here, all three terms in mode 3 too) */
+        split_copy_b(x, (size_t)N * P, &xh, &xs);
+        l.xbase = x; l.xh = xh; l.xs = xs;
+        for (int d = 0; d < l.dirs; ++d) {
+            split_copy_b(l.dir[d][B_TMPOUT], (size_t)N * H, &l.yh[d], &l.ys[d]);
+            for (int g = 0; g < 4; ++g) split_copy(l.dir[d][deltaBuf[g]], (size_t)N * H, &l.dq[d][g], &l.dl[d][g]);
+        }
     }
     ORC_PAR((long)nw * N)
     for (int i = 0; i < nw; ++i)
         wu[i] = weight_update(&l, x, i);
     if (g_opround) {
-        free(xq);
-        for (int d = 0; d < l.dirs; ++d)
-            for (int g = 0; g < 4; ++g) free(l.dq[d][g]);
+        free(xq); free(xh); free(xs);
+        for (int d = 0; d < l.dirs; ++d) {
+            free(l.yh[d]); free(l.ys[d]);
+            for (int g = 0; g < 4; ++g) { free(l.dq[d][g]); free(l.dl[d][g]); }
+        }
     }
+    x3_cache_release();
 }
 
 /* ------------------------------------------------------------------------- */
@@ -800,7 +963,7 @@ real_t orc_mcc_error(int L, int N, const int *targetClasses, const real_t *outpu
         if (targetClass == -1) continue;
         real_t p = outputs[(size_t)patIdx * L + targetClass];
         real_t targetProb = (NL_MIN > p ? NL_MIN : p);
-        error += logf(targetProb);
+        error += R_LOG(targetProb);
     }
     return -error;
 }
@@ -882,7 +1045,7 @@ real_t orc_post_error(int kind, int L, int N, const char *patTypes, const real_t
                 real_t diff = outputs[(size_t)patIdx * L + i] - targets[(size_t)patIdx * L + i];
                 sum += diff * diff;
             }
-            s += sqrtf(sum / L);
+            s += R_SQRT(sum / L);
         }
         return s;
     }
@@ -899,11 +1062,11 @@ real_t orc_post_error(int kind, int L, int N, const char *patTypes, const real_t
             real_t target = targets[index];
             real_t ftarget = (NL_MIN > target ? NL_MIN : target);
             real_t o = (NL_MIN > output ? NL_MIN : output);
-            s += target * logf(ftarget / o);
+            s += target * R_LOG(ftarget / o);
         } else {   /* POST_BINARY, L == 1 */
             real_t act = (output > NL_MIN ? output : NL_MIN);
             real_t targetProb = (targets[index] > 0 ? act : 1 - act);
-            s += -logf(targetProb);
+            s += -R_LOG(targetProb);
         }
     }
     if (kind == POST_SSE || kind == POST_WEIGHTEDSSE || kind == POST_SSE_MASK) s = (real_t)0.5 * s;
@@ -939,7 +1102,7 @@ void orc_post_backward(int kind, int L, int N, const char *patTypes, const real_
                 real_t diff = outputs[(size_t)patIdx * L + i] - targets[(size_t)patIdx * L + i];
                 sum += diff * diff;
             }
-            rmse = sqrtf(sum / L);
+            rmse = R_SQRT(sum / L);
         }
         for (int i = 0; i < L; ++i) {
             size_t index = (size_t)patIdx * L + i;

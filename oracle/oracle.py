@@ -9,16 +9,27 @@ restatement layer by layer in the call order of the reference:
   Optimizer::_processDataSet     (currennt_lib/src/optimizers/Optimizer.cu:37-104)
 """
 import ctypes as C
+import importlib.util
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "libcurrennt_oracle.so")
+# One source, two bindings.  This module bound to libcurrennt_oracle.so (real_t = float, fp32 arrays) is the oracle.
+# real64() executes the same file a second time with _DOUBLE preset: the same OracleNetwork / set_threads / operand_rounding
+# API bound to libcurrennt_oracle64.so (currennt_oracle.c built with -DORC_DOUBLE, float64 arrays): the fp64 statement of the path and the home of the
+# split-operand model of CN_PREC_BF16X3.  backend="ref" (the reference's object code) exists in fp32 only.
+_DOUBLE = bool(globals().get("_DOUBLE", False))
+REAL = np.float64 if _DOUBLE else np.float32
+_creal = C.c_double if _DOUBLE else C.c_float
+_LIB_NAME = "libcurrennt_oracle64.so" if _DOUBLE else "libcurrennt_oracle.so"
+_LIB_PATH = os.path.join(_HERE, _LIB_NAME)
 _lib = None
+_real64 = None
 
-f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
+f32p = np.ctypeslib.ndpointer(dtype=REAL, flags="C_CONTIGUOUS")      # real_t *: fp32, or fp64 in the double binding
 i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 i8p = np.ctypeslib.ndpointer(dtype=np.int8, flags="C_CONTIGUOUS")
 
@@ -27,8 +38,27 @@ POST = {"sse": 0, "weightedsse": 1, "wf": 2, "sse_mask": 2, "ce": 3, "rmse": 4, 
 
 
 def build():
-    """Compile oracle/libcurrennt_oracle.so with gcc (seconds)."""
-    subprocess.check_call(["make", "-s", "-C", _HERE, "libcurrennt_oracle.so"])
+    """Compile this binding's library (oracle/libcurrennt_oracle.so or libcurrennt_oracle64.so) with gcc (seconds)."""
+    subprocess.check_call(["make", "-s", "-C", _HERE, _LIB_NAME])
+
+
+def real64():
+    """The double-precision oracle: a sibling namespace with the same API (OracleNetwork, set_threads, get_threads,
+    operand_rounding, lib) bound to libcurrennt_oracle64.so; arrays are float64.  Its thread count and operand rounding mode
+    are its own (another shared library).  Operand rounding knows "bf16x3" and "bf16x3_minus_one" there as well as "bf16"."""
+    global _real64
+    if _DOUBLE:
+        return sys.modules[__name__]
+    if _real64 is None:
+        spec = importlib.util.spec_from_file_location("currennt_oracle64", os.path.abspath(__file__))
+        mod = importlib.util.module_from_spec(spec)
+        mod._DOUBLE = True
+        sys.modules["currennt_oracle64"] = mod
+        spec.loader.exec_module(mod)
+        if mod.lib().orc_real_bytes() != 8:
+            raise RuntimeError("libcurrennt_oracle64.so is not a double build")
+        _real64 = mod
+    return _real64
 
 
 def lib():
@@ -40,7 +70,7 @@ def lib():
             or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src)):
         build()
     L = C.CDLL(_LIB_PATH)
-    ci, cf, vp = C.c_int, C.c_float, C.c_void_p
+    ci, cf, vp = C.c_int, _creal, C.c_void_p
     L.orc_matmul.argtypes = [ci, f32p, f32p, ci, ci, f32p, ci, ci, ci]
     L.orc_lstm_weight_count.argtypes = [ci, ci, ci]
     L.orc_lstm_weight_count.restype = ci
@@ -74,6 +104,7 @@ def lib():
     L.orc_set_preact_rounding.argtypes = [ci]
     L.orc_get_preact_rounding.restype = ci
     L.orc_get_threads.restype = ci
+    L.orc_real_bytes.restype = ci
     L.orc_set_threads(int(os.environ.get("ORACLE_THREADS", "1")))
     _lib = L
     return L
@@ -96,14 +127,21 @@ def set_operand_rounding(mode):
     their outputs rounded; accumulation, states, activations (libm), bias / peephole terms and their gradient sums stay
     fp32 in the reference's order (currennt_oracle.c, "operand rounding").  The HIP bf16 path is then held to the oracle at
     summation-order + v_exp_f32 / v_rcp_f32 distance instead of 3e-2.  Only the C restatement has the mode
-    (OracleNetwork(backend="oracle")); oracle/_ref is the reference's object code and has no such switch."""
-    if mode not in (None, "f32", "bf16"):
-        raise ValueError("operand rounding mode must be None, 'f32' or 'bf16'")
-    lib().orc_set_operand_rounding(1 if mode == "bf16" else 0)
+    (OracleNetwork(backend="oracle")); oracle/_ref is the reference's object code and has no such switch.
+    "bf16x3": a MODEL of CN_PREC_BF16X3, meant for real64() -- at the same call sites each product term a * b becomes
+    ah * bh + ah * bl + al * bh with ah = bf16(a as fp32), al = bf16(a - ah); nothing is stored rounded, everything else stays in the
+    binding's precision.  "bf16x3_minus_one" (tests only) also drops ah * bl in the recurrent products: a kernel that lost one
+    of its three MFMAs (currennt_oracle.c, "Modes 2 and 3")."""
+    if mode not in _ROUNDING:
+        raise ValueError("operand rounding mode must be one of %r" % (list(_ROUNDING),))
+    lib().orc_set_operand_rounding(_ROUNDING[mode])
+
+
+_ROUNDING = {None: 0, "f32": 0, "bf16": 1, "bf16x3": 2, "bf16x3_minus_one": 3}
 
 
 def get_operand_rounding():
-    return "bf16" if lib().orc_get_operand_rounding() else None
+    return [None, "bf16", "bf16x3", "bf16x3_minus_one"][lib().orc_get_operand_rounding()]
 
 
 class operand_rounding:
@@ -185,8 +223,8 @@ class _Layer:
         self.post = self.type == "multiclass_classification" or self.type in POST
         n = PS * maxT * self.size
         # PostOutputLayer writes into the preceding layer's outputErrors (PostOutputLayer.cpp:43-47)
-        self.outputs = np.zeros(n, np.float32) if not self.post else None
-        self.outputErrors = np.zeros(n, np.float32) if not self.post else None
+        self.outputs = np.zeros(n, REAL) if not self.post else None
+        self.outputErrors = np.zeros(n, REAL) if not self.post else None
         self.weights = self.weightUpdates = None
         if self.trainable:
             P = prev.size
@@ -197,20 +235,20 @@ class _Layer:
                 nw = lib().orc_lstm_weight_count(P, self.size, int(self.bidir))
                 dirs = 2 if self.bidir else 1
                 self.H = self.size // dirs
-                self.bufs = np.zeros(dirs * 12 * PS * maxT * self.H, np.float32)
+                self.bufs = np.zeros(dirs * 12 * PS * maxT * self.H, REAL)
             else:
                 nw = lib().orc_ff_weight_count(P, self.size)
-                self.patTmp = np.zeros(PS * maxT, np.float32)
+                self.patTmp = np.zeros(PS * maxT, REAL)
             w = weights.get(self.name) if weights else None
             if w is None:
                 raise RuntimeError("oracle networks need explicit weights (SURVEY Q13)")
-            flat = np.concatenate([np.asarray(w["input"], np.float32),
-                                   np.asarray(w["bias"], np.float32),
-                                   np.asarray(w["internal"], np.float32)])
+            flat = np.concatenate([np.asarray(w["input"], REAL),
+                                   np.asarray(w["bias"], REAL),
+                                   np.asarray(w["internal"], REAL)])
             if flat.size != nw:
                 raise RuntimeError("Invalid number of weights for layer '%s'" % self.name)
             self.weights = np.ascontiguousarray(flat)
-            self.weightUpdates = np.zeros(nw, np.float32)
+            self.weightUpdates = np.zeros(nw, REAL)
 
     def internal(self, which, d=0):
         """LSTM per-direction internal vector by reference name (LstmLayer.hpp:88-100)."""
@@ -225,6 +263,8 @@ class OracleNetwork:
     def __init__(self, layers, weights, parallel_sequences, max_seq_length, backend="oracle"):
         """backend "oracle": the C restatement; "ref": the same call sequence through oracle/_ref, i.e. the reference's own
         compiled functors and Cpu GEMM (tests/test_oracle_ref.py holds the two bit-equal)."""
+        if backend != "oracle" and _DOUBLE:
+            raise RuntimeError("oracle/_ref (the reference's object code) is fp32 only")
         self._L = lib() if backend == "oracle" else ref_lib()
         self.PS, self.maxT = parallel_sequences, max_seq_length
         self.layers = []
@@ -246,15 +286,15 @@ class OracleNetwork:
         self.T, self.Tmin = int(frac["T"]), int(frac["Tmin"])
         self.N = self.T * self.PS
         self.patTypes = np.ascontiguousarray(frac["patTypes"], np.int8)
-        x = np.ascontiguousarray(frac["inputs"], np.float32).reshape(-1)
+        x = np.ascontiguousarray(frac["inputs"], REAL).reshape(-1)
         self.layers[0].outputs[:x.size] = x
         post = self.layers[-1]
         if post.type == "multiclass_classification":
             self.targetClasses = np.ascontiguousarray(frac["targetClasses"], np.int32)
         elif post.type == "binary_classification":      # BinaryClassificationLayer.cu:157-164
-            self.targets = np.ascontiguousarray(frac["targetClasses"], np.float32).reshape(-1)
+            self.targets = np.ascontiguousarray(frac["targetClasses"], REAL).reshape(-1)
         else:
-            self.targets = np.ascontiguousarray(frac["targets"], np.float32).reshape(-1)
+            self.targets = np.ascontiguousarray(frac["targets"], REAL).reshape(-1)
 
     # -- NeuralNetwork::computeForwardPass (NeuralNetwork.cpp:168-173)
     def compute_forward_pass(self):

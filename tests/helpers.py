@@ -93,3 +93,41 @@ def load_ref_golden(name):
     tkey = pre + ("targetClasses" if pre + "targetClasses" in z.files else "targets")      # real-valued targets: sse case
     ts = [z[tkey][off[i]:off[i + 1]] for i in range(len(lens))]
     return layers, weights, xs, ts, int(z[pre + "PS"]), exp
+
+
+# ---- references for the fp64-relative bounds (tests/test_oracle_fp64.py, tests/test_gpu_long_fp64.py) ----------------------
+
+def oracle_reference(ons, layers, weights, frac, PS, rounding=None):
+    """One forward + backward pass of an oracle namespace (`orc` = fp32, `orc.real64()` = double), optionally under an operand
+    rounding model, as a dict of float64 arrays in the layout the comparisons use: posteriors of the real frames `post`
+    [frames][C], `error`, `correct`, `grad/<layer>`, `err/<layer>` (propagated errors into a trainable layer, real frames), and
+    `ylast`: the last LSTM layer's outputs [T][PS][L]."""
+    with ons.operand_rounding(rounding):
+        ref = ons.OracleNetwork(layers, weights, PS, frac["T"])
+        ref.load_sequences(frac); ref.compute_forward_pass()
+        out = {"error": ref.calculate_error(), "correct": ref.count_correct_classifications()}
+        ref.compute_backward_pass()
+    real = real_mask(frac)
+    C = layers[-1]["size"]
+    out["post"] = ref.outputs().reshape(-1, C)[real].astype(np.float64)
+    for lay in ref.trainable_layers():
+        out["grad/" + lay.name] = lay.weightUpdates.astype(np.float64)
+        if lay.prev.trainable:
+            out["err/" + lay.prev.name] = lay.prev.outputErrors[:ref.N * lay.prev.size].reshape(-1, lay.prev.size)[real].astype(np.float64)
+        if lay.type in ("lstm", "blstm"):
+            out["ylast"] = lay.outputs[:ref.N * lay.size].reshape(ref.T, PS, lay.size).astype(np.float64)
+    return out
+
+
+def fp64_distances(got, r64, t_long, slot=0):
+    """The compared quantities of `got` against the double oracle's `r64` (both as oracle_reference returns them):
+    `post` posteriors max-abs; `grad/<layer>`, `err/<layer>` max-abs over the layer's max (rel_err of test_gpu_parity);
+    `y_first` / `y_last`: the last LSTM layer's outputs at frame 0 and frame t_long - 1 of `slot` (the longest sequence:
+    the backward direction has run all its steps at frame 0, the forward direction at the last frame), max-abs."""
+    d = {"post": float(np.abs(got["post"] - r64["post"]).max())}
+    for k in r64:
+        if k.startswith("grad/") or k.startswith("err/"):
+            d[k] = float(np.abs(got[k] - r64[k]).max() / max(1e-12, np.abs(r64[k]).max()))
+    d["y_first"] = float(np.abs(got["ylast"][0, slot] - r64["ylast"][0, slot]).max())
+    d["y_last"] = float(np.abs(got["ylast"][t_long - 1, slot] - r64["ylast"][t_long - 1, slot]).max())
+    return d

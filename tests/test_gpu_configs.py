@@ -215,7 +215,7 @@ def test_config1_reading_b_three_layers_of_250_units_per_direction(pkg, orc, pre
 
 def test_config4_long_utterance_T2000_cluster_vs_oracle(pkg, orc):
     """BASELINE configs[4] layer shape: 39 -> blstm1024 -> softmax183, T = 2000, bf16 8-CU cluster kernels against the
-    fp32 oracle (about 90 GFLOP of oracle work).  Ragged: one sequence ends at 1 501, the fraction has an unused slot.
+    fp32 oracle (about 90 GFLOP of oracle work).  Ragged: one sequence ends at 1 501 (the three sequences fill the fraction's three slots).
     The oracle runs multi-threaded here (bit-identical to its single-threaded order, oracle.set_threads)."""
     rng = np.random.RandomState(53)
     P, C, PS = 39, 183, 3

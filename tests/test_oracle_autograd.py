@@ -88,6 +88,67 @@ def test_autograd_matches_oracle(pkg, orc):
         assert np.abs(g - gr).max() < 2e-4 * max(1.0, np.abs(g).max()), (lay.name, np.abs(g - gr).max())
 
 
+def _autograd_stack(frac, lens, hidden, P, C, flat_weights):
+    """The fp64 autograd statement of a stack of (b)lstm layers + softmax + summed cross entropy on one fraction.
+    flat_weights: {layer name: flat float64 array in the oracle's layout}.  -> (loss, posteriors [frames][C] of the real frames,
+    {layer name: gradient})."""
+    T, PS = frac["T"], frac["PS"]
+    params = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in flat_weights.items()}
+    h = torch.tensor(frac["inputs"].reshape(T, PS, P).astype(np.float64))
+    lens = list(lens) + [0] * (PS - len(lens))
+    prev = P
+    for i, (kind, size) in enumerate(hidden):
+        h = lstm_layer(h, lens, params["%s_%d" % (kind, i)], prev, size, kind == "blstm", 1.0)
+        prev = size
+    wo = params["output"]
+    z = h @ wo[:C * prev].reshape(C, prev).T + 1.0 * wo[C * prev:]
+    logp = torch.log_softmax(z, dim=2)
+    tc = torch.tensor(frac["targetClasses"].reshape(T, PS).astype(np.int64))
+    mask = tc >= 0
+    loss = -(logp.gather(2, tc.clamp(min=0).unsqueeze(2)).squeeze(2) * mask).sum()
+    loss.backward()
+    post = torch.exp(logp).detach().numpy().reshape(-1, C)[real_mask(frac)]
+    return float(loss.detach()), post, {k: v.grad.numpy() for k, v in params.items()}
+
+
+DOUBLE_CASES = {
+    # name: (P, hidden, C, lengths, PS, weight scale, seed)
+    "toy_blstm8_lstm4": (3, [("blstm", 8), ("lstm", 4)], 3, [6, 4, 2], 3, 0.5, 3),               # the case of test_autograd_matches_oracle
+    "ragged_3xblstm_T40": (5, [("blstm", 12), ("blstm", 10), ("blstm", 6)], 7, [40, 37, 37, 22, 9, 1], 7, 0.4, 13),   # one unused slot
+}
+
+
+def test_double_oracle_equals_fp64_autograd_to_rounding_noise(pkg, orc):
+    """The DOUBLE build of the oracle (oracle.real64(): the same C source with real_t = double) against the fp64 autograd model:
+    two independent fp64 statements of the same equations, so they agree to rounding noise -- 1e-10 relative on the loss, the
+    posteriors and every gradient (measured: at most 7e-16), against the 1e-4 / 1e-5 / 2e-4 that the fp32 oracle can be
+    held to above.  This pins the restated time loops (both directions, ragged lengths, dummy slots, layer stacking) five orders
+    tighter than KAT-0's recorded digits.  No delta may reach the +-1 clip (asserted): the clip is not part of the gradient."""
+    o64 = orc.real64()
+    for name, (P, hidden, C, lens, PS, scale, seed) in sorted(DOUBLE_CASES.items()):
+        rng = np.random.RandomState(seed)
+        layers = net_desc(P, hidden, C)
+        weights = random_weights(layers, rng, scale)
+        xs, ts = random_sequences(rng, lens, P, C=C)
+        frac = pkg.make_fraction(xs, ts, PS)
+        ref = o64.OracleNetwork(layers, weights, PS, frac["T"])
+        ref.load_sequences(frac); ref.compute_forward_pass()
+        err = ref.calculate_error(); ref.compute_backward_pass()
+        assert ref.outputs().dtype == np.float64
+        loss, post, grads = _autograd_stack(frac, lens, hidden, P, C, {lay.name: lay.weights for lay in ref.trainable_layers()})
+        worst = {"loss": abs(loss - err) / max(1.0, abs(loss)),
+                 "post": float(np.abs(post - ref.outputs().reshape(-1, C)[real_mask(frac)]).max())}
+        for lay in ref.trainable_layers():
+            if lay.type in ("lstm", "blstm"):
+                deltas = np.concatenate([lay.internal(n, d) for n in ("niDeltas", "igDeltas", "fgDeltas", "ogDeltas")
+                                         for d in range(2 if lay.type == "blstm" else 1)])
+                assert np.abs(deltas).max() < 1.0, (name, lay.name)
+            g = grads[lay.name]
+            worst["grad/" + lay.name] = float(np.abs(g - lay.weightUpdates).max() / np.abs(g).max())
+        print(name, {k: float("%.2g" % v) for k, v in worst.items()})
+        assert all(v <= 1e-10 for v in worst.values()), (name, worst)
+
+
 def _post_loss64(kind, y, t, L):
     """fp64 statement of calculateError() of the post output layers (formulas of the layer headers)."""
     if kind == "sse":
