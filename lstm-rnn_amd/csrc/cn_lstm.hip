@@ -73,19 +73,6 @@ __device__ unsigned long long cn_stamp_buf[2][16][8];
 #define STAMP_STORE(k)
 #endif
 
-// element `elem` of an array of T at a wave-uniform base: the byte offset stays a 32-bit VGPR (saddr form)
-// Keeps every lane of an MFMA accumulator tuple allocated until `after` (a value computed from the tuple's results) exists.
-// Lanes whose rows are never read are dead to the register allocator, which may hand them to another value while the MFMA
-// that will still write them is in flight.  For ordinary instructions the hazard recognizer then inserts the wait states; the
-// staged-operand copies of these kernels are inline asm, which it does not look into: observed once (an experimental build,
-// T = 1 path): `v_smfmac v[140:143]` followed by the asm copy `v_mov_b32 v142, ...`, overwritten when the MFMA retired.
-#define KEEP_TUPLE(tuple, after) asm volatile("" :: "v"(tuple), "v"(after))
-
-template <typename T> __device__ __forceinline__ T &at32(const void *base, unsigned elem)
-{
-    return *(T *)((char *)base + elem * (unsigned)sizeof(T));
-}
-
 // dtab[t][j] = (t >= Tmin && patTypes[t][s0 + j] == NONE) for the 4*RPL sequences of a workgroup.  One dword
 // (four sequences) per thread and round, so a pass of up to blockDim.x / RPL time steps is a single round
 // trip; PS and s0 are multiples of 4, the rows are dword aligned.
@@ -396,7 +383,6 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_fwd_kernel(LstmR
             for (int r = 0; r < RPL; ++r) {
                 const bool dummy = dummy_[r];
                 const float cp = cst[u][r];
-                // ComputeBlockOutputFn, LstmLayer.cu:87-136 (bias is already inside the pre-activation)
                 float s_[4];                             // recurrent sums of this sequence (SP: its two tile rows)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)          // SP: the pre-activation entered through the even row's accumulator
@@ -405,15 +391,10 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_fwd_kernel(LstmR
 #pragma unroll
                     for (int g = 0; g < 4; ++g) { if constexpr (SP) KEEP_TUPLE(accp[g], s_[g]); else KEEP_TUPLE(acc[u][g], s_[g]); }
                 }
-                const float ni = tanh_ref<ACC>(s_[0]);
-                const float ig = logistic<ACC>(s_[1] + cp * pi[u]);
-                const float fg = logistic<ACC>(s_[2] + cp * pf[u]);
-                const float cs = ni * ig + cp * fg;
-                const float og = logistic<ACC>(s_[3] + cs * po[u]);
-                const float th = tanh_ref<ACC>(cs);
-                const float y = th * og;
-                float yo = dummy ? 0.f : y;
-                const float co = dummy ? 0.f : cs;     // :78-85 (zeroed in both directions here)
+                // ComputeBlockOutputFn (cn_lstm_device.h; bias is already inside the pre-activation)
+                const CellOut o = lstm_cell_fwd<ACC, false>(s_, cp, pi[u], pf[u], po[u], dummy);
+                const float co = o.co, th = o.th;
+                float yo = o.yo;
                 cst[u][r] = co;
 #ifdef CN_STAMP
                 if (u == UG - 1 && r == RPL - 1) { STAMP_FORCE(yo) STAMP(3) }
@@ -425,7 +406,7 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_fwd_kernel(LstmR
                     *(__bf16 *)(ynxt + oT[u][r]) = yh;
                     *(__bf16 *)(ynxt + plane + oT[u][r]) = yl;
                 } else *(__bf16 *)(ynxt + oT[u][r]) = (__bf16)yo;
-                const f32x4 av = {ni, ig, fg, og};       // (dummy slots: never read back)
+                const f32x4 av = {o.ni, o.ig, o.fg, o.og};       // (dummy slots: never read back)
                 *(f32x4 *)&at32<float>(actsT, oA[u][r]) = av;
                 at32<float>(cellT, oC[u][r]) = co;
                 at32<float>(thT, oC[u][r]) = th;          // the backward pass reads it back instead of recomputing it (dummy slots: never used)

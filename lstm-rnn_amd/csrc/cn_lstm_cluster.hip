@@ -75,9 +75,8 @@
 #include <type_traits>
 #include <mutex>
 
-#define KEEP_TUPLE(tuple, after) asm volatile("" :: "v"(tuple), "v"(after))
 
-// In-kernel segment timing of the delta-exchange backward kernel (tools/stamps_cl.py; `make variantc NAME=clstamp DEFS=-DCN_CL_STAMP`;
+// In-kernel segment timing of the delta-exchange backward kernel (tools/stamps_cl.py; `make variant FILE=cn_lstm_cluster NAME=clstamp DEFS=-DCN_CL_STAMP`;
 // never defined in the shipped build): wave w of cluster 0, member 0 sums s_memtime deltas per step segment
 #ifdef CN_CL_STAMP
 __device__ unsigned long long cn_cl_stamp_buf[8][8], cn_cl_stamp_buf_f[8][8];
@@ -914,7 +913,7 @@ __global__ __launch_bounds__(UPC * 4) void lstm_bwd_cluster_kernel(LstmRec p)
             float dig = ig * (1.0f - ig) * ni * ec;
             dni = clip1(dni); dig = clip1(dig); dfg = clip1(dfg); dog = clip1(dog);
             dni = dummy ? 0.f : dni; dig = dummy ? 0.f : dig; dfg = dummy ? 0.f : dfg; dog = dummy ? 0.f : dog;
-            ec = dummy ? 0.f : ec;      // selects, not a branch (see cn_lstm.hip)
+            ec = dummy ? 0.f : ec;      // selects, not a branch (see lstm_bwd_kernel, cn_lstm.hip)
             fgn[r] = dummy ? 0.f : fg;
             ecn[r] = ec; dign[r] = dig; dfgn[r] = dfg;
             ccur[r] = cp;
@@ -1235,7 +1234,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_s2c_kernel(LstmRec p)
     u64 *xbase = p.xch + (long)cluster * 2 * CS * (G * NT);
     bool gaveup = false;
 
-    float fgn = 0.f, ecn = 0.f, dign = 0.f, dfgn = 0.f, ccur;
+    CellCarry car = {0.f, 0.f, 0.f, 0.f};
+    float ccur;
     float sb[4] = {0.f, 0.f, 0.f, 0.f}, spi = 0.f, spf = 0.f, spo = 0.f;
 
     const int tfirst = d ? 0 : T - 1;
@@ -1294,30 +1294,10 @@ __global__ __launch_bounds__(256) void lstm_bwd_s2c_kernel(LstmRec p)
         const float e = (accA[0] + accA[1]) + (accB[2] + accB[3]);
         KEEP_TUPLE(accA, e); KEEP_TUPLE(accB, e);
 
-        // ComputeBlockErrorsFn, LstmLayer.cu:236-285, the explicit operation sequence of lstm_bwd_s2_kernel
-        const bool dummy = dmy != 0;
-        const float ni = a_[0], ig = a_[1], fg = a_[2], og = a_[3];
-        const float cs = ccur, th = th_;
-        float dog, ec, dni, dfg, dig;
-        {
-#pragma clang fp contract(off)
-            const float m = dummy ? 0.f : 1.f;
-            const float t2p = __builtin_fmaf(-og, og, og) * th;
-            const float vp = og * __builtin_fmaf(-th, th, 1.0f);
-            const float w = __builtin_fmaf(po, t2p, vp);
-            const float d2p = ig * __builtin_fmaf(-ni, ni, 1.0f);
-            const float d3p = __builtin_fmaf(-fg, fg, fg) * cp;              // cp = 0 at lastCall
-            const float d4p = __builtin_fmaf(-ig, ig, ig) * ni;
-            float car = fgn * ecn;                                          // zero carry at firstCall
-            car = __builtin_fmaf(pi, dign, car);
-            car = __builtin_fmaf(pf, dfgn, car);
-            dog = (t2p * m) * e;
-            ec = __builtin_fmaf(e, w * m, car * m);
-            dni = (d2p * m) * ec; dfg = (d3p * m) * ec; dig = (d4p * m) * ec;
-            fgn = fg * m;
-        }
-        dni = clip1(dni); dig = clip1(dig); dfg = clip1(dfg); dog = clip1(dog);
-        ecn = ec; dign = dig; dfgn = dfg;
+        // ComputeBlockErrorsFn as the explicit operation sequence (cn_lstm_device.h), the same call as lstm_bwd_s2_kernel
+        const float cs = ccur;
+        float dni, dig, dfg, dog;
+        lstm_cell_bwd_explicit(e, a_, cp, th_, pi, pf, po, car, dmy != 0, dni, dig, dfg, dog);
         ccur = cp;
         sb[0] += dni; sb[1] += dig; sb[2] += dfg; sb[3] += dog;
         spi = __builtin_fmaf(cp, dig, spi); spf = __builtin_fmaf(cp, dfg, spf); spo = __builtin_fmaf(cs, dog, spo);
@@ -1358,7 +1338,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_s2c_kernel(LstmRec p)
 // fragments = all 256 AGPRs.  Members publish a granule of zeros for "step -1" in front of the loop, so that step 0 polls like
 // every other step.  Dummy slots as in the other hand-written loops: the pattern type alone decides.
 #include "cn_lstm_s2c_loop.inc"
-// CN_S2C_STAMP (tools/stamps_s2c.py; `make variantc NAME=s2cstamp DEFS=-DCN_S2C_STAMP`; never in the shipped build): every wave of
+// CN_S2C_STAMP (tools/stamps_s2c.py; `make variant FILE=cn_lstm_cluster NAME=s2cstamp DEFS=-DCN_S2C_STAMP`; never in the shipped build): every wave of
 // workgroup 0 sums s_memtime deltas per step segment (the segments are named in tools/gen_s2c_loop.py)
 #ifdef CN_S2C_STAMP
 __device__ unsigned cn_s2c_stamp_buf[4][8];

@@ -1,5 +1,6 @@
-// Device helpers shared by the recurrent LSTM kernels (cn_lstm.hip, cn_lstm_cluster.hip): the reference's
-// activation functions, the 16x16 MFMA step and the LDS-only workgroup barrier.
+// Device helpers shared by the recurrent LSTM kernels (cn_lstm.hip, cn_lstm_s2.hip, cn_lstm_cluster.hip): the reference's
+// activation functions and LSTM cell (forward and backward), the 16x16 MFMA steps, the split-bf16 operands, the gradient
+// sums and the LDS-only workgroup barrier.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -130,6 +131,93 @@ __device__ __forceinline__ void sp_load_split(const float *p, u32x8 &hi, u32x8 &
     split8(*(const f32x4 *)p, *(const f32x4 *)(p + 4), h0, l0);
     split8(*(const f32x4 *)(p + 8), *(const f32x4 *)(p + 12), h1, l1);
     hi = sp_join(h0, h1); lo = sp_join(l0, l1);
+}
+
+// Keeps every lane of an MFMA accumulator tuple allocated until `after` (a value computed from the tuple's results) exists.
+// Lanes whose rows are never read are dead to the register allocator, which may hand them to another value while the MFMA
+// that will still write them is in flight.  For ordinary instructions the hazard recognizer then inserts the wait states; the
+// staged-operand copies of these kernels are inline asm, which it does not look into: observed once (an experimental build,
+// T = 1 path): `v_smfmac v[140:143]` followed by the asm copy `v_mov_b32 v142, ...`, overwritten when the MFMA retired.
+// The pin is part of a kernel's instruction stream (the register allocator reacts to where it sits): it stays at the call
+// site, at its point of the data flow.
+#define KEEP_TUPLE(tuple, after) asm volatile("" :: "v"(tuple), "v"(after))
+
+// element `elem` of an array of T at a wave-uniform base: the byte offset stays a 32-bit VGPR (saddr form)
+template <typename T> __device__ __forceinline__ T &at32(const void *base, unsigned elem)
+{
+    return *(T *)((char *)base + elem * (unsigned)sizeof(T));
+}
+
+// ---- the LSTM cell ----------------------------------------------------------------------------------------------------
+// What differs between kernels (where the gate sums come from, the KEEP_TUPLE pins, the stamps, the stores) stays at the call
+// site.  The arithmetic has two forms that are NOT interchangeable:
+//   contracted (EXPLICIT = false): plain C++ expressions, a * b + c left to the compiler's contraction -- lstm_fwd_kernel
+//     here; the cluster kernels and the contracted backward kernels (lstm_bwd_kernel, lstm_bwd_cluster_kernel,
+//     lstm_bwd_cluster_psum_kernel) still state this form in place: moved behind a call they compile to other register
+//     counts, spills and packed / scalar multiplies (tools/isa_same.py), so they wait for a spelling that does not;
+//   explicit (EXPLICIT = true / lstm_cell_bwd_explicit): the fused operations written out -- the compiled twins of the
+//     hand-written and generated loops (lstm_fwd_s2_kernel, lstm_fwd_s2w_kernel, lstm_bwd_s2_kernel, lstm_bwd_s2c_kernel),
+//     which tests hold bit-equal to those loops: their rounding must not depend on the optimiser.
+// Forward, ComputeBlockOutputFn (LstmLayer.cu:87-136): s = the four gate sums n, i, f, o (bias and recurrent part inside), cp
+// the previous cell state.  co / yo are the cell state and the output with dummy slots zeroed (:78-85, in both directions here);
+// the activations and th of a dummy slot are never read back.
+struct CellOut { float ni, ig, fg, og, th, co, yo; };
+template <bool ACC, bool EXPLICIT>
+__device__ __forceinline__ CellOut lstm_cell_fwd(const float (&s)[4], float cp, float pi, float pf, float po, bool dummy)
+{
+    CellOut c;
+    c.ni = tanh_ref<ACC>(s[0]);
+    c.ig = logistic<ACC>(s[1] + cp * pi);
+    c.fg = logistic<ACC>(s[2] + cp * pf);
+    float cs;
+    if constexpr (EXPLICIT) cs = __builtin_fmaf(c.ni, c.ig, cp * c.fg);
+    else cs = c.ni * c.ig + cp * c.fg;
+    c.og = logistic<ACC>(s[3] + cs * po);
+    c.th = tanh_ref<ACC>(cs);
+    const float y = c.th * c.og;
+    c.yo = dummy ? 0.f : y;
+    c.co = dummy ? 0.f : cs;
+    return c;
+}
+
+// what a backward step hands to the next one (the step of t+1 in time order): forget gate, cell state error, input and
+// forget gate deltas; all zero at firstCall
+struct CellCarry { float fg, ec, dig, dfg; };
+
+// Backward, ComputeBlockErrorsFn (LstmLayer.cu:236-285), as an explicit operation sequence: e = outputErrors + the recurrent
+// product, a = the activations n, i, f, o, th = tanh(cell state), cp the previous cell state (0 at lastCall); out come the
+// deltas, clipped when stored (:281-285; the cell state error is not, and ec uses the unclipped dog, :262-263), and the carry
+// is updated in place.  No contraction is left to the compiler: the hand-written and generated backward loops issue exactly
+// these operations and are held bit-equal.  Everything that does not depend on e is formed first -- in
+// the hand-written loops one step early, in the shadow of the LDS hand-off --, and the dummy-slot rule enters as a factor
+// m = 0 / 1, so that behind the product only
+//   dog = [m og (1 - og) th] e,   ec = e [m (og (1 - th^2) + po og (1 - og) th)] + m (fg' ec' + pi dig' + pf dfg')
+//   dni = [m ig (1 - ni^2)] ec,   dfg = [m fg (1 - fg) cp] ec,   dig = [m ig (1 - ig) ni] ec      (' = carried from t+1)
+// remain: one multiply or fma each, then the clips.
+__device__ __forceinline__ void lstm_cell_bwd_explicit(float e, const f32x4 &a, float cp, float th, float pi, float pf, float po,
+                                                       CellCarry &c, bool dummy, float &dni, float &dig, float &dfg, float &dog)
+{
+    const float ni = a[0], ig = a[1], fg = a[2], og = a[3];
+    float ec;
+    {
+#pragma clang fp contract(off)
+        const float m = dummy ? 0.f : 1.f;
+        const float t2p = __builtin_fmaf(-og, og, og) * th;
+        const float vp = og * __builtin_fmaf(-th, th, 1.0f);
+        const float w = __builtin_fmaf(po, t2p, vp);
+        const float d2p = ig * __builtin_fmaf(-ni, ni, 1.0f);
+        const float d3p = __builtin_fmaf(-fg, fg, fg) * cp;
+        const float d4p = __builtin_fmaf(-ig, ig, ig) * ni;
+        float car = c.fg * c.ec;
+        car = __builtin_fmaf(pi, c.dig, car);
+        car = __builtin_fmaf(pf, c.dfg, car);
+        dog = (t2p * m) * e;
+        ec = __builtin_fmaf(e, w * m, car * m);
+        dni = (d2p * m) * ec; dfg = (d3p * m) * ec; dig = (d4p * m) * ec;
+        c.fg = fg * m;
+    }
+    dni = clip1(dni); dig = clip1(dig); dfg = clip1(dfg); dog = clip1(dog);
+    c.ec = ec; c.dig = dig; c.dfg = dfg;
 }
 
 // The bias / peephole sums a backward workgroup has formed over its time steps and sequences for unit `unit` of direction d

@@ -31,13 +31,6 @@
 
 namespace cn {
 
-#define KEEP_TUPLE(tuple, after) asm volatile("" :: "v"(tuple), "v"(after))
-
-template <typename T> __device__ __forceinline__ T &at32(const void *base, unsigned elem)
-{
-    return *(T *)((char *)base + elem * (unsigned)sizeof(T));
-}
-
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
@@ -159,7 +152,6 @@ __global__ __launch_bounds__(HP * 2) void lstm_fwd_s2_kernel(LstmRec p)
                 }
             }
 
-        // ComputeBlockOutputFn, LstmLayer.cu:87-136 (bias is already inside the pre-activation)
         float s_[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -167,16 +159,10 @@ __global__ __launch_bounds__(HP * 2) void lstm_fwd_s2_kernel(LstmRec p)
             else s_[g] = accp[g][0] + accp[g][1];
             KEEP_TUPLE(accp[g], s_[g]);
         }
-        const float cp = cst;
-        const float ni = tanh_ref<false>(s_[0]);
-        const float ig = logistic<false>(s_[1] + cp * pi);
-        const float fg = logistic<false>(s_[2] + cp * pf);
-        const float cs = __builtin_fmaf(ni, ig, cp * fg);     // (written out: the hand-written loop below rounds the same way)
-        const float og = logistic<false>(s_[3] + cs * po);
-        const float th = tanh_ref<false>(cs);
-        const float y = th * og;
-        const float yo = dummy ? 0.f : y;
-        const float co = dummy ? 0.f : cs;            // :78-85 (zeroed in both directions here)
+        // ComputeBlockOutputFn (cn_lstm_device.h; bias is already inside the pre-activation), explicit form: the hand-written
+        // loop below rounds the same way
+        const CellOut o = lstm_cell_fwd<false, true>(s_, cst, pi, pf, po, dummy);
+        const float co = o.co, th = o.th, yo = o.yo;
         cst = co;
         if constexpr (X3) {
             __bf16 yh, yl;
@@ -184,7 +170,7 @@ __global__ __launch_bounds__(HP * 2) void lstm_fwd_s2_kernel(LstmRec p)
             *(__bf16 *)(ynxt + oT) = yh;
             *(__bf16 *)(ynxt + oT + 2 * pitch) = yl;
         } else *(__bf16 *)(ynxt + oT) = (__bf16)yo;
-        const f32x4 av = {ni, ig, fg, og};           // (dummy slots: never read back)
+        const f32x4 av = {o.ni, o.ig, o.fg, o.og};   // (dummy slots: never read back)
         *(f32x4 *)&at32<float>(actsT, oA) = av;
         at32<float>(cellT, oC) = co;
         at32<float>(thT, oC) = th;
@@ -811,19 +797,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_s2w_kernel(LstmRec p)
             float s_[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) { s_[g] = acc[g][0] + acc[g][1]; KEEP_TUPLE(acc[g], s_[g]); }
-            const float cp = cst[s];
-            const float ni = tanh_ref<false>(s_[0]);
-            const float ig = logistic<false>(s_[1] + cp * pi[s]);
-            const float fg = logistic<false>(s_[2] + cp * pf[s]);
-            const float cs = __builtin_fmaf(ni, ig, cp * fg);
-            const float og = logistic<false>(s_[3] + cs * po[s]);
-            const float th = tanh_ref<false>(cs);
-            const float y = th * og;
-            const float yo = dummy ? 0.f : y;
-            const float co = dummy ? 0.f : cs;
+            const CellOut o = lstm_cell_fwd<false, true>(s_, cst[s], pi[s], pf[s], po[s], dummy);      // explicit form, as the generated loop
+            const float co = o.co, th = o.th, yo = o.yo;
             cst[s] = co;
             *(__bf16 *)(ynxt + oT[s]) = (__bf16)yo;
-            const f32x4 av = {ni, ig, fg, og};
+            const f32x4 av = {o.ni, o.ig, o.fg, o.og};
             *(f32x4 *)&at32<float>(actsT, oA[s]) = av;
             at32<float>(cellT, oC[s]) = co;
             at32<float>(thT, oC[s]) = th;
@@ -1064,8 +1042,8 @@ __global__ __launch_bounds__(HP * 2) void lstm_bwd_s2_kernel(LstmRec p)
     const int uh = X3 ? unit : unit % (HP / 2), half = X3 ? 0 : unit / (HP / 2);
     const int oT = (4 * sq + 2 * half) * pitch + ((uh >> 4) * 32 + sp_pos(4 * (uh & 15))) * 2;      // (split-bf16: the hi rows; lo two rows on)
 
-    float fgn = 0.f, ecn = 0.f, dign = 0.f, dfgn = 0.f, ccur;
-    float sb[4] = {0.f, 0.f, 0.f, 0.f}, spi = 0.f, spf = 0.f, spo = 0.f;
+    CellCarry car = {0.f, 0.f, 0.f, 0.f};
+    float ccur, sb[4] = {0.f, 0.f, 0.f, 0.f}, spi = 0.f, spf = 0.f, spo = 0.f;
 
     const int tfirst = d ? 0 : T - 1;
     BwdStage preA, preB;
@@ -1131,37 +1109,10 @@ __global__ __launch_bounds__(HP * 2) void lstm_bwd_s2_kernel(LstmRec p)
             KEEP_TUPLE(accA, e); KEEP_TUPLE(accB, e);
         }
 
-        // ComputeBlockErrorsFn, LstmLayer.cu:236-285, as an explicit operation sequence (no contraction left to the compiler:
-        // the hand-written loop below issues exactly these operations and is held bit-equal).  Everything that does not
-        // depend on e is formed first -- in the hand-written loop one step early, in the shadow of the LDS hand-off --, and
-        // the dummy-slot rule (:224-234: all deltas and the cell state error are 0) enters as a factor m = 0 / 1, so that
-        // behind the product only
-        //   dog = [m og (1 - og) th] e,   ec = e [m (og (1 - th^2) + po og (1 - og) th)] + m (fg' ec' + pi dig' + pf dfg')
-        //   dni = [m ig (1 - ni^2)] ec,   dfg = [m fg (1 - fg) cp] ec,   dig = [m ig (1 - ig) ni] ec      (' = carried from t+1)
-        // remain: one multiply or fma each, then the clips.  (ec uses the unclipped dog, :262-263, as the reference does.)
-        const bool dummy = dmy != 0;
-        const float ni = a_[0], ig = a_[1], fg = a_[2], og = a_[3];
-        const float cs = ccur, th = th_;
-        float dog, ec, dni, dfg, dig;
-        {
-#pragma clang fp contract(off)
-            const float m = dummy ? 0.f : 1.f;
-            const float t2p = __builtin_fmaf(-og, og, og) * th;
-            const float vp = og * __builtin_fmaf(-th, th, 1.0f);
-            const float w = __builtin_fmaf(po, t2p, vp);
-            const float d2p = ig * __builtin_fmaf(-ni, ni, 1.0f);
-            const float d3p = __builtin_fmaf(-fg, fg, fg) * cp;              // cp = 0 at lastCall
-            const float d4p = __builtin_fmaf(-ig, ig, ig) * ni;
-            float car = fgn * ecn;                                          // zero carry at firstCall
-            car = __builtin_fmaf(pi, dign, car);
-            car = __builtin_fmaf(pf, dfgn, car);
-            dog = (t2p * m) * e;
-            ec = __builtin_fmaf(e, w * m, car * m);
-            dni = (d2p * m) * ec; dfg = (d3p * m) * ec; dig = (d4p * m) * ec;
-            fgn = fg * m;
-        }
-        dni = clip1(dni); dig = clip1(dig); dfg = clip1(dfg); dog = clip1(dog);
-        ecn = ec; dign = dig; dfgn = dfg;
+        // ComputeBlockErrorsFn as the explicit operation sequence of the hand-written loop below (cn_lstm_device.h)
+        const float cs = ccur;
+        float dni, dig, dfg, dog;
+        lstm_cell_bwd_explicit(e, a_, cp, th_, pi, pf, po, car, dmy != 0, dni, dig, dfg, dog);
         ccur = cp;
         // gradient sums (ComputeWeightUpdateFn bias / peephole cases, :392-408, :440-475)
         sb[0] += dni; sb[1] += dig; sb[2] += dfg; sb[3] += dog;

@@ -1,5 +1,5 @@
 """Segment timing inside the delta-exchange backward cluster kernel (s_memtime deltas summed per step segment by the waves of
-workgroup 0 = member 0 of cluster 0).  Needs `make -C lstm-rnn_amd/csrc variantc NAME=clstamp DEFS=-DCN_CL_STAMP`; on the GPU box:
+workgroup 0 = member 0 of cluster 0).  Needs `make -C lstm-rnn_amd/csrc variant FILE=cn_lstm_cluster NAME=clstamp DEFS=-DCN_CL_STAMP`; on the GPU box:
     CURRENNT_HIP_LIB=lstm-rnn_amd/libcurrennt_hip_clstamp.so python tools/stamps_cl.py [size] [PS] [T]
 Segments: 0 stage copies (step top -> first product issued), 1 own part of the product done, 2 partners' deltas polled,
 3 their LDS write + barrier, 4 second part of the product done (incl. the prefetch issue), 5 block errors + publish + stores

@@ -1,5 +1,5 @@
 """Segment timing inside the hand-written backward loop of cn_lstm_s2.hip (s_memtime deltas summed per step segment by every
-wave of workgroup 0).  Needs `make -C lstm-rnn_amd/csrc variants2 NAME=s2stamp DEFS=-DCN_S2_STAMP`; run on the GPU box:
+wave of workgroup 0).  Needs `make -C lstm-rnn_amd/csrc variant FILE=cn_lstm_s2 NAME=s2stamp DEFS=-DCN_S2_STAMP`; run on the GPU box:
     CURRENNT_HIP_LIB=lstm-rnn_amd/libcurrennt_hip_s2stamp.so python tools/stamps_s2.py [H] [PS] [T]
 Segments (cycles per step, each ending with a stamp that waits for lgkmcnt(0), which perturbs the schedule):
 0 barrier -> stage landed (vmcnt)   1 LDS reads issued + landed   2 16 MFMAs (+ fillers) issued   3 prefetch issued, MFMA

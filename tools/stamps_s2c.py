@@ -1,5 +1,5 @@
 """Segment timing inside the hand-written two-CU backward loop (cn_lstm_cluster.hip: lstm_bwd_s2c_asm_kernel; s_memtime deltas summed
-per step segment by every wave of workgroup 0).  Needs `make -C lstm-rnn_amd/csrc variantc NAME=s2cstamp DEFS=-DCN_S2C_STAMP`; on
+per step segment by every wave of workgroup 0).  Needs `make -C lstm-rnn_amd/csrc variant FILE=cn_lstm_cluster NAME=s2cstamp DEFS=-DCN_S2C_STAMP`; on
 the GPU box:   CURRENNT_HIP_LIB=lstm-rnn_amd/libcurrennt_hip_s2cstamp.so python tools/stamps_s2c.py [H] [PS] [T] [layers]
 Segments (cycles per step; each ends with a stamp that waits for lgkmcnt(0), ~45 cycles by itself, and perturbs the schedule):
 0 barrier + loop control   1 poll / prefetch issue + own K half (16 reads, 16 MFMAs)   2 waiting for the poll

@@ -1,5 +1,5 @@
 """Loop time of every workgroup of the LAST backward launch of the hand-written s2 loop (diag build:
-make -C lstm-rnn_amd/csrc variants2 NAME=wgtime DEFS=-DCN_S2_WGTIME): which workgroups are the slow ones, and where they sit.
+make -C lstm-rnn_amd/csrc variant FILE=cn_lstm_s2 NAME=wgtime DEFS=-DCN_S2_WGTIME): which workgroups are the slow ones, and where they sit.
     CURRENNT_HIP_LIB=lstm-rnn_amd/libcurrennt_hip_wgtime.so python tools/wgtime_s2.py [layers]"""
 import ctypes as C, os, sys
 import numpy as np
