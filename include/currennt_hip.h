@@ -94,7 +94,11 @@ typedef enum cn_buffer {
     CN_BUF_LSTM_IG_DELTAS,
     CN_BUF_LSTM_FG_DELTAS,
     CN_BUF_LSTM_OG_DELTAS,
-    CN_BUF_LSTM_TMP_OUTPUTS    /* per-direction block outputs y */
+    CN_BUF_LSTM_TMP_OUTPUTS,   /* per-direction block outputs y */
+    /* Adam's second moments v, flat like the weights (cn_adam_update below; no counterpart in the reference, whose only optimizer
+     * state is m_weightDeltas, SteepestDescentOptimizer.cu:117-123).  Valid in cn_layer_read / cn_layer_upload /
+     * cn_layer_device_ptr; a read before any Adam call returns zeros.  Adam's FIRST moments are CN_BUF_WEIGHT_DELTAS. */
+    CN_BUF_ADAM_SECOND_MOMENTS
 } cn_buffer;
 
 /* one parallel-sequence mini batch = data_sets::DataSetFraction (DataSetFraction.hpp:50-60) */
@@ -330,6 +334,42 @@ int  cn_ctx_timing_reset(cn_ctx *ctx);
  * that instantiated it, e.g. "lstm_bwd_s2_kernel<0,128>", "lstm_fwd_kernel<2,128,1,1>" or
  * "lstm_bwd_cluster_kernel<0,256,128,1>"; "" for other layers and before the first pass */
 const char *cn_layer_recurrent_kernel(cn_layer *layer, int backward);
+
+/* ---- Adam (no counterpart in the reference, whose option table names steepest_descent and rprop only,
+ *      Configuration.cpp:152,265) ---------------------------------------------------------------------------------
+ * A second update rule beside UpdateWeightFn, with the same three entry points and the same protocol as the cn_sgd_* trio.
+ *
+ * Arithmetic.  All state is fp32.  g is the layer's weightUpdates entry, the quantity the steepest-descent step reads.  The
+ * first moments m live in the weightDeltas part of the parameter arena (CN_BUF_WEIGHT_DELTAS; cn_ctx_param_arena is unchanged),
+ * the second moments v in one more vector of the same length (CN_BUF_ADAM_SECOND_MOMENTS), zero at the first Adam call unless
+ * uploaded.  The library keeps no clock: `step` (>= 1) is the caller's count of updates, this one included.  From the float
+ * arguments the host forms, in double, rounded once to float,
+ *      omb1 = 1 - beta1      omb2 = 1 - beta2
+ *      alpha_t = lr * sqrt(1 - beta2^step) / (1 - beta1^step)        (product first, then the quotient)
+ *      eps_t   = eps * sqrt(1 - beta2^step)
+ * and the device computes per weight, every operation an fp32 operation rounded to nearest on its own (no contraction, correctly
+ * rounded square root and division, denormals kept):
+ *      m = beta1*m + omb1*g
+ *      v = beta2*v + omb2*(g*g)
+ *      w = w - (alpha_t*m) / (sqrt(v) + eps_t)
+ * which is algebraically Adam with bias correction (Kingma & Ba 2015; torch.optim.Adam without amsgrad and weight decay).  Every
+ * path -- the flat kernel, and the forms fused into the operand-copy launch -- computes exactly this, bit for bit.
+ *
+ * Binding.  weightDeltas is the momentum term under steepest descent and the first moment under Adam, so a context belongs to the
+ * family of its first update or arm call; a later call of the other family fails with CN_ERR_STATE.  step < 1, a beta outside
+ * [0, 1) and eps <= 0 fail with CN_ERR_BAD_ARG. */
+/* beside cn_sgd_update (UpdateWeightFn, SteepestDescentOptimizer.cu:39-59; the reference has no counterpart): the Adam step of
+ * one layer with `learning_rate` as given, then the packed copies are refreshed before the next forward pass */
+int  cn_adam_update(cn_layer *layer, float learning_rate, float beta1, float beta2, float eps, int64_t step);
+/* beside cn_sgd_update_all (SteepestDescentOptimizer::_updateWeights, SteepestDescentOptimizer.cu:67-94; the reference has no
+ * counterpart): every trainable layer in one launch, operand copies included; a layer with a learning rate of its own
+ * (cn_layer_set_learning_rate) takes it as its lr.  Orders itself behind cn_allreduce_grads like cn_sgd_update_all. */
+int  cn_adam_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step);
+/* beside cn_ctx_arm_update (the per-fraction protocol of Optimizer.cu:86-94 around SteepestDescentOptimizer.cu:67-94; the
+ * reference has no counterpart): arms the Adam step of the COMING backward pass, applied per layer as soon as its gradient is
+ * complete.  Completed by cn_adam_update_all(ctx, same values) or by cn_adam_update per layer (same values; a layer with a
+ * learning rate of its own passes that), else CN_ERR_STATE; cn_ctx_accumulate_updates is refused while it is armed.   [async] */
+int  cn_ctx_arm_adam(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step);
 
 #ifdef __cplusplus
 }

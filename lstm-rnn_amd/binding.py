@@ -24,6 +24,7 @@ BUF = {
     "outputs": 0, "outputErrors": 1, "weights": 2, "weightUpdates": 3, "weightDeltas": 4,
     "cellStates": 5, "niActs": 6, "igActs": 7, "fgActs": 8, "ogActs": 9,
     "niDeltas": 10, "igDeltas": 11, "fgDeltas": 12, "ogDeltas": 13, "tmpOutputs": 14,
+    "adamSecondMoments": 15,
 }
 
 # every symbol include/currennt_hip.h declares (tests check the .so exports all of them)
@@ -38,6 +39,8 @@ EXPORTS = [
     "cn_comm_unique_id", "cn_comm_init", "cn_comm_destroy", "cn_comm_info", "cn_comm_backend", "cn_allreduce_grads", "cn_loss_read_global",
     # include/currennt_hip_debug.h
     "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits",
+    # include/currennt_hip.h, section Adam
+    "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
 
 
@@ -127,6 +130,9 @@ def load_library():
     L.cn_sgd_update.argtypes = [vp, cf, cf]
     L.cn_sgd_update_all.argtypes = [vp, cf, cf]
     L.cn_ctx_arm_update.argtypes = [vp, cf, cf]
+    L.cn_adam_update.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_adam_update_all.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_ctx_arm_adam.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
     L.cn_ctx_accumulate_updates.argtypes = [vp, ci]
     L.cn_ctx_take_accumulated.argtypes = [vp]
     L.cn_ctx_timing_enable.argtypes = [vp, ci]

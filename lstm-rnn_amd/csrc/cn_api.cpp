@@ -12,6 +12,8 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>       // types and prototypes only: librccl is opened with dlopen (struct Rccl below), never linked
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -143,6 +145,17 @@ struct cn_ctx {
     // gradient is complete (on the stream that computed it), instead of for all layers behind the last backward kernel
     bool armed = false;
     float arm_lr = 0.f, arm_mom = 0.f;
+    // cn_ctx_arm_adam: the same protocol with the Adam step (arm_adam: which of the two is armed)
+    bool arm_adam = false;
+    struct AdamArgs {
+        float lr = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0;
+        bool same(const AdamArgs &o, float lr_) const { return lr_ == o.lr && b1 == o.b1 && b2 == o.b2 && eps == o.eps && step == o.step; }
+    } arm_a;
+    // Optimizer family of the context's first update / arm call (0: none yet).  weightDeltas is the momentum term under one and the
+    // first moment under the other, so a context stays with its family.
+    enum { FAMILY_NONE = 0, FAMILY_SGD, FAMILY_ADAM };
+    int family = FAMILY_NONE;
+    float *adam_v = nullptr;              // Adam's second moments, [total] like a part of the arena, zeroed; allocated at the first Adam call
 
     // parameter arena [weights | weightUpdates | weightDeltas]
     bool finalized = false;
@@ -598,6 +611,48 @@ void finalize(cn_ctx *c)
     c->finalized = true;
 }
 
+// ---- optimizer rule of an update launch ---------------------------------------------------------
+// momentum SGD (lr, mom) or Adam (a; a.lr is the caller's learning rate)
+struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f; cn_ctx::AdamArgs a; };
+UpdateRule armed_rule(const cn_ctx *c)
+{
+    UpdateRule r; r.adam = c->arm_adam; r.lr = c->arm_adam ? c->arm_a.lr : c->arm_lr; r.mom = c->arm_mom; r.a = c->arm_a;
+    return r;
+}
+// The scalars of include/currennt_hip.h (cn_adam_update): formed in double from the float arguments, rounded once
+AdamScalars adam_scalars(const cn_ctx::AdamArgs &a, float lr)
+{
+    const double b1 = a.b1, b2 = a.b2, t = (double)a.step;
+    const double c2 = std::sqrt(1.0 - std::pow(b2, t)), c1 = 1.0 - std::pow(b1, t);
+    AdamScalars s;
+    s.b1 = a.b1; s.b2 = a.b2; s.omb1 = (float)(1.0 - b1); s.omb2 = (float)(1.0 - b2);
+    s.alpha_t = (float)((double)lr * c2 / c1); s.eps_t = (float)((double)a.eps * c2);
+    return s;
+}
+void ensure_adam_v(cn_ctx *c)
+{
+    finalize(c);
+    if (c->adam_v || !c->total) return;
+    HIP_CHECK(hipMalloc((void **)&c->adam_v, c->total * sizeof(float)));
+    HIP_CHECK(hipMemsetAsync(c->adam_v, 0, c->total * sizeof(float), c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));          // (once per context: the side and communication streams use it too)
+}
+void bind_family(cn_ctx *c, int family, const char *fn)
+{
+    if (c->family != cn_ctx::FAMILY_NONE && c->family != family)
+        throw cn_error(CN_ERR_STATE, std::string(fn) + ": this context is bound to " +
+                       (c->family == cn_ctx::FAMILY_SGD ? "steepest descent (cn_sgd_update*, cn_ctx_arm_update)" : "Adam (cn_adam_update*, cn_ctx_arm_adam)") +
+                       " by its first update, and " + (family == cn_ctx::FAMILY_SGD ? "steepest descent" : "Adam") +
+                       " would read its weightDeltas as something they are not (momentum term / first moment)");
+    c->family = family;
+}
+void check_adam_args(const char *fn, float beta1, float beta2, float eps, int64_t step)
+{
+    if (step < 1) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": step must be >= 1 (the caller's update count)");
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": beta1 and beta2 must lie in [0, 1)");
+    if (!(eps > 0.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": eps must be > 0");
+}
+
 void repack(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
@@ -705,7 +760,8 @@ void check_rec_lds(const cn_layer *l, bool bwd)
 // One layer's weight update + operand copies as one launch of the grouped pack kernel on `st`.
 // mode 1: gradient from the flat weightUpdates; mode 2: from the packed accumulators (unpack fused in, cn_elementwise.hip)
 // folds (mode 2, deterministic mode; nullable): f_in, f_rec[0], f_rec[1], f_bias -- the partial sums the launch adds itself
-void launch_layer_update(hipStream_t st, cn_layer *l, int mode, float lr, float mom, hipEvent_t done, const PackFold *folds = nullptr)
+// r: the optimizer's rule (the armed one, or the completing call's): its kind selects the instantiation (PackItem::optimizer)
+void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule &r, hipEvent_t done, const PackFold *folds = nullptr)
 {
     cn_ctx *c = l->ctx;
     PackGroup grp{};
@@ -715,10 +771,16 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, float lr, float 
     it.bias = l->bias; it.w = l->w; it.Win = l->Win; it.WinT = l->WinT; it.Wrec = l->Wrec; it.WrecT = l->WrecT;
     it.bias_p = l->bias_p; it.peep_p = l->peep_p;
     it.update = mode; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd; it.wu_rw = l->wu;
-    it.lr = l->own_lr >= 0.f ? l->own_lr : lr; it.mom = mom;
+    it.lr = l->own_lr >= 0.f ? l->own_lr : r.lr; it.mom = r.mom;
     it.g_in = l->dWin; it.g_rec = l->dWrec; it.g_bias = l->dbias; it.g_peep = l->dpeep;
     if (folds) { it.update = 3; it.f_in = folds[0]; it.f_rec[0] = folds[1]; it.f_rec[1] = folds[2]; it.f_bias = folds[3]; }
-    launch_pack_group(st, c->f32, grp, done);
+    PackAdam ad{};
+    if (r.adam) {
+        const AdamScalars a = adam_scalars(r.a, it.lr);
+        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
+        ad.v[0] = c->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
+    }
+    launch_pack_group(st, c->f32, grp, done, r.adam ? &ad : nullptr);
     l->dirty = false; l->pack_pending = false; l->updated = true;
 }
 // armed update without a communicator: unpack + update + operand copies ride on ONE launch behind the gradient GEMMs
@@ -835,7 +897,7 @@ void lstm_backward(cn_layer *l)
                     {l->det_ws ? l->det_ws + (size_t)DET_MAX_SPLITS * (size_t)R * l->Pp : nullptr, 4L * Hp * Hp, used_rec[0], 0},
                     {l->det_ws ? l->det_ws + (size_t)DET_MAX_SPLITS * ((size_t)R * l->Pp + (size_t)4 * Hp * Hp) : nullptr, 4L * Hp * Hp, used_rec[1], 0},
                     {l->gpart, (long)slot, det_grid, 1}};
-                launch_layer_update(st, l, 2, c->arm_lr, c->arm_mom, join, defer ? folds : nullptr);
+                launch_layer_update(st, l, 2, armed_rule(c), join, defer ? folds : nullptr);
             } else launch_lstm_unpack_grads(st, lstm_geom(l), l->dWin, l->dWrec, l->dbias, l->dpeep, l->wu, join);
         }
         return join != nullptr;
@@ -939,7 +1001,7 @@ void ff_backward(cn_layer *l)
                 // (the column sums' partial rows: colfold describes them; its target, the packed bias gradient, stays zero)
                 const PackFold folds[4] = {{l->det_ws, (long)l->Lp * l->Pp, used_in, 0}, {nullptr, 0, 0, 0}, {nullptr, 0, 0, 0},
                                            {colfold.part, colfold.stride, colfold.nparts, 0}};
-                launch_layer_update(st, l, 2, c->arm_lr, c->arm_mom, join, defer ? folds : nullptr);
+                launch_layer_update(st, l, 2, armed_rule(c), join, defer ? folds : nullptr);
             } else launch_ff_unpack_grads(st, ff_geom(l), l->bias, l->dWin, l->dbias, l->wu, join);
         }
         return join != nullptr;
@@ -1063,7 +1125,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -1288,7 +1350,7 @@ int cn_allreduce_grads(cn_ctx *ctx, cn_layer *const *layers, int n)
                 else if (ctx->ipc) ipc_reduce(ctx, l->wu, (size_t)l->nw);
                 else RCCL_CHECK(rccl().AllReduce(l->wu, l->wu, (size_t)l->nw, ncclFloat32, ncclSum, ctx->comm, ctx->comm_stream));
                 // armed update: the layer's step follows its reduction on the communication stream
-                if (ctx->armed && !l->updated) launch_layer_update(ctx->comm_stream, l, 1, ctx->arm_lr, ctx->arm_mom, nullptr);
+                if (ctx->armed && !l->updated) launch_layer_update(ctx->comm_stream, l, 1, armed_rule(ctx), nullptr);
             }
         }
         HIP_CHECK(hipEventRecord(ctx->ev_comm, ctx->comm_stream));
@@ -1748,7 +1810,9 @@ int cn_layer_backward(cn_layer *layer)
         require_loaded(c);
         finalize(c);
         if (layer->trainable && layer->updated)
-            throw cn_error(CN_ERR_STATE, "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_sgd_update_all / cn_sgd_update first)");
+            throw cn_error(CN_ERR_STATE, c->arm_adam
+                ? "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_adam_update_all / cn_adam_update first)"
+                : "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_sgd_update_all / cn_sgd_update first)");
         if (layer->lstm) lstm_backward(layer);
         else if (layer->trainable) ff_backward(layer);
         else if (layer->post) {
@@ -1903,11 +1967,12 @@ int cn_layer_upload(cn_layer *layer, cn_buffer which, const float *host, size_t 
         cn_ctx *c = layer->ctx;
         enter(c);
         if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload: layer has no weights");
-        if (which != CN_BUF_WEIGHT_UPDATES && which != CN_BUF_WEIGHT_DELTAS) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload: not a parameter vector");
+        if (which != CN_BUF_WEIGHT_UPDATES && which != CN_BUF_WEIGHT_DELTAS && which != CN_BUF_ADAM_SECOND_MOMENTS) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload: not a parameter vector");
         if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_layer_upload: count != weight count");
         finalize(c);
         join_side(c);
-        HIP_CHECK(hipMemcpyAsync(which == CN_BUF_WEIGHT_UPDATES ? layer->wu : layer->wd, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (which == CN_BUF_ADAM_SECOND_MOMENTS) ensure_adam_v(c);
+        HIP_CHECK(hipMemcpyAsync(which == CN_BUF_ADAM_SECOND_MOMENTS ? c->adam_v + layer->woff : which == CN_BUF_WEIGHT_UPDATES ? layer->wu : layer->wd, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     });
 }
@@ -1944,9 +2009,15 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
         const size_t e = c->esz();
         const bool opbf = !c->f32;
         // flat parameter vectors
-        if (which == CN_BUF_WEIGHTS || which == CN_BUF_WEIGHT_UPDATES || which == CN_BUF_WEIGHT_DELTAS) {
+        if (which == CN_BUF_WEIGHTS || which == CN_BUF_WEIGHT_UPDATES || which == CN_BUF_WEIGHT_DELTAS || which == CN_BUF_ADAM_SECOND_MOMENTS) {
             if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no weights");
             if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_layer_read: count != weight count");
+            if (which == CN_BUF_ADAM_SECOND_MOMENTS) {
+                if (!c->adam_v) { std::fill(host, host + count, 0.f); return; }          // before any Adam call: what it will start from
+                HIP_CHECK(hipMemcpyAsync(host, c->adam_v + layer->woff, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+                HIP_CHECK(hipStreamSynchronize(c->stream));
+                return;
+            }
             const float *src = which == CN_BUF_WEIGHTS ? layer->w : (which == CN_BUF_WEIGHT_UPDATES ? layer->wu : layer->wd);
             HIP_CHECK(hipMemcpyAsync(host, src, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
             HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -2012,6 +2083,9 @@ void *cn_layer_device_ptr(cn_layer *layer, cn_buffer which)
     case CN_BUF_WEIGHTS: return layer->w;
     case CN_BUF_WEIGHT_UPDATES: return layer->wu;
     case CN_BUF_WEIGHT_DELTAS: return layer->wd;
+    case CN_BUF_ADAM_SECOND_MOMENTS:
+        if (guarded([&] { ensure_adam_v(layer->ctx); }) != CN_OK) return nullptr;
+        return layer->ctx->adam_v + layer->woff;
     default: return nullptr;
     }
 }
@@ -2042,7 +2116,24 @@ int cn_ctx_arm_update(cn_ctx *ctx, float learning_rate, float momentum)
     return guarded([&] {
         for (cn_layer *l : ctx->layers)
             if (l->updated) throw cn_error(CN_ERR_STATE, "cn_ctx_arm_update: the previous armed update has not been completed (cn_sgd_update_all)");
-        ctx->armed = true; ctx->arm_lr = learning_rate; ctx->arm_mom = momentum;
+        bind_family(ctx, cn_ctx::FAMILY_SGD, "cn_ctx_arm_update");
+        ctx->armed = true; ctx->arm_adam = false; ctx->arm_lr = learning_rate; ctx->arm_mom = momentum;
+    });
+}
+
+int cn_ctx_arm_adam(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!ctx) { g_last_error = "cn_ctx_arm_adam: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        check_adam_args("cn_ctx_arm_adam", beta1, beta2, eps, step);
+        for (cn_layer *l : ctx->layers)
+            if (l->updated) throw cn_error(CN_ERR_STATE, "cn_ctx_arm_adam: the previous armed update has not been completed (cn_adam_update_all)");
+        bind_family(ctx, cn_ctx::FAMILY_ADAM, "cn_ctx_arm_adam");
+        ensure_adam_v(ctx);
+        ctx->armed = true; ctx->arm_adam = true;
+        ctx->arm_a.lr = learning_rate; ctx->arm_a.b1 = beta1; ctx->arm_a.b2 = beta2; ctx->arm_a.eps = eps; ctx->arm_a.step = step;
+        ctx->arm_mom = 0.f;
     });
 }
 
@@ -2053,6 +2144,7 @@ int cn_sgd_update(cn_layer *layer, float learning_rate, float momentum)
         cn_ctx *c = layer->ctx;
         enter(c);
         if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_sgd_update: layer has no weights");
+        bind_family(c, cn_ctx::FAMILY_SGD, "cn_sgd_update");
         comm_check_fast(c);
         finalize(c);
         join_side(c);
@@ -2068,6 +2160,36 @@ int cn_sgd_update(cn_layer *layer, float learning_rate, float momentum)
         }
         Timed tm(c, KC_OTHER);
         launch_sgd(c->stream, layer->w, layer->wu, layer->wd, (size_t)layer->nw, learning_rate, momentum);
+        layer->dirty = true;
+    });
+}
+
+int cn_adam_update(cn_layer *layer, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!layer) { g_last_error = "cn_adam_update: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_adam_update: layer has no weights");
+        check_adam_args("cn_adam_update", beta1, beta2, eps, step);
+        bind_family(c, cn_ctx::FAMILY_ADAM, "cn_adam_update");
+        comm_check_fast(c);
+        ensure_adam_v(c);
+        join_side(c);
+        cn_ctx::AdamArgs a; a.lr = learning_rate; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.step = step;
+        if (layer->updated) {            // cn_ctx_arm_adam: this layer's step ran behind its gradient; nothing left but the wait above
+            const float want = layer->own_lr >= 0.f ? layer->own_lr : c->arm_a.lr;
+            a.lr = c->arm_a.lr;
+            if (learning_rate != want || !a.same(c->arm_a, c->arm_a.lr))
+                throw cn_error(CN_ERR_STATE, "cn_adam_update: learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied");
+            layer->updated = false;
+            bool any = false;
+            for (cn_layer *o : c->layers) any = any || o->updated;
+            if (!any) c->armed = false;
+            return;
+        }
+        Timed tm(c, KC_OTHER);
+        launch_adam(c->stream, layer->w, layer->wu, layer->wd, c->adam_v + layer->woff, (size_t)layer->nw, adam_scalars(a, learning_rate));
         layer->dirty = true;
     });
 }
@@ -2109,19 +2231,25 @@ int cn_layer_set_learning_rate(cn_layer *layer, float learning_rate)
     return CN_OK;
 }
 
-int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
+namespace {
+// cn_sgd_update_all / cn_adam_update_all: one sequence for both rules (r.lr: the call's learning rate)
+void update_all(cn_ctx *ctx, const UpdateRule &r)
 {
-    if (!ctx) { g_last_error = "cn_sgd_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        enter(ctx);
-        comm_check_fast(ctx);
-        finalize(ctx);
-        join_side(ctx);
+    const float learning_rate = r.lr, momentum = r.mom;
+    // the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in
+    auto launch_flat = [&](size_t off, size_t n, float lr, hipEvent_t done) {
+        float *w = ctx->arena + off, *wu = w + ctx->total, *wd = w + 2 * ctx->total;
+        if (r.adam) launch_adam(ctx->stream, w, wu, wd, ctx->adam_v + off, n, adam_scalars(r.a, lr), done);
+        else        launch_sgd(ctx->stream, w, wu, wd, n, lr, momentum, done);
+    };
+    {
         // cn_ctx_arm_update: layers whose step ran behind their gradient are complete (the wait above orders this stream behind
         // them); what follows handles the rest (none, normally)
         bool any_updated = false;
         for (cn_layer *l : ctx->layers) any_updated = any_updated || l->updated;
-        if (any_updated && (learning_rate != ctx->arm_lr || momentum != ctx->arm_mom))
+        if (any_updated && r.adam && !r.a.same(ctx->arm_a, learning_rate))
+            throw cn_error(CN_ERR_STATE, "cn_adam_update_all: learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied");
+        if (any_updated && !r.adam && (learning_rate != ctx->arm_lr || momentum != ctx->arm_mom))
             throw cn_error(CN_ERR_STATE, "cn_sgd_update_all: learning rate / momentum differ from what cn_ctx_arm_update armed and applied");
         ctx->armed = false;
         struct ClearUpdated { cn_ctx *c; ~ClearUpdated() { for (cn_layer *l : c->layers) l->updated = false; } } clear_updated{ctx};
@@ -2131,7 +2259,7 @@ int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
         if (ntrain == 0) return;
         if (any_updated) {               // some layers were not reached by the armed pass (no backward call for them): one launch each
             for (cn_layer *l : ctx->layers)
-                if (l->trainable && !l->updated) launch_layer_update(ctx->stream, l, 1, learning_rate, momentum, nullptr);
+                if (l->trainable && !l->updated) launch_layer_update(ctx->stream, l, 1, r, nullptr);
             return;
         }
         // The operand copies of the new weights are rebuilt right away, all layers in ONE launch on this stream
@@ -2148,20 +2276,19 @@ int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
         const bool fused = grouped && !fuse_off;
         if (fused) {
         } else if (!own_rates) {
-            launch_sgd(ctx->stream, ctx->arena, ctx->arena + ctx->total, ctx->arena + 2 * ctx->total, ctx->total, learning_rate, momentum,
-                       attach ? ctx->ev_sgd : nullptr);
+            launch_flat(0, ctx->total, learning_rate, attach ? ctx->ev_sgd : nullptr);
         } else {
             // a layer with a "learningRate" of its own (SteepestDescentOptimizer.cu:78-80): one launch per layer
             cn_layer *last = nullptr;
             for (cn_layer *l : ctx->layers) if (l->trainable) last = l;
             for (cn_layer *l : ctx->layers)
                 if (l->trainable)
-                    launch_sgd(ctx->stream, l->w, l->wu, l->wd, (size_t)l->nw, l->own_lr >= 0.f ? l->own_lr : learning_rate, momentum,
-                               (attach && l == last) ? ctx->ev_sgd : nullptr);
+                    launch_flat(l->woff, (size_t)l->nw, l->own_lr >= 0.f ? l->own_lr : learning_rate, (attach && l == last) ? ctx->ev_sgd : nullptr);
         }
         for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
         if (grouped) {
             PackGroup grp{};
+            PackAdam ad{};
             for (cn_layer *l : ctx->layers) {
                 if (!l->trainable) continue;
                 PackItem &it = grp.item[grp.n++];
@@ -2172,10 +2299,15 @@ int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
                 if (fused) {
                     it.update = 1; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd;
                     it.lr = l->own_lr >= 0.f ? l->own_lr : learning_rate; it.mom = momentum;
+                    if (r.adam) {
+                        const AdamScalars a = adam_scalars(r.a, it.lr);
+                        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
+                        ad.v[grp.n - 1] = ctx->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
+                    }
                 }
                 l->dirty = false; l->pack_pending = false;
             }
-            launch_pack_group(ctx->stream, ctx->f32, grp);
+            launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr);
         } else if (ctx->overlap) {
             // (more layers than one group launch takes: the first trainable layer's copy on this stream, its forward pass
             // is next; the others on the side stream, each layer's forward pass waits for them in repack())
@@ -2196,6 +2328,38 @@ int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
                 l->dirty = false; l->pack_pending = true;
             }
         }
+    }
+}
+}  // namespace
+
+int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
+{
+    if (!ctx) { g_last_error = "cn_sgd_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        bind_family(ctx, cn_ctx::FAMILY_SGD, "cn_sgd_update_all");
+        comm_check_fast(ctx);
+        finalize(ctx);
+        join_side(ctx);
+        UpdateRule r; r.lr = learning_rate; r.mom = momentum;
+        update_all(ctx, r);
+    });
+}
+
+int cn_adam_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!ctx) { g_last_error = "cn_adam_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        check_adam_args("cn_adam_update_all", beta1, beta2, eps, step);
+        bind_family(ctx, cn_ctx::FAMILY_ADAM, "cn_adam_update_all");
+        comm_check_fast(ctx);
+        ensure_adam_v(ctx);
+        join_side(ctx);
+        UpdateRule r; r.adam = true; r.lr = learning_rate;
+        r.a.lr = learning_rate; r.a.b1 = beta1; r.a.b2 = beta2; r.a.eps = eps; r.a.step = step;
+        r.mom = 0.f;
+        update_all(ctx, r);
     });
 }
 

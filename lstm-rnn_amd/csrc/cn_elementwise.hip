@@ -9,6 +9,7 @@
 //   layers/MulticlassClassificationLayer.cu:48-135               -> mcc_rows_kernel, mcc_backward_kernel
 //   layers/SsePostOutputLayer.cu:39-88 and the other post output layers -> post_rows_kernel, post_backward_kernel
 //   optimizers/SteepestDescentOptimizer.cu:39-59 UpdateWeightFn  -> sgd_kernel
+//   (no counterpart in the reference) the Adam step of include/currennt_hip.h -> adam_kernel, pack_group_adam_kernel
 #include "cn_internal.h"
 
 #include <float.h>
@@ -48,6 +49,30 @@ __device__ __forceinline__ int pad_col(int i, int prevH, int prevHp)
 // feed-forward layer is bias * column sum, FeedForwardLayer.cu:94-100): it is read, cleared for the next backward pass and
 // written to the flat weightUpdates on the way (what lstm_unpack_kernel / ff_unpack_kernel do in the unfused sequence).
 struct PackUpd { float *w_rw; const float *wu; float *wd; float lr, mom; float *wu_rw; };
+// The Adam forms (a type of their own: pack_fetch and the pack bodies are instantiated a second time for it and the SGD
+// instantiations keep their code): wd holds the first moments, lr alpha_t, mom beta1
+struct PackUpdAdam : PackUpd { float *v; float b2, omb1, omb2, eps_t; };
+// One weight's update from its gradient g.  Adam as stated in include/currennt_hip.h (cn_adam_update), every operation rounded
+// on its own like the SGD step's: m = b1*m + omb1*g; v = b2*v + omb2*(g*g); w = w - (alpha_t*m) / (sqrt(v) + eps_t)
+__device__ __forceinline__ float adam_step(float w, float g, float *m, float *v, float b1, float omb1, float b2, float omb2, float alpha_t, float eps_t)
+{
+    const float mn = __fadd_rn(__fmul_rn(b1, *m), __fmul_rn(omb1, g));
+    const float vn = __fadd_rn(__fmul_rn(b2, *v), __fmul_rn(omb2, __fmul_rn(g, g)));
+    *m = mn; *v = vn;
+    // (sqrtf, not __fsqrt_rn: hipcc's __fsqrt_rn is the NATIVE square root, v_sqrt_f32 alone, 1 ulp; sqrtf compiles to the correctly
+    // rounded sequence -- v_sqrt_f32 and a residual step -- as long as no fast-math flag is given, and csrc/Makefile gives none)
+    return __fsub_rn(w, __fdiv_rn(__fmul_rn(alpha_t, mn), __fadd_rn(sqrtf(vn), eps_t)));
+}
+__device__ __forceinline__ float apply_update(const PackUpd &u, long fi, float g)
+{
+    const float dl = __fsub_rn(__fmul_rn(u.mom, u.wd[fi]), __fmul_rn(u.lr, g));          // SteepestDescentOptimizer.cu:51
+    u.wd[fi] = dl;
+    return __fadd_rn(u.w_rw[fi], dl);                                                     // :55
+}
+__device__ __forceinline__ float apply_update(const PackUpdAdam &u, long fi, float g)
+{
+    return adam_step(u.w_rw[fi], g, u.wd + fi, u.v + fi, u.mom, u.omb1, u.b2, u.omb2, u.lr, u.eps_t);
+}
 // deterministic mode: the partial sums of this entry, added in order -- ((p0 + p1) + p2) + ..., exactly fold_kernel's sum
 // (sixteen loads in flight per batch: the bias / peephole sums have one partial per backward workgroup -- 52 on the headline --
 // and four at a time made the launch 11 us longer, a chain of thirteen L2 round trips per thread)
@@ -70,8 +95,8 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
     }
     return t;
 }
-template <int UPD>
-__device__ __forceinline__ float pack_fetch(const float *w, const PackUpd &u, long fi, float *gp = nullptr, float gscale = 1.0f,
+template <int UPD, class U>
+__device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
                                             const PackFold *fold = nullptr, long foff = 0)
 {
     if constexpr (UPD != 0) {
@@ -83,9 +108,7 @@ __device__ __forceinline__ float pack_fetch(const float *w, const PackUpd &u, lo
             u.wu_rw[fi] = g;
         } else if constexpr (UPD == 2) { g = *gp; *gp = 0.f; if (gscale != 1.0f) g = __fmul_rn(gscale, g); u.wu_rw[fi] = g; }
         else g = u.wu[fi];
-        const float dl = __fsub_rn(__fmul_rn(u.mom, u.wd[fi]), __fmul_rn(u.lr, g));          // SteepestDescentOptimizer.cu:51
-        u.wd[fi] = dl;
-        const float v = __fadd_rn(u.w_rw[fi], dl);                                            // :55
+        const float v = apply_update(u, fi, g);
         u.w_rw[fi] = v;
         return v;
     } else return w[fi];
@@ -93,10 +116,10 @@ __device__ __forceinline__ float pack_fetch(const float *w, const PackUpd &u, lo
 struct PackGrad { float *g_in, *g_rec, *g_bias, *g_peep; PackFold f_in, f_rec[2], f_bias; };
 
 // (first / count: the workgroups [first, first + count) of the launch work on this layer: pack_group_kernel)
-template <bool F32, int UPD = 0>
+template <bool F32, int UPD = 0, class U = PackUpd>
 __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, const float *w, void *Win, void *WinT,
                                                void *Wrec, void *WrecT, float *bias_p, float *peep_p, int first, int count,
-                                               const PackUpd &upd = PackUpd{}, const PackGrad &pg = PackGrad{})
+                                               const U &upd = U{}, const PackGrad &pg = PackGrad{})
 {
     const int P = g.P, Pp = g.Pp, L = g.L, H = g.H, Hp = g.Hp, dirs = g.dirs;
     const long R = (long)dirs * 4 * Hp;                 // packed gate rows
@@ -198,9 +221,9 @@ void launch_lstm_unpack_grads(hipStream_t s, const LstmGeom &g, float *dWin, flo
 // feed-forward weight packing (flat layout: [j][i] P x L column-major then L bias weights,
 // FeedForwardLayer.cu:148,160)
 // ---------------------------------------------------------------------------------------------
-template <bool F32, int UPD = 0>
+template <bool F32, int UPD = 0, class U = PackUpd>
 __device__ __forceinline__ void ff_pack_body(const FfGeom &g, float bias, const float *w, void *W, void *WT, float *bias_p, int first, int count,
-                                             const PackUpd &upd = PackUpd{}, const PackGrad &pg = PackGrad{})
+                                             const U &upd = U{}, const PackGrad &pg = PackGrad{})
 {
     const long nW = (long)g.Lp * g.Pp, total = nW + g.Lp;
     for (long idx = (blockIdx.x - first) * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)count * blockDim.x) {
@@ -253,7 +276,34 @@ __global__ void pack_group_kernel(PackGroup grp)
     if (it.lstm) lstm_pack_body<F32>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count);
     else         ff_pack_body<F32>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count);
 }
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done)
+// The Adam forms of the three update modes: the same bodies instantiated for PackUpdAdam.  A kernel of its own, so that
+// pack_group_kernel -- the tail of the SGD step -- does not carry their registers or their code.
+template <bool F32>
+__global__ void pack_group_adam_kernel(PackGroup grp, PackAdam ad)
+{
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) i = k;
+    const PackItem it = grp.item[i];
+    float *v = ad.v[0];
+#pragma unroll
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k == i) v = ad.v[k];           // (no dynamic index into the argument: it would go through scratch)
+    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
+    const PackUpdAdam upd{{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw}, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t};
+    if (it.update == 2) {
+        const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}};
+        if (it.lstm) lstm_pack_body<F32, 2>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
+        else         ff_pack_body<F32, 2>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
+    } else if (it.update == 3) {
+        const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias};
+        if (it.lstm) lstm_pack_body<F32, 3>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
+        else         ff_pack_body<F32, 3>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
+    } else {
+        if (it.lstm) lstm_pack_body<F32, 1>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
+        else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
+    }
+}
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam)
 {
     int blocks = 0;
     for (int i = 0; i < grp.n; ++i) {
@@ -264,6 +314,11 @@ void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done)
         grp.first[i] = blocks; blocks += b;
     }
     if (blocks == 0) return;
+    if (grp.item[0].optimizer == PACK_OPT_ADAM) {
+        if (f32) hipExtLaunchKernelGGL(pack_group_adam_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
+        else     hipExtLaunchKernelGGL(pack_group_adam_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
+        return;
+    }
     if (f32) hipExtLaunchKernelGGL(pack_group_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
     else     hipExtLaunchKernelGGL(pack_group_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
 }
@@ -1417,6 +1472,18 @@ void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, f
     if (n == 0) return;
     int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipExtLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom);
+}
+
+__global__ void adam_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        w[i] = adam_step(w[i], wu[i], m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
+}
+void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done)
+{
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    hipExtLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a);
 }
 
 }  // namespace cn

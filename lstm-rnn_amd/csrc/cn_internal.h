@@ -220,7 +220,10 @@ struct PackItem {
     void *Win, *WinT, *Wrec, *WrecT; float *bias_p, *peep_p;
     // update == 1: the momentum-SGD step of SteepestDescentOptimizer.cu:39-59 is applied on the way (every flat weight is read by
     // exactly one packed position, so the thread that packs it also updates it): wd = mom*wd - lr*wu; w += wd
-    int update; float *w_rw; const float *wu; float *wd; float lr, mom;
+    // optimizer (beside `update`, in what was padding: the layout of the SGD forms is unchanged): PACK_OPT_SGD, or PACK_OPT_ADAM --
+    // launch_pack_group then launches pack_group_adam_kernel, instantiations of their own, with the group's PackAdam; lr holds the
+    // layer's alpha_t and mom holds beta1, wd is the first moment
+    int update; int optimizer; float *w_rw; const float *wu; float *wd; float lr, mom;
     // update == 2 (cn_ctx_arm_update, no communicator): the gradient is taken straight from the PACKED accumulators the gradient
     // GEMMs / recurrent kernel summed into (every packed position is visited by exactly one thread, which also clears it and
     // writes the flat weightUpdates entry): unpack + update + operand copies in ONE launch behind the layer's gradient GEMMs
@@ -230,7 +233,12 @@ struct PackItem {
     PackFold f_in, f_rec[2], f_bias;
 };
 struct PackGroup { PackItem item[PACK_GROUP_MAX]; int first[PACK_GROUP_MAX]; int n; };
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr);
+enum { PACK_OPT_SGD = 0, PACK_OPT_ADAM = 1 };
+// What an Adam launch needs beyond PackItem (a kernel argument of its own: PackItem, and with it the SGD instantiations, stay as
+// they are): item i's second moments, and the scalars every layer shares (include/currennt_hip.h, cn_adam_update)
+struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
+// adam: required when the group's items say PACK_OPT_ADAM (all items of a group name the same optimizer)
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr);
 void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const float *w,
                     void *W, void *WT, float *bias_p);
 void launch_ff_unpack_grads(hipStream_t s, const FfGeom &g, float bias, float *dW, float *colsum, float *wu, hipEvent_t done = nullptr);
@@ -320,6 +328,9 @@ struct P2pArgs {
 };
 void launch_p2p_allreduce(hipStream_t s, const P2pArgs &a);
 void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, hipEvent_t done = nullptr);
+// the Adam step over a flat range (include/currennt_hip.h, cn_adam_update): m first moments, v second moments
+struct AdamScalars { float b1, omb1, b2, omb2, alpha_t, eps_t; };
+void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done = nullptr);
 void launch_accumulate(hipStream_t s, float *acc, const float *wu, size_t n, bool first);
 // gather a padded row-major fp32/op matrix into the reference layout [N][L]
 // (host row n = t*PS + s maps to device row t*PSp + s)

@@ -44,6 +44,8 @@ const char *Configuration::usage()
            "                      parallel_sequences is per GPU; gradients are summed with RCCL)\n"
            "  training: --train B --stochastic B (= --hybrid_online_batch) --shuffle_fractions B --shuffle_sequences B\n"
            "            --max_epochs N --max_epochs_no_best N --validate_every N --test_every N --learning_rate X\n"
+           "            --optimizer steepest_descent|adam (adam: --learning_rate is its step size, --momentum is ignored)\n"
+           "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
            "            --momentum X --save_network F --train_file F[,F] --val_file F --test_file F --truncate_seq N\n"
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
@@ -79,9 +81,12 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "max_epochs_no_best") m_maxEpochsNoBest = atoi(v.c_str());
     else if (key == "validate_every") m_validateEvery = atoi(v.c_str());
     else if (key == "test_every") m_testEvery = atoi(v.c_str());
-    else if (key == "optimizer") { if (v != "steepest_descent") throw std::runtime_error("Error while parsing the command line and/or options file: unknown optimizer '" + v + "'"); }
+    else if (key == "optimizer") { if (v == "adam" || v == "steepest_descent") m_optimizer = v; else throw std::runtime_error("Error while parsing the command line and/or options file: unknown optimizer '" + v + "'"); }
     else if (key == "learning_rate") m_learningRate = (real_t)atof(v.c_str());
     else if (key == "momentum") m_momentum = (real_t)atof(v.c_str());
+    else if (key == "adam_beta1") m_adamBeta1 = (real_t)atof(v.c_str());
+    else if (key == "adam_beta2") m_adamBeta2 = (real_t)atof(v.c_str());
+    else if (key == "adam_epsilon") m_adamEpsilon = (real_t)atof(v.c_str());
     else if (key == "save_network") m_trainedNetwork = v;
     else if (key == "train_file") m_trainingFiles = splitList(v);
     else if (key == "val_file") m_validationFiles = splitList(v);

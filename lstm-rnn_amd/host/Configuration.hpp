@@ -34,6 +34,11 @@ public:
     unsigned randomSeed() const { return m_randomSeed; }
     real_t learningRate() const { return m_learningRate; }
     real_t momentum() const { return m_momentum; }
+    // --optimizer: "steepest_descent" (the reference's default, Configuration.cpp:152) or "adam" (no counterpart there)
+    const std::string &optimizer() const { return m_optimizer; }
+    real_t adamBeta1() const { return m_adamBeta1; }
+    real_t adamBeta2() const { return m_adamBeta2; }
+    real_t adamEpsilon() const { return m_adamEpsilon; }
     real_t featurePeriod() const { return m_featurePeriod; }
     real_t trainingFraction() const { return m_trainingFraction; }
     real_t validationFraction() const { return m_validationFraction; }
@@ -91,6 +96,8 @@ private:
     unsigned m_randomSeed = 0;
     real_t m_learningRate = 1e-5f, m_momentum = 0.9f, m_featurePeriod = 10, m_trainingFraction = 1, m_validationFraction = 1,
            m_testFraction = 1, m_weightsUniformMin = -0.1f, m_weightsUniformMax = 0.1f, m_weightsNormalSigma = 0.1f, m_weightsNormalMean = 0;
+    real_t m_adamBeta1 = 0.9f, m_adamBeta2 = 0.999f, m_adamEpsilon = 1e-8f;
+    std::string m_optimizer = "steepest_descent";
     feedforwardformat_type_t m_feedForwardFormat = FORMAT_SINGLE_CSV;
     std::string m_networkFile = "network.jsn", m_trainedNetwork = "trained_network.jsn", m_feedForwardOutputFile = "ff_output.csv";
     std::vector<std::string> m_trainingFiles, m_validationFiles, m_testFiles, m_feedForwardInputFiles;

@@ -296,17 +296,31 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
         if (config.trainingMode()) {
             printf("Creating the optimizer... ");
             fflush(stdout);
-            optimizers::SteepestDescentOptimizer optimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
-                                                           config.maxEpochsNoBest(), config.validateEvery(), config.testEvery(),
-                                                           config.learningRate(), config.momentum(), config.hybridOnlineBatch());
+            const bool adam = config.optimizer() == "adam";
+            std::unique_ptr<optimizers::Optimizer> optimizerPtr;
+            if (adam) optimizerPtr.reset(new optimizers::AdamOptimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
+                                                                       config.maxEpochsNoBest(), config.validateEvery(), config.testEvery(),
+                                                                       config.learningRate(), config.adamBeta1(), config.adamBeta2(),
+                                                                       config.adamEpsilon(), config.hybridOnlineBatch()));
+            else optimizerPtr.reset(new optimizers::SteepestDescentOptimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
+                                                                             config.maxEpochsNoBest(), config.validateEvery(), config.testEvery(),
+                                                                             config.learningRate(), config.momentum(), config.hybridOnlineBatch()));
+            optimizers::Optimizer &optimizer = *optimizerPtr;
             printf("done.\n");
-            printf("Optimizer type: Steepest descent with momentum\n");                         // main.cpp:660-678
+            if (adam) printf("Optimizer type: Adam\n");
+            else printf("Optimizer type: Steepest descent with momentum\n");                    // main.cpp:660-678
             printf("Max training epochs:       %d\n", config.maxEpochs());
             printf("Max epochs until new best: %d\n", config.maxEpochsNoBest());
             printf("Validation error every:    %d\n", config.validateEvery());
             printf("Test error every:          %d\n", config.testEvery());
             printf("Learning rate:             %g\n", (double)config.learningRate());
-            printf("Momentum:                  %g\n\n", (double)config.momentum());
+            if (adam) {
+                printf("Adam beta1 / beta2:        %g / %g\n", (double)config.adamBeta1(), (double)config.adamBeta2());
+                printf("Adam epsilon:              %g\n", (double)config.adamEpsilon());
+                printf("Momentum:                  ignored (--momentum is an option of steepest_descent)\n\n");
+            } else {
+                printf("Momentum:                  %g\n\n", (double)config.momentum());
+            }
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
 
             std::string infoRows;

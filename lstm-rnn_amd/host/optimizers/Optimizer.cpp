@@ -255,6 +255,8 @@ void SteepestDescentOptimizer::exportState(json::Value *jsonDoc) const
 }
 void SteepestDescentOptimizer::importState(const json::Value &jsonDoc)
 {
+    if (jsonDoc.hasMember("adam_optimizer_step"))
+        throw std::runtime_error("The autosave file was written by the adam optimizer and cannot be continued with steepest_descent");
     Optimizer::importState(jsonDoc);
     NeuralNetwork &nn = _neuralNetwork();
     const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
@@ -299,6 +301,83 @@ void SteepestDescentOptimizer::_updateWeights()
         real_t lr = m_learningRate;
         if (layer->learningRate() >= 0.0) lr = layer->learningRate();        // SteepestDescentOptimizer.cu:78-80
         hipCheck(cn_sgd_update(layer->handle(), lr, m_momentum), nn.context());
+    }
+}
+
+AdamOptimizer::AdamOptimizer(NeuralNetwork &neuralNetwork, data_sets::DataSet &trainingSet, data_sets::DataSet &validationSet,
+                             data_sets::DataSet &testSet, int maxEpochs, int maxEpochsNoBest, int validateEvery, int testEvery,
+                             real_t learningRate, real_t beta1, real_t beta2, real_t epsilon, bool hybridOnlineBatch)
+    : Optimizer(neuralNetwork, trainingSet, validationSet, testSet, maxEpochs, maxEpochsNoBest, validateEvery, testEvery, hybridOnlineBatch)
+    , m_learningRate(learningRate), m_beta1(beta1), m_beta2(beta2), m_epsilon(epsilon), m_step(0), m_armed(false) {}
+
+void AdamOptimizer::_armUpdate()
+{
+    NeuralNetwork &nn = _neuralNetwork();
+    ++m_step;
+    m_armed = true;
+    hipCheck(cn_ctx_arm_adam(nn.context(), m_learningRate, m_beta1, m_beta2, m_epsilon, m_step), nn.context());
+}
+
+void AdamOptimizer::_updateWeights()
+{
+    NeuralNetwork &nn = _neuralNetwork();
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
+    if (!m_armed) ++m_step;
+    m_armed = false;
+    if (!hybridOnlineBatch()) {              // batch mode: as in SteepestDescentOptimizer::_updateWeights
+        hipCheck(cn_ctx_take_accumulated(nn.context()), nn.context());
+        if (nn.dataParallel()) hipCheck(cn_allreduce_grads(nn.context(), 0, 0), nn.context());
+    }
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (!layer) continue;
+        real_t lr = m_learningRate;
+        if (layer->learningRate() >= 0.0) lr = layer->learningRate();        // a layer's own "learningRate" is its Adam step size
+        hipCheck(cn_adam_update(layer->handle(), lr, m_beta1, m_beta2, m_epsilon, m_step), nn.context());
+    }
+}
+
+// both moment vectors live on the device (CN_BUF_WEIGHT_DELTAS, CN_BUF_ADAM_SECOND_MOMENTS); autosave moves them through the host
+void AdamOptimizer::exportState(json::Value *jsonDoc) const
+{
+    Optimizer::exportState(jsonDoc);
+    NeuralNetwork &nn = const_cast<AdamOptimizer *>(this)->_neuralNetwork();
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
+    std::vector<Hip::real_vector> m(ls.size()), v(ls.size());
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (!layer) continue;
+        m[i].resize(layer->weightCount()); v[i].resize(layer->weightCount());
+        hipCheck(cn_layer_read(layer->handle(), CN_BUF_WEIGHT_DELTAS, 0, m[i].data(), m[i].size()), nn.context());
+        hipCheck(cn_layer_read(layer->handle(), CN_BUF_ADAM_SECOND_MOMENTS, 0, v[i].data(), v[i].size()), nn.context());
+    }
+    _exportWeights(jsonDoc, "adam_optimizer_first_moments", m);
+    _exportWeights(jsonDoc, "adam_optimizer_second_moments", v);
+    jsonDoc->addMember("adam_optimizer_step", json::Value((double)m_step));
+}
+void AdamOptimizer::importState(const json::Value &jsonDoc)
+{
+    if (!jsonDoc.hasMember("adam_optimizer_step")) {
+        if (jsonDoc.hasMember("steepest_descent_optimizer_weight_deltas"))
+            throw std::runtime_error("The autosave file was written by the steepest_descent optimizer and cannot be continued with adam");
+        throw std::runtime_error("Value 'adam_optimizer_step' is missing in the autosave file");
+    }
+    Optimizer::importState(jsonDoc);
+    NeuralNetwork &nn = _neuralNetwork();
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
+    std::vector<Hip::real_vector> m(ls.size()), v(ls.size());
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (layer) { m[i].resize(layer->weightCount()); v[i].resize(layer->weightCount()); }
+    }
+    _importWeights(jsonDoc, "adam_optimizer_first_moments", &m);
+    _importWeights(jsonDoc, "adam_optimizer_second_moments", &v);
+    m_step = (int64_t)jsonDoc["adam_optimizer_step"].getDouble();
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (!layer) continue;
+        hipCheck(cn_layer_upload(layer->handle(), CN_BUF_WEIGHT_DELTAS, m[i].data(), m[i].size()), nn.context());
+        hipCheck(cn_layer_upload(layer->handle(), CN_BUF_ADAM_SECOND_MOMENTS, v[i].data(), v[i].size()), nn.context());
     }
 }
 

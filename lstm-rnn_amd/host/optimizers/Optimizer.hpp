@@ -1,4 +1,4 @@
-// Epoch protocol and momentum SGD (currennt_lib/src/optimizers/{Optimizer,SteepestDescentOptimizer}.*).
+// Epoch protocol and momentum SGD (currennt_lib/src/optimizers/{Optimizer,SteepestDescentOptimizer}.*), and Adam beside it.
 // Gradient accumulation, the update and best-weight bookkeeping all stay on the device; the host only
 // sequences them.
 #pragma once
@@ -85,6 +85,26 @@ protected:
     void _armUpdate();
 private:
     real_t m_learningRate, m_momentum;
+};
+
+// Adam (include/currennt_hip.h, cn_adam_update; the reference has no counterpart: its second optimizer is rprop,
+// Configuration.cpp:152,265).  Stands beside SteepestDescentOptimizer on the same two seams, so hybrid online/batch and batch
+// learning, weight noise and --gpus N sequence it exactly as they sequence steepest descent.  The library keeps no clock: the
+// update count lives here and travels with the autosave.
+class AdamOptimizer : public Optimizer {
+public:
+    AdamOptimizer(NeuralNetwork &neuralNetwork, data_sets::DataSet &trainingSet, data_sets::DataSet &validationSet,
+                  data_sets::DataSet &testSet, int maxEpochs, int maxEpochsNoBest, int validateEvery, int testEvery,
+                  real_t learningRate, real_t beta1, real_t beta2, real_t epsilon, bool hybridOnlineBatch);
+    void exportState(json::Value *jsonDoc) const;
+    void importState(const json::Value &jsonDoc);
+protected:
+    void _updateWeights();
+    void _armUpdate();
+private:
+    real_t m_learningRate, m_beta1, m_beta2, m_epsilon;
+    int64_t m_step;                 // updates applied so far
+    bool m_armed;                   // _armUpdate() has counted and armed the update _updateWeights() is about to complete
 };
 
 }  // namespace optimizers

@@ -68,6 +68,21 @@ class Layer:
     def weight_updates(self):
         return self._read("weightUpdates", self.weight_count)
 
+    def first_moments(self):
+        """Adam's first moments m: the weightDeltas vector of a context that updates with Adam."""
+        return self._read("weightDeltas", self.weight_count)
+
+    def second_moments(self):
+        """Adam's second moments v (zeros before the context's first Adam call)."""
+        return self._read("adamSecondMoments", self.weight_count)
+
+    def upload(self, which, array):
+        """cn_layer_upload: overwrite a flat parameter vector ("weights", "weightUpdates", "weightDeltas",
+        "adamSecondMoments") from the host."""
+        flat = np.ascontiguousarray(array, np.float32).reshape(-1)
+        B.check(self.net.lib.cn_layer_upload(self.handle, B.BUF[which], flat.ctypes.data_as(C.c_void_p), flat.size),
+                self.net.ctx)
+
     def weight_updates_tensor(self, torch):
         """The layer's weightUpdates in HBM as a torch tensor aliasing the library's memory (no copy)."""
         if getattr(self, "_wu_tensor", None) is None:
@@ -404,6 +419,21 @@ class NeuralNetwork:
     def update_weights_fused(self, learning_rate, momentum):
         """One launch for all layers; layers with a JSON learningRate of their own keep it (cn_layer_set_learning_rate)."""
         B.check(self.lib.cn_sgd_update_all(self.ctx, learning_rate, momentum), self.ctx)
+
+    def update_weights_adam(self, learning_rate, beta1=0.9, beta2=0.999, eps=1e-8, step=1, per_layer=False):
+        """The Adam step of include/currennt_hip.h (cn_adam_update_all; per_layer: cn_adam_update layer by layer).  `step` is the
+        caller's update count, from 1.  Layers with a JSON learningRate of their own keep it."""
+        if not per_layer:
+            B.check(self.lib.cn_adam_update_all(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+            return
+        for lay in self.trainable_layers():
+            lr = lay.learning_rate if lay.learning_rate >= 0.0 else learning_rate
+            B.check(self.lib.cn_adam_update(lay.handle, lr, beta1, beta2, eps, int(step)), self.ctx)
+
+    def arm_adam(self, learning_rate, beta1=0.9, beta2=0.999, eps=1e-8, step=1):
+        """cn_ctx_arm_adam: the coming backward pass applies each layer's Adam step as soon as that layer's gradient is complete;
+        follow the backward pass with update_weights_adam(same values), which completes the step."""
+        B.check(self.lib.cn_ctx_arm_adam(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
 
     def accumulate_updates(self, first):
         """Batch learning (Optimizer.cu:72-85): add this fraction's weightUpdates of all layers to the epoch sum on the device
