@@ -51,6 +51,28 @@ template <typename F> int guarded(F &&f)
     catch (const std::exception &e) { g_last_error = e.what(); return CN_ERR_HIP; }
 }
 
+// a device temporary of one call: freed on every way out of it, a throw included
+struct Scratch {
+    void *p = nullptr;
+    Scratch() = default;
+    explicit Scratch(size_t bytes) { alloc(bytes); }
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { if (p) (void)hipFree(p); }
+    void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
+    template <typename T = float> T *get() const { return (T *)p; }
+};
+
+// The optimizer's rule of an update: momentum SGD (lr, mom) or Adam (lr, b1, b2, eps, step); lr is the caller's learning rate,
+// a layer with a rate of its own replaces it (layer_lr)
+struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0; };
+bool same_rule(const UpdateRule &a, const UpdateRule &b)
+{
+    if (a.adam != b.adam) return false;
+    return a.adam ? a.lr == b.lr && a.b1 == b.b1 && a.b2 == b.b2 && a.eps == b.eps && a.step == b.step
+                  : a.lr == b.lr && a.mom == b.mom;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -141,16 +163,10 @@ struct cn_ctx {
     bool comm_pending = false;
     int64_t comm_exchanges = 0;                // all-reduces enqueued by cn_allreduce_grads (cn_comm_backend)
 
-    // cn_ctx_arm_update: the momentum-SGD step of the coming backward pass is applied layer by layer, as soon as a layer's own
-    // gradient is complete (on the stream that computed it), instead of for all layers behind the last backward kernel
+    // cn_ctx_arm_update / cn_ctx_arm_adam: the step of the coming backward pass (rule `arm`) is applied layer by layer, as soon as
+    // a layer's own gradient is complete (on the stream that computed it), instead of for all layers behind the last backward kernel
     bool armed = false;
-    float arm_lr = 0.f, arm_mom = 0.f;
-    // cn_ctx_arm_adam: the same protocol with the Adam step (arm_adam: which of the two is armed)
-    bool arm_adam = false;
-    struct AdamArgs {
-        float lr = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0;
-        bool same(const AdamArgs &o, float lr_) const { return lr_ == o.lr && b1 == o.b1 && b2 == o.b2 && eps == o.eps && step == o.step; }
-    } arm_a;
+    UpdateRule arm;
     // Optimizer family of the context's first update / arm call (0: none yet).  weightDeltas is the momentum term under one and the
     // first moment under the other, so a context stays with its family.
     enum { FAMILY_NONE = 0, FAMILY_SGD, FAMILY_ADAM };
@@ -456,21 +472,47 @@ void require_comm(cn_ctx *c, const char *who)
 {
     if (!c->has_comm()) throw cn_error(CN_ERR_STATE, std::string(who) + ": no communicator bound to this context (call cn_comm_init first)");
 }
-// cn_fraction_prefetch_resident: the re-layout of the announced fraction, into the alternate buffers
+// ---- re-layout of a fraction ---------------------------------------------------------------------
+bool is_class_post(const cn_layer *post)
+{
+    return post && (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post->kind == CN_LAYER_BINARY_CLASSIFICATION);
+}
+// the buffers a fraction is re-laid out into: the current ones, or the alternates of a prefetch
+struct FractionBuffers { char *pat, *pat_raw; int *tcls; void *in_op; float *targets; };
+// `f` with DEVICE pointers (the caller's resident arrays or a staging area): [T][PS] -> [T][PSp] operands, pattern types with their
+// row map, classes or targets; a binary classification layer's classes become its targets
+void relayout(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b)
+{
+    const bool cls = is_class_post(post);
+    launch_fraction_load(st, c->f32, f.max_seq_length, c->PS, c->PSp, f.pat_types, b.pat,
+                         cls ? f.target_classes : nullptr, b.tcls,
+                         (post && !cls) ? f.targets : nullptr, post ? b.targets : nullptr,
+                         post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN, f.min_seq_length);
+    if (post && post->kind == CN_LAYER_BINARY_CLASSIFICATION)
+        launch_classes_to_targets(st, b.tcls, b.targets, f.max_seq_length * c->PSp);
+}
+// ... out of staging area `slot`: behind its upload (copy stream); the area is free again when the re-layout has read it
+void relayout_staged(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b, int slot)
+{
+    HIP_CHECK(hipStreamWaitEvent(st, c->ev_up[slot], 0));
+    relayout(st, c, input, post, f, b);
+    HIP_CHECK(hipEventRecord(c->ev_free[slot], st));
+    c->stage_used[slot] = true;
+}
+// cn_fraction_prefetch_resident / cn_fraction_prefetch: the re-layout of the announced fraction, into the alternate buffers
 void launch_prefetch(cn_ctx *c, hipStream_t st)
 {
     cn_ctx::Prefetch &p = c->pf;
-    const cn_fraction &f = p.f;
-    const bool cls = p.post && (p.post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || p.post->kind == CN_LAYER_BINARY_CLASSIFICATION);
-    if (p.host) HIP_CHECK(hipStreamWaitEvent(st, c->ev_up[p.slot], 0));      // cn_fraction_prefetch: f points into a staging area whose upload is on the copy stream
-    launch_fraction_load(st, c->f32, f.max_seq_length, c->PS, c->PSp, (const char *)f.pat_types, p.pat,
-                         cls ? (const int *)f.target_classes : nullptr, p.tcls,
-                         (p.post && !cls) ? (const float *)f.targets : nullptr, p.post ? p.targets : nullptr,
-                         p.post ? p.post->size : 0, (const float *)f.inputs, p.input->size, p.in_op, p.input->Lp, c->rowmap_of(p.pat_raw), (int)c->pat_maxN, f.min_seq_length);
-    if (p.post && p.post->kind == CN_LAYER_BINARY_CLASSIFICATION)
-        launch_classes_to_targets(st, p.tcls, p.targets, f.max_seq_length * c->PSp);
-    if (p.host) { HIP_CHECK(hipEventRecord(c->ev_free[p.slot], st)); c->stage_used[p.slot] = true; }
+    const FractionBuffers alt{p.pat, p.pat_raw, p.tcls, p.in_op, p.targets};
+    if (p.host) relayout_staged(st, c, p.input, p.post, p.f, alt, p.slot);     // (f points into the staging area)
+    else relayout(st, c, p.input, p.post, p.f, alt);
     p.launched = true;
+}
+void ensure_fork_events(cn_layer *l)
+{
+    if (l->ev_fork) return;
+    HIP_CHECK(hipEventCreateWithFlags(&l->ev_fork, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&l->ev_join, hipEventDisableTiming));
 }
 // run `f(stream)` on the side stream after everything enqueued on the main stream so far
 // (fork_attached: ev_fork already completes with the last main-stream kernel, see fork_event)
@@ -483,7 +525,7 @@ template <typename F> void on_side(cn_layer *l, F &&f, bool fork_attached = fals
     // stream it saves the two cross-stream hand-offs (fork, join) in front of the update.
     const bool tail_on_main = !opt().tail_on_side;
     if (tail_on_main && l->prev && !l->prev->trainable && !fork_attached) { f(c->stream, nullptr); return; }
-    if (!l->ev_fork) { HIP_CHECK(hipEventCreateWithFlags(&l->ev_fork, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&l->ev_join, hipEventDisableTiming)); }
+    ensure_fork_events(l);
     if (!fork_attached) HIP_CHECK(hipEventRecord(l->ev_fork, c->stream));
     // a recurrent kernel follows on the main stream when the preceding layer is an LSTM layer: slow lane (a CU-masked stream, so
     // that the gradient products leave the latency-bound recurrent kernel's CUs and memory path alone) -- unless the products
@@ -533,7 +575,7 @@ hipEvent_t fork_event(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     if (!c->overlap || !c->attach_forks) return nullptr;
-    if (!l->ev_fork) { HIP_CHECK(hipEventCreateWithFlags(&l->ev_fork, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&l->ev_join, hipEventDisableTiming)); }
+    ensure_fork_events(l);
     return l->ev_fork;
 }
 void timing_collect(cn_ctx *c)
@@ -612,21 +654,17 @@ void finalize(cn_ctx *c)
 }
 
 // ---- optimizer rule of an update launch ---------------------------------------------------------
-// momentum SGD (lr, mom) or Adam (a; a.lr is the caller's learning rate)
-struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f; cn_ctx::AdamArgs a; };
-UpdateRule armed_rule(const cn_ctx *c)
-{
-    UpdateRule r; r.adam = c->arm_adam; r.lr = c->arm_adam ? c->arm_a.lr : c->arm_lr; r.mom = c->arm_mom; r.a = c->arm_a;
-    return r;
-}
+// a layer's JSON "learningRate" (SteepestDescentOptimizer.cu:78-80) replaces the rule's
+float layer_lr(const cn_layer *l, const UpdateRule &r) { return l->own_lr >= 0.f ? l->own_lr : r.lr; }
 // The scalars of include/currennt_hip.h (cn_adam_update): formed in double from the float arguments, rounded once
-AdamScalars adam_scalars(const cn_ctx::AdamArgs &a, float lr)
+// lr: the effective rate (layer_lr)
+AdamScalars adam_scalars(const UpdateRule &r, float lr)
 {
-    const double b1 = a.b1, b2 = a.b2, t = (double)a.step;
+    const double b1 = r.b1, b2 = r.b2, t = (double)r.step;
     const double c2 = std::sqrt(1.0 - std::pow(b2, t)), c1 = 1.0 - std::pow(b1, t);
     AdamScalars s;
-    s.b1 = a.b1; s.b2 = a.b2; s.omb1 = (float)(1.0 - b1); s.omb2 = (float)(1.0 - b2);
-    s.alpha_t = (float)((double)lr * c2 / c1); s.eps_t = (float)((double)a.eps * c2);
+    s.b1 = r.b1; s.b2 = r.b2; s.omb1 = (float)(1.0 - b1); s.omb2 = (float)(1.0 - b2);
+    s.alpha_t = (float)((double)lr * c2 / c1); s.eps_t = (float)((double)r.eps * c2);
     return s;
 }
 void ensure_adam_v(cn_ctx *c)
@@ -646,11 +684,19 @@ void bind_family(cn_ctx *c, int family, const char *fn)
                        " would read its weightDeltas as something they are not (momentum term / first moment)");
     c->family = family;
 }
-void check_adam_args(const char *fn, float beta1, float beta2, float eps, int64_t step)
+void check_adam_args(const char *fn, const UpdateRule &r)
 {
-    if (step < 1) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": step must be >= 1 (the caller's update count)");
-    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": beta1 and beta2 must lie in [0, 1)");
-    if (!(eps > 0.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": eps must be > 0");
+    if (r.step < 1) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": step must be >= 1 (the caller's update count)");
+    if (!(r.b1 >= 0.f && r.b1 < 1.f) || !(r.b2 >= 0.f && r.b2 < 1.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": beta1 and beta2 must lie in [0, 1)");
+    if (!(r.eps > 0.f)) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": eps must be > 0");
+}
+
+// one layer's operand copies from its flat weights
+void launch_pack(hipStream_t st, cn_layer *l)
+{
+    const bool f32 = l->ctx->f32;
+    if (l->lstm) launch_lstm_pack(st, f32, lstm_geom(l), l->bias, l->w, l->Win, l->WinT, l->Wrec, l->WrecT, l->bias_p, l->peep_p);
+    else         launch_ff_pack(st, f32, ff_geom(l), l->bias, l->w, l->Win, l->WinT, l->bias_p);
 }
 
 void repack(cn_layer *l)
@@ -664,8 +710,7 @@ void repack(cn_layer *l)
     }
     if (!l->dirty) return;
     Timed tm(c, KC_OTHER);
-    if (l->lstm) launch_lstm_pack(c->stream, c->f32, lstm_geom(l), l->bias, l->w, l->Win, l->WinT, l->Wrec, l->WrecT, l->bias_p, l->peep_p);
-    else         launch_ff_pack(c->stream, c->f32, ff_geom(l), l->bias, l->w, l->Win, l->WinT, l->bias_p);
+    launch_pack(c->stream, l);
     l->dirty = false;
 }
 
@@ -757,6 +802,29 @@ void check_rec_lds(const cn_layer *l, bool bwd)
                        " or shorter fractions (truncate_seq)");
 }
 
+// The next item of a group: a layer's geometry and the operand copies the launch rebuilds from its flat weights
+PackItem &add_pack_item(PackGroup &grp, const cn_layer *l)
+{
+    PackItem &it = grp.item[grp.n++];
+    it.lstm = l->lstm ? 1 : 0;
+    if (l->lstm) it.lg = lstm_geom(l); else it.fg = ff_geom(l);
+    it.bias = l->bias; it.w = l->w; it.Win = l->Win; it.WinT = l->WinT; it.Wrec = l->Wrec; it.WrecT = l->WrecT;
+    it.bias_p = l->bias_p; it.peep_p = l->peep_p;
+    return it;
+}
+// ... and the step that rides on it, for the item added last: update mode (PackItem::update), the rule with the layer's effective
+// rate; Adam: the item's second moments and the scalars all items share
+void set_pack_update(PackGroup &grp, PackAdam &ad, int mode, const UpdateRule &r, const cn_layer *l)
+{
+    PackItem &it = grp.item[grp.n - 1];
+    it.update = mode; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd;
+    it.lr = layer_lr(l, r); it.mom = r.mom;
+    if (r.adam) {
+        const AdamScalars a = adam_scalars(r, it.lr);
+        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
+        ad.v[grp.n - 1] = l->ctx->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
+    }
+}
 // One layer's weight update + operand copies as one launch of the grouped pack kernel on `st`.
 // mode 1: gradient from the flat weightUpdates; mode 2: from the packed accumulators (unpack fused in, cn_elementwise.hip)
 // folds (mode 2, deterministic mode; nullable): f_in, f_rec[0], f_rec[1], f_bias -- the partial sums the launch adds itself
@@ -765,21 +833,11 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule
 {
     cn_ctx *c = l->ctx;
     PackGroup grp{};
-    PackItem &it = grp.item[grp.n++];
-    it.lstm = l->lstm ? 1 : 0;
-    if (l->lstm) it.lg = lstm_geom(l); else it.fg = ff_geom(l);
-    it.bias = l->bias; it.w = l->w; it.Win = l->Win; it.WinT = l->WinT; it.Wrec = l->Wrec; it.WrecT = l->WrecT;
-    it.bias_p = l->bias_p; it.peep_p = l->peep_p;
-    it.update = mode; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd; it.wu_rw = l->wu;
-    it.lr = l->own_lr >= 0.f ? l->own_lr : r.lr; it.mom = r.mom;
-    it.g_in = l->dWin; it.g_rec = l->dWrec; it.g_bias = l->dbias; it.g_peep = l->dpeep;
-    if (folds) { it.update = 3; it.f_in = folds[0]; it.f_rec[0] = folds[1]; it.f_rec[1] = folds[2]; it.f_bias = folds[3]; }
     PackAdam ad{};
-    if (r.adam) {
-        const AdamScalars a = adam_scalars(r.a, it.lr);
-        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
-        ad.v[0] = c->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
-    }
+    PackItem &it = add_pack_item(grp, l);
+    set_pack_update(grp, ad, mode, r, l);
+    it.wu_rw = l->wu; it.g_in = l->dWin; it.g_rec = l->dWrec; it.g_bias = l->dbias; it.g_peep = l->dpeep;
+    if (folds) { it.update = 3; it.f_in = folds[0]; it.f_rec[0] = folds[1]; it.f_rec[1] = folds[2]; it.f_bias = folds[3]; }
     launch_pack_group(st, c->f32, grp, done, r.adam ? &ad : nullptr);
     l->dirty = false; l->pack_pending = false; l->updated = true;
 }
@@ -897,7 +955,7 @@ void lstm_backward(cn_layer *l)
                     {l->det_ws ? l->det_ws + (size_t)DET_MAX_SPLITS * (size_t)R * l->Pp : nullptr, 4L * Hp * Hp, used_rec[0], 0},
                     {l->det_ws ? l->det_ws + (size_t)DET_MAX_SPLITS * ((size_t)R * l->Pp + (size_t)4 * Hp * Hp) : nullptr, 4L * Hp * Hp, used_rec[1], 0},
                     {l->gpart, (long)slot, det_grid, 1}};
-                launch_layer_update(st, l, 2, armed_rule(c), join, defer ? folds : nullptr);
+                launch_layer_update(st, l, 2, c->arm, join, defer ? folds : nullptr);
             } else launch_lstm_unpack_grads(st, lstm_geom(l), l->dWin, l->dWrec, l->dbias, l->dpeep, l->wu, join);
         }
         return join != nullptr;
@@ -1001,7 +1059,7 @@ void ff_backward(cn_layer *l)
                 // (the column sums' partial rows: colfold describes them; its target, the packed bias gradient, stays zero)
                 const PackFold folds[4] = {{l->det_ws, (long)l->Lp * l->Pp, used_in, 0}, {nullptr, 0, 0, 0}, {nullptr, 0, 0, 0},
                                            {colfold.part, colfold.stride, colfold.nparts, 0}};
-                launch_layer_update(st, l, 2, armed_rule(c), join, defer ? folds : nullptr);
+                launch_layer_update(st, l, 2, c->arm, join, defer ? folds : nullptr);
             } else launch_ff_unpack_grads(st, ff_geom(l), l->bias, l->dWin, l->dbias, l->wu, join);
         }
         return join != nullptr;
@@ -1350,7 +1408,7 @@ int cn_allreduce_grads(cn_ctx *ctx, cn_layer *const *layers, int n)
                 else if (ctx->ipc) ipc_reduce(ctx, l->wu, (size_t)l->nw);
                 else RCCL_CHECK(rccl().AllReduce(l->wu, l->wu, (size_t)l->nw, ncclFloat32, ncclSum, ctx->comm, ctx->comm_stream));
                 // armed update: the layer's step follows its reduction on the communication stream
-                if (ctx->armed && !l->updated) launch_layer_update(ctx->comm_stream, l, 1, armed_rule(ctx), nullptr);
+                if (ctx->armed && !l->updated) launch_layer_update(ctx->comm_stream, l, 1, ctx->arm, nullptr);
             }
         }
         HIP_CHECK(hipEventRecord(ctx->ev_comm, ctx->comm_stream));
@@ -1564,14 +1622,21 @@ static void check_fraction(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
     if (f->min_seq_length < 0 || f->min_seq_length > T) throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: bad min_seq_length");
     if (!f->pat_types || !f->inputs) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: pat_types / inputs missing");
 }
+static void require_targets(const char *fn, const cn_layer *post, const cn_fraction *f)
+{
+    if (!post) return;
+    const bool cls = is_class_post(post);
+    if (cls ? !f->target_classes : !f->targets) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + (cls ? ": target_classes missing" : ": targets missing"));
+}
 // Host buffers of a fraction -> pinned staging area -> ONE contiguous upload on the copy stream ([patTypes | classes or targets |
-// inputs]; the two staging areas alternate).  Returns the area and where its parts lie; ev_up[slot] completes with the upload.
-struct Staged { int slot; char *dv; size_t b_pat, b_tgt_al, W; bool cls; };
+// inputs]; the two staging areas alternate).  Returns the area and the fraction with its pointers into it; ev_up[slot] completes
+// with the upload.
+struct Staged { int slot; cn_fraction f; };
 static Staged stage_upload(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, const cn_fraction *f)
 {
     const int T = f->max_seq_length;
     const size_t PS = ctx->PS;
-    const bool cls = post_output && (post_output->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post_output->kind == CN_LAYER_BINARY_CLASSIFICATION);
+    const bool cls = is_class_post(post_output);
     const size_t rows = (size_t)T * PS;
     const size_t W = post_output ? (size_t)post_output->size : 0;
     const size_t b_pat = (rows + 15) & ~(size_t)15;
@@ -1605,7 +1670,12 @@ static Staged stage_upload(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
     memcpy(h + b_pat + b_tgt_al, f->inputs, b_in);
     HIP_CHECK(hipMemcpyAsync(dv, h, need, hipMemcpyHostToDevice, ctx->copy));
     HIP_CHECK(hipEventRecord(ctx->ev_up[slot], ctx->copy));
-    return Staged{slot, dv, b_pat, b_tgt_al, W, cls};
+    Staged sg{slot, *f};
+    sg.f.pat_types = dv;
+    sg.f.target_classes = (post_output && cls) ? (const int *)(dv + b_pat) : nullptr;
+    sg.f.targets = (post_output && !cls) ? (const float *)(dv + b_pat) : nullptr;
+    sg.f.inputs = (const float *)(dv + b_pat + b_tgt_al);
+    return sg;
 }
 
 static bool same_fraction(const cn_fraction &a, const cn_fraction &b)
@@ -1614,10 +1684,25 @@ static bool same_fraction(const cn_fraction &a, const cn_fraction &b)
            a.input_pattern_size == b.input_pattern_size && a.output_pattern_size == b.output_pattern_size &&
            a.pat_types == b.pat_types && a.inputs == b.inputs && a.target_classes == b.target_classes && a.targets == b.targets;
 }
+// `f` is the current fraction from here on
+static void set_current(cn_ctx *ctx, const cn_fraction *f)
+{
+    const int T = f->max_seq_length;
+    ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = T * ctx->PSp; ctx->Next = T * ctx->PS; ctx->numSeqs = f->num_sequences;
+    ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2);
+    ctx->loaded = true;
+}
+// the alternate buffers a prefetch re-laid its fraction out into become the current ones
+static void swap_in_prefetched(cn_ctx *ctx, cn_layer *input, cn_layer *post_output)
+{
+    cn_ctx::Prefetch &pf = ctx->pf;
+    std::swap(ctx->d_pat, pf.pat); std::swap(ctx->d_pat_raw, pf.pat_raw); std::swap(ctx->d_tcls, pf.tcls);
+    std::swap(input->out_op, pf.in_op);
+    if (post_output && post_output->targets) std::swap(post_output->targets, pf.targets);
+}
 static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, const cn_fraction *f, bool resident)
 {
     if (!ctx || !input || !f) { g_last_error = "cn_fraction_load: NULL argument"; return CN_ERR_BAD_ARG; }
-    const hipMemcpyKind kind = resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     return guarded([&] {
         enter(ctx);
         check_fraction(ctx, input, post_output, f);
@@ -1625,94 +1710,48 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
         finalize(ctx);
         join_side(ctx);                      // gradient GEMMs of the previous fraction still read the activations
         flush_loss(ctx);                     // (a deferred loss sum counts the rows of the fraction that is being replaced)
-        const size_t PS = ctx->PS, PSp = ctx->PSp;
-        const size_t N = (size_t)T * PSp;
         Timed tm(ctx, KC_OTHER);
-        if (resident) {      // everything is in HBM already: one kernel re-lays it out
-            const bool cls = post_output && (post_output->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post_output->kind == CN_LAYER_BINARY_CLASSIFICATION);
-            if (post_output && cls && !f->target_classes) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: target_classes missing");
-            if (post_output && !cls && !f->targets) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: targets missing");
-            cn_ctx::Prefetch &pf = ctx->pf;
-            const bool hit = pf.valid && pf.launched && !pf.host && pf.input == input && pf.post == post_output && same_fraction(pf.f, *f);
-            pf.valid = false;          // a prefetch serves the very next load or nothing
-            if (hit) {
-                ++pf.hits;
-                // the side stream has re-laid this fraction out already (join_side above ordered this stream behind it): the
-                // alternate buffers become the current ones
-                std::swap(ctx->d_pat, pf.pat); std::swap(ctx->d_pat_raw, pf.pat_raw); std::swap(ctx->d_tcls, pf.tcls);
-                std::swap(input->out_op, pf.in_op);
-                if (post_output && post_output->targets) std::swap(post_output->targets, pf.targets);
-            } else {
-            launch_fraction_load(ctx->stream, ctx->f32, T, (int)PS, (int)PSp, f->pat_types, ctx->d_pat,
-                                 cls ? f->target_classes : nullptr, ctx->d_tcls,
-                                 (post_output && !cls) ? f->targets : nullptr, post_output ? post_output->targets : nullptr,
-                                 post_output ? post_output->size : 0, f->inputs, input->size, input->out_op, input->Lp, ctx->rowmap_of(ctx->d_pat_raw), (int)ctx->pat_maxN, f->min_seq_length);
-            if (post_output && post_output->kind == CN_LAYER_BINARY_CLASSIFICATION)
-                launch_classes_to_targets(ctx->stream, ctx->d_tcls, post_output->targets, (int)N);
-            }
-            ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = (int)N; ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2); ctx->Next = T * (int)PS; ctx->numSeqs = f->num_sequences;
-            ctx->loaded = true;
-            return;
-        }
-        {   // cn_fraction_prefetch announced exactly this fraction and the side stream has re-laid it out (join_side above ordered
-            // this stream behind it): the alternate buffers become the current ones, nothing is copied or launched here
-            cn_ctx::Prefetch &pf = ctx->pf;
-            const bool hit = pf.valid && pf.launched && pf.host && pf.input == input && pf.post == post_output && same_fraction(pf.f_host, *f);
-            pf.valid = false;          // a prefetch serves the very next load or nothing
-            if (hit) {
-                ++pf.hits;
-                std::swap(ctx->d_pat, pf.pat); std::swap(ctx->d_pat_raw, pf.pat_raw); std::swap(ctx->d_tcls, pf.tcls);
-                std::swap(input->out_op, pf.in_op);
-                if (post_output && post_output->targets) std::swap(post_output->targets, pf.targets);
-                ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = (int)N; ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2); ctx->Next = T * (int)PS; ctx->numSeqs = f->num_sequences;
-                ctx->loaded = true;
-                return;
-            }
-        }
-        if (ctx->overlap) {
+        require_targets("cn_fraction_load", post_output, f);
+        cn_ctx::Prefetch &pf = ctx->pf;
+        // a prefetch of the same kind (resident / host buffers) announced exactly this fraction and the side stream has re-laid it
+        // out (join_side above ordered this stream behind it): nothing is copied or launched here
+        const bool hit = pf.valid && pf.launched && pf.host == !resident && pf.input == input && pf.post == post_output &&
+                         same_fraction(pf.host ? pf.f_host : pf.f, *f);
+        pf.valid = false;          // a prefetch serves the very next load or nothing
+        const FractionBuffers cur{ctx->d_pat, ctx->d_pat_raw, ctx->d_tcls, input->out_op, post_output ? post_output->targets : nullptr};
+        if (hit) {
+            ++pf.hits;
+            swap_in_prefetched(ctx, input, post_output);
+        } else if (resident) {      // everything is in HBM already: one kernel re-lays it out
+            relayout(ctx->stream, ctx, input, post_output, *f, cur);
+        } else if (ctx->overlap) {
             // Host buffers: pack [patTypes | classes or targets | inputs] into pinned memory, ONE contiguous upload
             // on the copy stream (it runs while the previous fraction still computes: the staging areas alternate),
             // then the same re-layout kernel as the resident path.  (Strided 2-D copies from pageable memory cost
             // one transfer per time step: 3.5 ms per fraction of 2.3 MB, twice the whole training step.)
-            const bool cls = post_output && (post_output->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post_output->kind == CN_LAYER_BINARY_CLASSIFICATION);
-            if (post_output && cls && !f->target_classes) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: target_classes missing");
-            if (post_output && !cls && !f->targets) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: targets missing");
             const Staged sg = stage_upload(ctx, input, post_output, f);
-            const int slot = sg.slot; char *dv = sg.dv; const size_t b_pat = sg.b_pat, b_tgt_al = sg.b_tgt_al, W = sg.W;
-            HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_up[slot], 0));
-            launch_fraction_load(ctx->stream, ctx->f32, T, (int)PS, (int)PSp, dv, ctx->d_pat,
-                                 cls ? (const int *)(dv + b_pat) : nullptr, ctx->d_tcls,
-                                 (post_output && !cls) ? (const float *)(dv + b_pat) : nullptr, post_output ? post_output->targets : nullptr,
-                                 (int)W, (const float *)(dv + b_pat + b_tgt_al), input->size, input->out_op, input->Lp, ctx->rowmap_of(ctx->d_pat_raw), (int)ctx->pat_maxN, f->min_seq_length);
-            HIP_CHECK(hipEventRecord(ctx->ev_free[slot], ctx->stream));
-            ctx->stage_used[slot] = true;
-            if (post_output && post_output->kind == CN_LAYER_BINARY_CLASSIFICATION)
-                launch_classes_to_targets(ctx->stream, ctx->d_tcls, post_output->targets, (int)N);
-            ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = (int)N; ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2); ctx->Next = T * (int)PS; ctx->numSeqs = f->num_sequences;
-            ctx->loaded = true;
-            return;
-        }
-        // CN_NO_OVERLAP: strided copies [T][PS] -> [T][PSp]: pad slots keep their permanent NONE / -1 / 0 contents
-        HIP_CHECK(hipMemcpy2DAsync(ctx->d_pat, PSp, f->pat_types, PS, PS, T, kind, ctx->stream));
-        launch_rowmap(ctx->stream, ctx->d_pat, (int)N, ctx->rowmap_of(ctx->d_pat_raw), (int)ctx->pat_maxN, f->min_seq_length * (int)PSp);
-        const size_t irow = (size_t)input->size * sizeof(float);
-        HIP_CHECK(hipMemcpy2DAsync(input->stage_in, PSp * irow, f->inputs, PS * irow, PS * irow, T, kind, ctx->stream));
-        if (post_output) {
-            if (post_output->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post_output->kind == CN_LAYER_BINARY_CLASSIFICATION) {
-                if (!f->target_classes) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: target_classes missing");
+            relayout_staged(ctx->stream, ctx, input, post_output, sg.f, cur, sg.slot);
+        } else {
+            // CN_NO_OVERLAP: strided copies [T][PS] -> [T][PSp]: pad slots keep their permanent NONE / -1 / 0 contents
+            const size_t PS = ctx->PS, PSp = ctx->PSp;
+            const int N = T * (int)PSp;
+            const hipMemcpyKind kind = hipMemcpyHostToDevice;
+            HIP_CHECK(hipMemcpy2DAsync(ctx->d_pat, PSp, f->pat_types, PS, PS, T, kind, ctx->stream));
+            launch_rowmap(ctx->stream, ctx->d_pat, N, ctx->rowmap_of(ctx->d_pat_raw), (int)ctx->pat_maxN, f->min_seq_length * (int)PSp);
+            const size_t irow = (size_t)input->size * sizeof(float);
+            HIP_CHECK(hipMemcpy2DAsync(input->stage_in, PSp * irow, f->inputs, PS * irow, PS * irow, T, kind, ctx->stream));
+            if (is_class_post(post_output)) {
                 HIP_CHECK(hipMemcpy2DAsync(ctx->d_tcls, PSp * sizeof(int), f->target_classes, PS * sizeof(int), PS * sizeof(int), T, kind, ctx->stream));
                 if (post_output->kind == CN_LAYER_BINARY_CLASSIFICATION)
-                    launch_classes_to_targets(ctx->stream, ctx->d_tcls, post_output->targets, (int)N);
-            } else {
-                if (!f->targets) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: targets missing");
+                    launch_classes_to_targets(ctx->stream, ctx->d_tcls, post_output->targets, N);
+            } else if (post_output) {
                 const size_t trow = (size_t)post_output->size * sizeof(float);
                 HIP_CHECK(hipMemcpy2DAsync(post_output->targets, PSp * trow, f->targets, PS * trow, PS * trow, T, kind, ctx->stream));
             }
+            launch_pad_convert(ctx->stream, ctx->f32, input->stage_in, N, input->size, input->out_op, input->Lp);
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));     // the caller may reuse its host buffers on return
         }
-        launch_pad_convert(ctx->stream, ctx->f32, input->stage_in, (int)N, input->size, input->out_op, input->Lp);
-        ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = (int)N; ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2); ctx->Next = T * (int)PS; ctx->numSeqs = f->num_sequences;
-        ctx->loaded = true;
-        if (!resident) HIP_CHECK(hipStreamSynchronize(ctx->stream));     // the caller may reuse its host buffers on return
+        set_current(ctx, f);
     });
 }
 
@@ -1740,9 +1779,7 @@ static int fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output
         enter(ctx);
         check_fraction(ctx, input, post_output, f);
         if (host && !ctx->overlap) return;            // CN_NO_OVERLAP: no copy stream, no side streams: the load does it all
-        const bool cls = post_output && (post_output->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post_output->kind == CN_LAYER_BINARY_CLASSIFICATION);
-        if (post_output && cls && !f->target_classes) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_prefetch_resident: target_classes missing");
-        if (post_output && !cls && !f->targets) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_prefetch_resident: targets missing");
+        require_targets("cn_fraction_prefetch_resident", post_output, f);
         cn_ctx::Prefetch &pf = ctx->pf;
         if (pf.valid && pf.launched) throw cn_error(CN_ERR_STATE, "cn_fraction_prefetch_resident: the previous prefetch has not been consumed by a cn_fraction_load_resident yet");
         if (!pf.allocated) {          // the alternates of the four buffers a fraction is re-laid out into (same initial contents)
@@ -1762,11 +1799,7 @@ static int fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output
             // pack and upload NOW (copy stream, beside whatever the device is doing); the re-layout follows on the side stream of the
             // next gradient work, reading the staging area
             const Staged sg = stage_upload(ctx, input, post_output, f);
-            pf.f_host = *f; pf.slot = sg.slot;
-            pf.f.pat_types = sg.dv;
-            pf.f.target_classes = (post_output && sg.cls) ? (const int *)(sg.dv + sg.b_pat) : nullptr;
-            pf.f.targets = (post_output && !sg.cls) ? (const float *)(sg.dv + sg.b_pat) : nullptr;
-            pf.f.inputs = (const float *)(sg.dv + sg.b_pat + sg.b_tgt_al);
+            pf.f_host = *f; pf.slot = sg.slot; pf.f = sg.f;
         }
         pf.valid = true;
     });
@@ -1810,7 +1843,7 @@ int cn_layer_backward(cn_layer *layer)
         require_loaded(c);
         finalize(c);
         if (layer->trainable && layer->updated)
-            throw cn_error(CN_ERR_STATE, c->arm_adam
+            throw cn_error(CN_ERR_STATE, c->arm.adam
                 ? "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_adam_update_all / cn_adam_update first)"
                 : "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_sgd_update_all / cn_sgd_update first)");
         if (layer->lstm) lstm_backward(layer);
@@ -1826,6 +1859,34 @@ int cn_layer_backward(cn_layer *layer)
     });
 }
 
+// The current fraction's error and correct count into dst[2]: overwritten (per_call, cn_loss_eval) or added to (cn_loss_accumulate)
+static void launch_loss(cn_layer *post, float *dst, bool per_call)
+{
+    cn_ctx *c = post->ctx;
+    cn_layer *o = post->prev;
+    if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION && c->rowstat_of == o) {      // the softmax forward pass left the row statistics
+        launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, dst, per_call);
+        return;
+    }
+    flush_loss(c);                     // (the row statistics are about to be overwritten)
+    if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION)
+        launch_mcc_eval(c->stream, posteriors(o), c->d_tcls, c->N, post->size, o->Lp, dst, per_call, c->d_rowstat);
+    else
+        launch_post_eval(c->stream, post_kind(post), posteriors(o), post->targets, c->d_pat, c->N, o->size, o->Lp, c->d_rowstat, dst, per_call);
+    c->rowstat_of = nullptr;           // the row statistics now are this evaluation's terms
+}
+// {error, #correct as int bits} at `src` to the host; reset: the running sums are cleared behind the read
+static void read_loss_sums(cn_ctx *c, const float *src, bool reset, float *err, int *correct)
+{
+    float h[2];
+    HIP_CHECK(hipMemcpyAsync(h, src, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    if (reset) HIP_CHECK(hipMemsetAsync(c->d_loss_acc, 0, sizeof(h), c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    check_fault(c);
+    *err = h[0];
+    memcpy(correct, &h[1], sizeof(int));
+}
+
 int cn_loss_eval(cn_layer *post, float *error, int *correct)
 {
     if (!post || !error) { g_last_error = "cn_loss_eval: NULL argument"; return CN_ERR_BAD_ARG; }
@@ -1834,30 +1895,13 @@ int cn_loss_eval(cn_layer *post, float *error, int *correct)
         enter(c);
         if (!post->post) throw cn_error(CN_ERR_BAD_ARG, "cn_loss_eval: not a post output layer");
         require_loaded(c);
-        cn_layer *o = post->prev;
         {
             Timed tm(c, KC_OTHER);
-            if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION && c->rowstat_of == o)
-                launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, c->d_loss, true);
-            else if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION) {
-                flush_loss(c);
-                launch_mcc_eval(c->stream, posteriors(o), c->d_tcls, c->N, post->size, o->Lp, c->d_loss, true, c->d_rowstat);
-                c->rowstat_of = nullptr;       // (the row statistics now are this evaluation's terms)
-            } else {
-                flush_loss(c);
-                launch_post_eval(c->stream, post_kind(post), posteriors(o), post->targets, c->d_pat, c->N, o->size, o->Lp, c->d_rowstat, c->d_loss, true);
-                c->rowstat_of = nullptr;       // the softmax row statistics were overwritten
-            }
+            launch_loss(post, c->d_loss, true);
         }
-        float h[2];
-        HIP_CHECK(hipMemcpyAsync(h, c->d_loss, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-        check_fault(c);
-        *error = h[0];
-        if (correct) {
-            int cc; memcpy(&cc, &h[1], sizeof(int));
-            *correct = (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION || post->kind == CN_LAYER_BINARY_CLASSIFICATION) ? cc : -1;
-        }
+        int cc = 0;
+        read_loss_sums(c, c->d_loss, false, error, &cc);
+        if (correct) *correct = is_class_post(post) ? cc : -1;
     });
 }
 
@@ -1879,15 +1923,7 @@ int cn_loss_accumulate(cn_layer *post)
             return;
         }
         Timed tm(c, KC_OTHER);
-        if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION && c->rowstat_of == o)
-            launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, c->d_loss_acc, false);
-        else if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION) {
-            launch_mcc_eval(c->stream, posteriors(o), c->d_tcls, c->N, post->size, o->Lp, c->d_loss_acc, false, c->d_rowstat);
-            c->rowstat_of = nullptr;
-        } else {
-            launch_post_eval(c->stream, post_kind(post), posteriors(o), post->targets, c->d_pat, c->N, o->size, o->Lp, c->d_rowstat, c->d_loss_acc, false);
-            c->rowstat_of = nullptr;
-        }
+        launch_loss(post, c->d_loss_acc, false);       // (nothing is deferred any more: its flush_loss does nothing)
     });
 }
 
@@ -1897,13 +1933,10 @@ int cn_loss_read(cn_ctx *ctx, float *error_sum, int64_t *correct_sum, int reset)
     return guarded([&] {
         enter(ctx);
         flush_loss(ctx);
-        float h[2];
-        HIP_CHECK(hipMemcpyAsync(h, ctx->d_loss_acc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        if (reset) HIP_CHECK(hipMemsetAsync(ctx->d_loss_acc, 0, sizeof(h), ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        check_fault(ctx);
-        if (error_sum) *error_sum = h[0];
-        if (correct_sum) { int cc; memcpy(&cc, &h[1], sizeof(int)); *correct_sum = cc; }
+        float err = 0.f; int cc = 0;
+        read_loss_sums(ctx, ctx->d_loss_acc, reset != 0, &err, &cc);
+        if (error_sum) *error_sum = err;
+        if (correct_sum) *correct_sum = cc;
     });
 }
 
@@ -1914,29 +1947,21 @@ int cn_loss_read_global(cn_ctx *ctx, float *error_sum, int64_t *correct_sum, int
         require_comm(ctx, "cn_loss_read_global");
         enter(ctx);
         flush_loss(ctx);
-        float *g = ctx->d_loss + 4, h[2];
-        if (ctx->ipc) {
-            HIP_CHECK(hipMemcpyAsync(h, ctx->d_loss_acc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-            if (reset) HIP_CHECK(hipMemsetAsync(ctx->d_loss_acc, 0, sizeof(h), ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            check_fault(ctx);
-            int cc; memcpy(&cc, &h[1], sizeof(int));
-            try { ipc_comm_check(ctx->ipc, ctx->comm_stream); ipc_allreduce_loss(ctx->ipc, &h[0], &cc); }
+        float err = 0.f; int cc = 0;
+        if (ctx->ipc) {          // this rank's sums to the host, added across the ranks there
+            read_loss_sums(ctx, ctx->d_loss_acc, reset != 0, &err, &cc);
+            try { ipc_comm_check(ctx->ipc, ctx->comm_stream); ipc_allreduce_loss(ctx->ipc, &err, &cc); }
             catch (const std::exception &e) { ipc_comm_mark_failed(ctx->ipc); throw cn_error(CN_ERR_COMM, e.what()); }
-            if (error_sum) *error_sum = h[0];
-            if (correct_sum) *correct_sum = cc;
-            return;
+        } else {                 // added across the ranks on the device
+            float *g = ctx->d_loss + 4;
+            RCCL_CHECK(rccl().GroupStart());
+            RCCL_CHECK(rccl().AllReduce(ctx->d_loss_acc, g, 1, ncclFloat32, ncclSum, ctx->comm, ctx->stream));
+            RCCL_CHECK(rccl().AllReduce(ctx->d_loss_acc + 1, g + 1, 1, ncclInt32, ncclSum, ctx->comm, ctx->stream));
+            RCCL_CHECK(rccl().GroupEnd());
+            read_loss_sums(ctx, g, reset != 0, &err, &cc);
         }
-        RCCL_CHECK(rccl().GroupStart());
-        RCCL_CHECK(rccl().AllReduce(ctx->d_loss_acc, g, 1, ncclFloat32, ncclSum, ctx->comm, ctx->stream));
-        RCCL_CHECK(rccl().AllReduce(ctx->d_loss_acc + 1, g + 1, 1, ncclInt32, ncclSum, ctx->comm, ctx->stream));
-        RCCL_CHECK(rccl().GroupEnd());
-        HIP_CHECK(hipMemcpyAsync(h, g, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        if (reset) HIP_CHECK(hipMemsetAsync(ctx->d_loss_acc, 0, sizeof(h), ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        check_fault(ctx);
-        if (error_sum) *error_sum = h[0];
-        if (correct_sum) { int cc; memcpy(&cc, &h[1], sizeof(int)); *correct_sum = cc; }
+        if (error_sum) *error_sum = err;
+        if (correct_sum) *correct_sum = cc;
     });
 }
 
@@ -1986,15 +2011,14 @@ int cn_layer_write_output_errors(cn_layer *layer, const float *host, size_t coun
         require_loaded(c);
         if (!layer->err) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_write_output_errors: layer has no outputErrors");
         if (count != (size_t)c->Next * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_layer_write_output_errors: count != T*PS*size");
-        float *tmp = nullptr;
-        HIP_CHECK(hipMalloc((void **)&tmp, count * sizeof(float)));
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
         HIP_CHECK(hipMemcpyAsync(tmp, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
         layer->mcc_pending = false;
         layer->err_in_delta = false;
         HIP_CHECK(hipMemsetAsync(layer->err, 0, (size_t)c->N * layer->Lp * sizeof(float), c->stream));
         launch_pad_f32(c->stream, tmp, c->Next, layer->size, layer->err, layer->Lp, layer->lstm ? layer->H : 0, layer->lstm ? layer->Hp : 0, c->PS, c->PSp);
         HIP_CHECK(hipStreamSynchronize(c->stream));
-        hipFree(tmp);
     });
 }
 
@@ -2006,7 +2030,6 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
         enter(c);
         finalize(c);
         join_side(c);
-        const size_t e = c->esz();
         const bool opbf = !c->f32;
         // flat parameter vectors
         if (which == CN_BUF_WEIGHTS || which == CN_BUF_WEIGHT_UPDATES || which == CN_BUF_WEIGHT_DELTAS || which == CN_BUF_ADAM_SECOND_MOMENTS) {
@@ -2032,8 +2055,8 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
             width = layer->H;
         }
         if (count != (size_t)N * width) throw cn_error(CN_ERR_SHAPE, "cn_layer_read: count != T*PS*width");
-        float *tmp = nullptr;
-        HIP_CHECK(hipMalloc((void **)&tmp, count * sizeof(float)));
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
         const int R = layer->dirs * 4 * layer->Hp, Hp = layer->Hp, H = layer->H;
         switch (which) {
         case CN_BUF_OUTPUTS:
@@ -2065,13 +2088,10 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
         case CN_BUF_LSTM_NI_DELTAS: case CN_BUF_LSTM_IG_DELTAS: case CN_BUF_LSTM_FG_DELTAS: case CN_BUF_LSTM_OG_DELTAS:
             launch_unpad(c->stream, opbf, layer->delta_op, R, dir * 4 * Hp + (which - CN_BUF_LSTM_NI_DELTAS), 4, N, H, tmp, H, 0, c->PS, c->PSp); break;
         default:
-            hipFree(tmp);
             throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: unknown buffer");
         }
-        (void)e;
         HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
-        hipFree(tmp);
     });
 }
 
@@ -2110,88 +2130,93 @@ int cn_ctx_weights_touched(cn_ctx *ctx)
     return CN_OK;
 }
 
+// ---- the optimizer's calls: momentum SGD and Adam share every sequence, the rule says which -------------------------
+static UpdateRule sgd_rule(float lr, float mom) { UpdateRule r; r.lr = lr; r.mom = mom; return r; }
+static UpdateRule adam_rule(float lr, float b1, float b2, float eps, int64_t step)
+{
+    UpdateRule r; r.adam = true; r.lr = lr; r.b1 = b1; r.b2 = b2; r.eps = eps; r.step = step;
+    return r;
+}
+// what every update call does first (fn: the ABI function, for the messages); on return the main stream is ordered behind all
+// gradient work
+static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
+{
+    if (r.adam) check_adam_args(fn, r);
+    bind_family(c, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
+    comm_check_fast(c);
+    if (r.adam) ensure_adam_v(c); else finalize(c);
+    join_side(c);
+}
+[[noreturn]] static void throw_rule_mismatch(const char *fn, bool adam)
+{
+    throw cn_error(CN_ERR_STATE, std::string(fn) + (adam ? ": learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied"
+                                                          : ": learning rate / momentum differ from what cn_ctx_arm_update armed and applied"));
+}
+// the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in, at rate lr
+static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, hipEvent_t done = nullptr)
+{
+    float *w = c->arena + off, *wu = w + c->total, *wd = w + 2 * c->total;
+    if (r.adam) launch_adam(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), done);
+    else        launch_sgd(c->stream, w, wu, wd, n, lr, r.mom, done);
+}
+
+// cn_ctx_arm_update / cn_ctx_arm_adam
+static void arm(cn_ctx *ctx, const UpdateRule &r, const char *fn)
+{
+    enter(ctx);
+    if (r.adam) check_adam_args(fn, r);
+    for (cn_layer *l : ctx->layers)
+        if (l->updated) throw cn_error(CN_ERR_STATE, std::string(fn) + ": the previous armed update has not been completed (" +
+                                       (r.adam ? "cn_adam_update_all" : "cn_sgd_update_all") + ")");
+    bind_family(ctx, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
+    if (r.adam) ensure_adam_v(ctx);
+    ctx->armed = true; ctx->arm = r;
+}
+
 int cn_ctx_arm_update(cn_ctx *ctx, float learning_rate, float momentum)
 {
     if (!ctx) { g_last_error = "cn_ctx_arm_update: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        for (cn_layer *l : ctx->layers)
-            if (l->updated) throw cn_error(CN_ERR_STATE, "cn_ctx_arm_update: the previous armed update has not been completed (cn_sgd_update_all)");
-        bind_family(ctx, cn_ctx::FAMILY_SGD, "cn_ctx_arm_update");
-        ctx->armed = true; ctx->arm_adam = false; ctx->arm_lr = learning_rate; ctx->arm_mom = momentum;
-    });
+    return guarded([&] { arm(ctx, sgd_rule(learning_rate, momentum), "cn_ctx_arm_update"); });
 }
 
 int cn_ctx_arm_adam(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
 {
     if (!ctx) { g_last_error = "cn_ctx_arm_adam: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        enter(ctx);
-        check_adam_args("cn_ctx_arm_adam", beta1, beta2, eps, step);
-        for (cn_layer *l : ctx->layers)
-            if (l->updated) throw cn_error(CN_ERR_STATE, "cn_ctx_arm_adam: the previous armed update has not been completed (cn_adam_update_all)");
-        bind_family(ctx, cn_ctx::FAMILY_ADAM, "cn_ctx_arm_adam");
-        ensure_adam_v(ctx);
-        ctx->armed = true; ctx->arm_adam = true;
-        ctx->arm_a.lr = learning_rate; ctx->arm_a.b1 = beta1; ctx->arm_a.b2 = beta2; ctx->arm_a.eps = eps; ctx->arm_a.step = step;
-        ctx->arm_mom = 0.f;
-    });
+    return guarded([&] { arm(ctx, adam_rule(learning_rate, beta1, beta2, eps, step), "cn_ctx_arm_adam"); });
+}
+
+// cn_sgd_update / cn_adam_update: r.lr is the layer's effective rate (the caller applies the layer's own)
+static void update_layer(cn_layer *layer, const UpdateRule &r, const char *fn)
+{
+    cn_ctx *c = layer->ctx;
+    enter(c);
+    if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": layer has no weights");
+    begin_update(c, r, fn);
+    if (layer->updated) {            // armed: this layer's step ran behind its gradient; nothing left but the wait above
+        UpdateRule applied = c->arm;
+        applied.lr = layer_lr(layer, c->arm);
+        if (!same_rule(r, applied)) throw_rule_mismatch(fn, r.adam);
+        layer->updated = false;
+        bool any = false;
+        for (cn_layer *o : c->layers) any = any || o->updated;
+        if (!any) c->armed = false;
+        return;
+    }
+    Timed tm(c, KC_OTHER);
+    launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr);
+    layer->dirty = true;
 }
 
 int cn_sgd_update(cn_layer *layer, float learning_rate, float momentum)
 {
     if (!layer) { g_last_error = "cn_sgd_update: layer is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        cn_ctx *c = layer->ctx;
-        enter(c);
-        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_sgd_update: layer has no weights");
-        bind_family(c, cn_ctx::FAMILY_SGD, "cn_sgd_update");
-        comm_check_fast(c);
-        finalize(c);
-        join_side(c);
-        if (layer->updated) {            // cn_ctx_arm_update: this layer's step ran behind its gradient; nothing left but the wait above
-            const float want = layer->own_lr >= 0.f ? layer->own_lr : c->arm_lr;
-            if (learning_rate != want || momentum != c->arm_mom)
-                throw cn_error(CN_ERR_STATE, "cn_sgd_update: learning rate / momentum differ from what cn_ctx_arm_update armed and applied");
-            layer->updated = false;
-            bool any = false;
-            for (cn_layer *o : c->layers) any = any || o->updated;
-            if (!any) c->armed = false;
-            return;
-        }
-        Timed tm(c, KC_OTHER);
-        launch_sgd(c->stream, layer->w, layer->wu, layer->wd, (size_t)layer->nw, learning_rate, momentum);
-        layer->dirty = true;
-    });
+    return guarded([&] { update_layer(layer, sgd_rule(learning_rate, momentum), "cn_sgd_update"); });
 }
 
 int cn_adam_update(cn_layer *layer, float learning_rate, float beta1, float beta2, float eps, int64_t step)
 {
     if (!layer) { g_last_error = "cn_adam_update: layer is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        cn_ctx *c = layer->ctx;
-        enter(c);
-        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_adam_update: layer has no weights");
-        check_adam_args("cn_adam_update", beta1, beta2, eps, step);
-        bind_family(c, cn_ctx::FAMILY_ADAM, "cn_adam_update");
-        comm_check_fast(c);
-        ensure_adam_v(c);
-        join_side(c);
-        cn_ctx::AdamArgs a; a.lr = learning_rate; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.step = step;
-        if (layer->updated) {            // cn_ctx_arm_adam: this layer's step ran behind its gradient; nothing left but the wait above
-            const float want = layer->own_lr >= 0.f ? layer->own_lr : c->arm_a.lr;
-            a.lr = c->arm_a.lr;
-            if (learning_rate != want || !a.same(c->arm_a, c->arm_a.lr))
-                throw cn_error(CN_ERR_STATE, "cn_adam_update: learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied");
-            layer->updated = false;
-            bool any = false;
-            for (cn_layer *o : c->layers) any = any || o->updated;
-            if (!any) c->armed = false;
-            return;
-        }
-        Timed tm(c, KC_OTHER);
-        launch_adam(c->stream, layer->w, layer->wu, layer->wd, c->adam_v + layer->woff, (size_t)layer->nw, adam_scalars(a, learning_rate));
-        layer->dirty = true;
-    });
+    return guarded([&] { update_layer(layer, adam_rule(learning_rate, beta1, beta2, eps, step), "cn_adam_update"); });
 }
 
 int cn_ctx_accumulate_updates(cn_ctx *ctx, int first)
@@ -2231,102 +2256,78 @@ int cn_layer_set_learning_rate(cn_layer *layer, float learning_rate)
     return CN_OK;
 }
 
-namespace {
 // cn_sgd_update_all / cn_adam_update_all: one sequence for both rules (r.lr: the call's learning rate)
-void update_all(cn_ctx *ctx, const UpdateRule &r)
+// (in an unnamed namespace inside extern "C", as it has been: hipcc gives such a function an unmangled GLOBAL symbol, so the
+// library's dynamic symbol table lists "update_all" -- nobody declares it; dropping it is a change of the export list of its own)
+namespace {
+void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
 {
-    const float learning_rate = r.lr, momentum = r.mom;
-    // the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in
-    auto launch_flat = [&](size_t off, size_t n, float lr, hipEvent_t done) {
-        float *w = ctx->arena + off, *wu = w + ctx->total, *wd = w + 2 * ctx->total;
-        if (r.adam) launch_adam(ctx->stream, w, wu, wd, ctx->adam_v + off, n, adam_scalars(r.a, lr), done);
-        else        launch_sgd(ctx->stream, w, wu, wd, n, lr, momentum, done);
-    };
-    {
-        // cn_ctx_arm_update: layers whose step ran behind their gradient are complete (the wait above orders this stream behind
-        // them); what follows handles the rest (none, normally)
-        bool any_updated = false;
-        for (cn_layer *l : ctx->layers) any_updated = any_updated || l->updated;
-        if (any_updated && r.adam && !r.a.same(ctx->arm_a, learning_rate))
-            throw cn_error(CN_ERR_STATE, "cn_adam_update_all: learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied");
-        if (any_updated && !r.adam && (learning_rate != ctx->arm_lr || momentum != ctx->arm_mom))
-            throw cn_error(CN_ERR_STATE, "cn_sgd_update_all: learning rate / momentum differ from what cn_ctx_arm_update armed and applied");
-        ctx->armed = false;
-        struct ClearUpdated { cn_ctx *c; ~ClearUpdated() { for (cn_layer *l : c->layers) l->updated = false; } } clear_updated{ctx};
-        Timed tm(ctx, KC_OTHER);
-        int ntrain = 0;
-        for (cn_layer *l : ctx->layers) if (l->trainable && !l->updated) ++ntrain;
-        if (ntrain == 0) return;
-        if (any_updated) {               // some layers were not reached by the armed pass (no backward call for them): one launch each
-            for (cn_layer *l : ctx->layers)
-                if (l->trainable && !l->updated) launch_layer_update(ctx->stream, l, 1, r, nullptr);
-            return;
-        }
-        // The operand copies of the new weights are rebuilt right away, all layers in ONE launch on this stream
-        // (pack_group_kernel): it costs about as much as the first layer's copy alone did, which was on the critical
-        // path anyway, and the other layers' copies no longer need a fork event, the side stream and a wait.
-        const bool group_off = opt().no_pack_group;
-        const bool grouped = ctx->overlap && !group_off && ntrain <= PACK_GROUP_MAX;
-        const bool attach = ctx->overlap && !grouped && ctx->attach_forks && !ctx->timing;
-        if (ctx->overlap && !grouped && !ctx->ev_sgd) HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_sgd, hipEventDisableTiming));
+    enter(ctx);
+    begin_update(ctx, r, fn);
+    // armed: layers whose step ran behind their gradient are complete (the wait above orders this stream behind them); what
+    // follows handles the rest (none, normally)
+    bool any_updated = false;
+    for (cn_layer *l : ctx->layers) any_updated = any_updated || l->updated;
+    if (any_updated && !same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r.adam);
+    ctx->armed = false;
+    struct ClearUpdated { cn_ctx *c; ~ClearUpdated() { for (cn_layer *l : c->layers) l->updated = false; } } clear_updated{ctx};
+    Timed tm(ctx, KC_OTHER);
+    int ntrain = 0;
+    for (cn_layer *l : ctx->layers) if (l->trainable && !l->updated) ++ntrain;
+    if (ntrain == 0) return;
+    if (any_updated) {               // some layers were not reached by the armed pass (no backward call for them): one launch each
+        for (cn_layer *l : ctx->layers)
+            if (l->trainable && !l->updated) launch_layer_update(ctx->stream, l, 1, r, nullptr);
+        return;
+    }
+    // The operand copies of the new weights are rebuilt right away, all layers in ONE launch on this stream
+    // (pack_group_kernel): it costs about as much as the first layer's copy alone did, which was on the critical
+    // path anyway, and the other layers' copies no longer need a fork event, the side stream and a wait.
+    const bool group_off = opt().no_pack_group;
+    const bool grouped = ctx->overlap && !group_off && ntrain <= PACK_GROUP_MAX;
+    // grouped: the update itself rides on the pack launch (pack_fetch): one kernel instead of two behind the last gradient
+    const bool fuse_off = opt().no_sgd_fuse;
+    const bool fused = grouped && !fuse_off;
+    const bool attach = ctx->overlap && !grouped && ctx->attach_forks && !ctx->timing;
+    if (ctx->overlap && !grouped && !ctx->ev_sgd) HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_sgd, hipEventDisableTiming));
+    if (!fused) {
         bool own_rates = false;
-        for (cn_layer *l : ctx->layers) own_rates = own_rates || (l->trainable && l->own_lr >= 0.f);
-        // grouped: the update itself rides on the pack launch (pack_fetch): one kernel instead of two behind the last gradient
-        const bool fuse_off = opt().no_sgd_fuse;
-        const bool fused = grouped && !fuse_off;
-        if (fused) {
-        } else if (!own_rates) {
-            launch_flat(0, ctx->total, learning_rate, attach ? ctx->ev_sgd : nullptr);
-        } else {
-            // a layer with a "learningRate" of its own (SteepestDescentOptimizer.cu:78-80): one launch per layer
-            cn_layer *last = nullptr;
-            for (cn_layer *l : ctx->layers) if (l->trainable) last = l;
+        cn_layer *last = nullptr;
+        for (cn_layer *l : ctx->layers)
+            if (l->trainable) { own_rates = own_rates || l->own_lr >= 0.f; last = l; }
+        if (!own_rates) launch_flat(ctx, r, 0, ctx->total, r.lr, attach ? ctx->ev_sgd : nullptr);
+        else            // a layer with a "learningRate" of its own: one launch per layer
             for (cn_layer *l : ctx->layers)
-                if (l->trainable)
-                    launch_flat(l->woff, (size_t)l->nw, l->own_lr >= 0.f ? l->own_lr : learning_rate, (attach && l == last) ? ctx->ev_sgd : nullptr);
+                if (l->trainable) launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), (attach && l == last) ? ctx->ev_sgd : nullptr);
+    }
+    for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
+    if (grouped) {
+        PackGroup grp{};
+        PackAdam ad{};
+        for (cn_layer *l : ctx->layers) {
+            if (!l->trainable) continue;
+            add_pack_item(grp, l);
+            if (fused) set_pack_update(grp, ad, 1, r, l);
+            l->dirty = false; l->pack_pending = false;
         }
-        for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
-        if (grouped) {
-            PackGroup grp{};
-            PackAdam ad{};
-            for (cn_layer *l : ctx->layers) {
-                if (!l->trainable) continue;
-                PackItem &it = grp.item[grp.n++];
-                it.lstm = l->lstm ? 1 : 0;
-                if (l->lstm) it.lg = lstm_geom(l); else it.fg = ff_geom(l);
-                it.bias = l->bias; it.w = l->w; it.Win = l->Win; it.WinT = l->WinT; it.Wrec = l->Wrec; it.WrecT = l->WrecT;
-                it.bias_p = l->bias_p; it.peep_p = l->peep_p;
-                if (fused) {
-                    it.update = 1; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd;
-                    it.lr = l->own_lr >= 0.f ? l->own_lr : learning_rate; it.mom = momentum;
-                    if (r.adam) {
-                        const AdamScalars a = adam_scalars(r.a, it.lr);
-                        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
-                        ad.v[grp.n - 1] = ctx->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
-                    }
-                }
-                l->dirty = false; l->pack_pending = false;
+        launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr);
+    } else if (ctx->overlap) {
+        // (more layers than one group launch takes: the first trainable layer's copy on this stream, its forward pass
+        // is next; the others on the side stream, each layer's forward pass waits for them in repack())
+        if (!attach) HIP_CHECK(hipEventRecord(ctx->ev_sgd, ctx->stream));
+        HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_sgd, 0));
+        bool first = true;
+        for (cn_layer *l : ctx->layers) {
+            if (!l->trainable) continue;
+            if (first) { first = false; continue; }
+            if (!l->ev_pack) HIP_CHECK(hipEventCreateWithFlags(&l->ev_pack, hipEventDisableTiming));
+            {
+                Timed tp(ctx, KC_OTHER, ctx->side);
+                launch_pack(ctx->side, l);
             }
-            launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr);
-        } else if (ctx->overlap) {
-            // (more layers than one group launch takes: the first trainable layer's copy on this stream, its forward pass
-            // is next; the others on the side stream, each layer's forward pass waits for them in repack())
-            if (!attach) HIP_CHECK(hipEventRecord(ctx->ev_sgd, ctx->stream));
-            HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_sgd, 0));
-            bool first = true;
-            for (cn_layer *l : ctx->layers) {
-                if (!l->trainable) continue;
-                if (first) { first = false; continue; }
-                if (!l->ev_pack) HIP_CHECK(hipEventCreateWithFlags(&l->ev_pack, hipEventDisableTiming));
-                {
-                    Timed tp(ctx, KC_OTHER, ctx->side);
-                    if (l->lstm) launch_lstm_pack(ctx->side, ctx->f32, lstm_geom(l), l->bias, l->w, l->Win, l->WinT, l->Wrec, l->WrecT, l->bias_p, l->peep_p);
-                    else         launch_ff_pack(ctx->side, ctx->f32, ff_geom(l), l->bias, l->w, l->Win, l->WinT, l->bias_p);
-                }
-                HIP_CHECK(hipEventRecord(l->ev_pack, ctx->side));
-                ctx->ev_pack_last = l->ev_pack;
-                l->dirty = false; l->pack_pending = true;
-            }
+            HIP_CHECK(hipEventRecord(l->ev_pack, ctx->side));
+            ctx->ev_pack_last = l->ev_pack;
+            l->dirty = false; l->pack_pending = true;
         }
     }
 }
@@ -2335,32 +2336,13 @@ void update_all(cn_ctx *ctx, const UpdateRule &r)
 int cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum)
 {
     if (!ctx) { g_last_error = "cn_sgd_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        enter(ctx);
-        bind_family(ctx, cn_ctx::FAMILY_SGD, "cn_sgd_update_all");
-        comm_check_fast(ctx);
-        finalize(ctx);
-        join_side(ctx);
-        UpdateRule r; r.lr = learning_rate; r.mom = momentum;
-        update_all(ctx, r);
-    });
+    return guarded([&] { update_all(ctx, sgd_rule(learning_rate, momentum), "cn_sgd_update_all"); });
 }
 
 int cn_adam_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
 {
     if (!ctx) { g_last_error = "cn_adam_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    return guarded([&] {
-        enter(ctx);
-        check_adam_args("cn_adam_update_all", beta1, beta2, eps, step);
-        bind_family(ctx, cn_ctx::FAMILY_ADAM, "cn_adam_update_all");
-        comm_check_fast(ctx);
-        ensure_adam_v(ctx);
-        join_side(ctx);
-        UpdateRule r; r.adam = true; r.lr = learning_rate;
-        r.a.lr = learning_rate; r.a.b1 = beta1; r.a.b2 = beta2; r.a.eps = eps; r.a.step = step;
-        r.mom = 0.f;
-        update_all(ctx, r);
-    });
+    return guarded([&] { update_all(ctx, adam_rule(learning_rate, beta1, beta2, eps, step), "cn_adam_update_all"); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2408,19 +2390,20 @@ int cn_dbg_gemm_nt(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
         enter(ctx);
         if (K % 8 || N % 32) throw cn_error(CN_ERR_SHAPE, "cn_dbg_gemm_nt: K must be a multiple of 8 and N of 32");
         const size_t e = ctx->esz();
-        float *dA, *dB, *dC, *dbias = nullptr; void *oA, *oB;
-        HIP_CHECK(hipMalloc((void **)&dA, (size_t)M * K * 4)); HIP_CHECK(hipMalloc((void **)&dB, (size_t)N * K * 4));
-        HIP_CHECK(hipMalloc((void **)&dC, (size_t)M * N * 4));
-        HIP_CHECK(hipMalloc(&oA, (size_t)M * K * e)); HIP_CHECK(hipMalloc(&oB, (size_t)N * K * e));
+        const Scratch sA((size_t)M * K * 4), sB((size_t)N * K * 4), sC((size_t)M * N * 4), sOA((size_t)M * K * e), sOB((size_t)N * K * e);
+        Scratch sBias, sC2;
+        float *dA = sA.get(), *dB = sB.get(), *dC = sC.get();
+        void *oA = sOA.get<void>(), *oB = sOB.get<void>();
         HIP_CHECK(hipMemcpyAsync(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(dB, B, (size_t)N * K * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (bias) { HIP_CHECK(hipMalloc((void **)&dbias, (size_t)N * 4)); HIP_CHECK(hipMemcpyAsync(dbias, bias, (size_t)N * 4, hipMemcpyHostToDevice, ctx->stream)); }
+        if (bias) { sBias.alloc((size_t)N * 4); HIP_CHECK(hipMemcpyAsync(sBias.get(), bias, (size_t)N * 4, hipMemcpyHostToDevice, ctx->stream)); }
+        float *dbias = sBias.get();
         launch_pad_convert(ctx->stream, ctx->f32, dA, M, K, oA, K);
         launch_pad_convert(ctx->stream, ctx->f32, dB, N, K, oB, K);
         // act | 0x100: both outputs (fp32 and operand-type copy), the COPY is returned; act | 0x200: the copy alone
         const bool both = act & 0x100, copy_only = act & 0x200;
-        void *dC2 = nullptr;
-        if (both || copy_only) HIP_CHECK(hipMalloc(&dC2, (size_t)M * N * e));
+        if (both || copy_only) sC2.alloc((size_t)M * N * e);
+        void *dC2 = sC2.get<void>();
         GemmNT g{}; g.A = oA; g.lda = K; g.B = oB; g.ldb = K; g.C = copy_only ? nullptr : dC; g.ldc = N; g.C2 = dC2; g.ldc2 = N;
         g.bias = dbias; g.act = act & 0xff; g.M = M; g.N = N; g.K = K;
         launch_gemm_nt(ctx->stream, ctx->prec, g);
@@ -2434,7 +2417,6 @@ int cn_dbg_gemm_nt(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
             HIP_CHECK(hipMemcpyAsync(C, dC2 ? dC2 : dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIP_CHECK(hipStreamSynchronize(ctx->stream));
         }
-        hipFree(dA); hipFree(dB); hipFree(dC); hipFree(oA); hipFree(oB); hipFree(dbias); hipFree(dC2);
     });
 }
 
@@ -2465,10 +2447,9 @@ int cn_dbg_gemm_tn(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
         enter(ctx);
         if (M % 32 || N % 32) throw cn_error(CN_ERR_SHAPE, "cn_dbg_gemm_tn: M and N must be multiples of 32");
         const size_t e = ctx->esz();
-        float *dA, *dB, *dC; void *oA, *oB;
-        HIP_CHECK(hipMalloc((void **)&dA, (size_t)M * K * 4)); HIP_CHECK(hipMalloc((void **)&dB, (size_t)N * K * 4));
-        HIP_CHECK(hipMalloc((void **)&dC, (size_t)M * N * 4));
-        HIP_CHECK(hipMalloc(&oA, (size_t)M * K * e)); HIP_CHECK(hipMalloc(&oB, (size_t)N * K * e));
+        const Scratch sA((size_t)M * K * 4), sB((size_t)N * K * 4), sC((size_t)M * N * 4), sOA((size_t)M * K * e), sOB((size_t)N * K * e);
+        float *dA = sA.get(), *dB = sB.get(), *dC = sC.get();
+        void *oA = sOA.get<void>(), *oB = sOB.get<void>();
         HIP_CHECK(hipMemcpyAsync(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(dB, B, (size_t)N * K * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(hipMemsetAsync(dC, 0, (size_t)M * N * 4, ctx->stream));
@@ -2479,7 +2460,6 @@ int cn_dbg_gemm_tn(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        hipFree(dA); hipFree(dB); hipFree(dC); hipFree(oA); hipFree(oB);
     });
 }
 

@@ -1006,6 +1006,64 @@ def test_armed_update_equals_update_after_the_backward_pass(pkg, precision):
     assert moved > 1e-3
 
 
+UPDATE_FORMS = {"default": {}, "no_sgd_fuse": {"no_sgd_fuse": 1}, "no_pack_group": {"no_pack_group": 1}, "no_overlap": {"overlap": 0}}
+
+
+@pytest.mark.parametrize("own_lr", [False, True])
+@pytest.mark.parametrize("rule", ["sgd", "adam"])
+def test_update_forms_agree_and_operand_copies_follow(pkg, rule, own_lr):
+    """cn_sgd_update_all / cn_adam_update_all apply the step in one of four forms: fused into the grouped operand-copy launch
+    (the default), a flat launch over the arena in front of the grouped copies (no_sgd_fuse), a flat launch, the first layer's
+    copies left to its forward pass and the other layers' rebuilt on the side stream (no_pack_group), a flat launch and every
+    copy left to the forward pass (overlap off).  own_lr: one layer has a learningRate of its own, so the flat form is one launch
+    per layer.  5 -> blstm 12 -> softmax 4, PS 6 padded to 8, three steps over two fractions, CN_PREC_F32.
+    (a) In every form the operand copies follow the weights: a forward pass behind the last update gives outputs bit-equal to
+    those of a fresh network built from the weights read back.
+    (b) Every form ends in the default form's weights, within the bound test_armed_update_equals_update_after_the_backward_pass
+    holds the armed step to against the plain one."""
+    rng = np.random.RandomState(92)
+    P, C, PS = 5, 4, 6
+    layers = net_desc(P, [("blstm", 12)], C)
+    if own_lr:
+        layers[1]["learningRate"] = 3e-3
+    weights = random_weights(layers, rng, 0.4)
+    fracs = []
+    for lens in ([9, 7, 4, 6, 9], [5, 8, 3]):
+        xs, ts = random_sequences(rng, lens, P, C=C)
+        fracs.append(pkg.make_fraction(xs, ts, PS))
+
+    def step(net, k):
+        if rule == "adam":
+            net.update_weights_adam(1e-2, step=k + 1)
+        else:
+            net.update_weights_fused(1e-2, 0.9)
+
+    res = {}
+    for form, options in UPDATE_FORMS.items():
+        with pkg.NeuralNetwork(layers, weights, PS, 9, precision=pkg.PREC_F32) as net:
+            for name, value in options.items():
+                net.set_option(name, value)
+            for k in range(3):
+                net.load_sequences(fracs[k % 2]); net.compute_forward_pass(); net.calculate_error()
+                net.compute_backward_pass()
+                step(net, k)
+            net.load_sequences(fracs[1]); net.compute_forward_pass()
+            y = net.outputs()
+            trained = net.export_weights()
+            res[form] = {l.name: l.weights() for l in net.trainable_layers()}
+        with pkg.NeuralNetwork(layers, trained, PS, 9, precision=pkg.PREC_F32) as fresh:
+            fresh.load_sequences(fracs[1]); fresh.compute_forward_pass()
+            assert np.array_equal(fresh.outputs(), y), form
+    for form in UPDATE_FORMS:
+        for name, w in res["default"].items():
+            d = np.abs(res[form][name] - w).max()
+            print("update form %s/%s own_lr=%d %s: max |w - w_default| = %g" % (rule, form, own_lr, name, d))
+            assert d < 2e-6 * max(1.0, np.abs(w).max()), (form, name)
+    moved = max(np.abs(res["default"][l["name"]] - np.concatenate([np.ravel(weights[l["name"]][k]) for k in ("input", "bias", "internal")])).max()
+                for l in layers if l["name"] in weights)
+    assert moved > 1e-3
+
+
 def test_armed_update_state_errors(pkg):
     """A second backward pass before the armed step was completed, and a completing call with other values, are refused."""
     rng = np.random.RandomState(91)
