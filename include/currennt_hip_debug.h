@@ -21,6 +21,42 @@ int cn_dbg_gemm_nt(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
                    const float *bias, int act);
 /* C[M][N] = A[K][M]^T * B[K][N];  M % 32 == 0, N % 32 == 0 */
 int cn_dbg_gemm_tn(cn_ctx *ctx, const float *A, const float *B, float *C, int M, int N, int K);
+/* The weight-gradient products as a layer launches them (launch_gemm_tn_group: the three products of an LSTM layer, a dense
+ * layer's one): up to three products side by side, each on VIEWS into host-provided fp32 parents.
+ *   A parent [rows_a][lda], view rows a_row .. a_row + K - 1, columns a_col .. a_col + M - 1
+ *   B parent [rows_b][ldb], view rows b_row .. b_row + K - 1, columns b_col .. b_col + N - 1
+ *   C [M][ldc], ldc >= N, uploaded AS GIVEN (pre-zeroed where the sums go; the pitch columns may hold sentinels) and returned
+ * The parents are converted to the context's operand type whole (items that name the same host parent share one device copy),
+ * the views are pointer arithmetic on the copies.  An item with M, N or K == 0 is skipped.  M, N multiples of 32; every view
+ * inside its parent; pitches and column offsets multiples of 16 bytes in the operand type (4 floats, 8 bf16). */
+typedef struct cn_dbg_tn_item {
+    const float *A; int rows_a, lda;
+    const float *B; int rows_b, ldb;
+    int a_row, a_col, b_row, b_col;
+    int M, N, K;
+    float *C; int ldc;
+} cn_dbg_tn_item;
+/* dst[r][c] (+)= part[0][r][c] + part[1][r][c] + ... in that order, r < rows, c < cols <= ld; host dst [rows][ld], host part
+ * [nparts][stride] (partials share dst's pitch, stride >= (rows - 1) * ld + cols); clear: the partials read are zeroed. */
+typedef struct cn_dbg_fold_item {
+    float *dst; float *part; long long stride;
+    int nparts, rows, cols, ld, accumulate, clear;
+} cn_dbg_fold_item;
+/* what the hook fills a deterministic product's workspace with before the launch */
+#define CN_DBG_WS_SENTINEL (-1234.5f)
+#define CN_DBG_MAX_SPLITS 8
+/* n <= 3 items, cu_budget as launch_gemm_tn_group's (0 = the chip).  Context option "deterministic" on: every item gets a
+ * workspace of CN_DBG_MAX_SPLITS * M * ldc floats filled with CN_DBG_WS_SENTINEL.
+ * flags & 1 (deterministic contexts only): the deferred form -- no fold is launched, splits_out[i] (required) = the splits
+ * item i was cut into (0: skipped), and item i's C is [CN_DBG_MAX_SPLITS][M][ldc]: the whole workspace comes back, nothing is
+ * uploaded from it.
+ * extra (nullable): one more fold that rides on the call's last launch; its dst is returned, and its part when clear is set.
+ * Everything is validated before anything is launched (CN_ERR_SHAPE / CN_ERR_BAD_ARG).  [sync] */
+int cn_dbg_gemm_tn_group(cn_ctx *ctx, const cn_dbg_tn_item *items, int n, int cu_budget, int flags, int *splits_out,
+                         const cn_dbg_fold_item *extra);
+/* launch_fold on host-provided partials; n may exceed the items of one launch.  Every dst is returned, and every part whose
+ * item has clear set.  [sync] */
+int cn_dbg_fold(cn_ctx *ctx, const cn_dbg_fold_item *items, int n);
 /* The row map of the fraction that is loaded (no counterpart in the reference, which multiplies every frame of a fraction:
  * LstmLayer.cu:771-786): out[0] frames whose rows the N-wide products compute, out[1] dummy frames whose rows they fill with
  * bias / 0 instead, out[2] T x (padded) parallel sequences.  [sync] */

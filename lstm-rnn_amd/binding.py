@@ -38,7 +38,7 @@ EXPORTS = [
     "cn_layer_recurrent_kernel",
     "cn_comm_unique_id", "cn_comm_init", "cn_comm_destroy", "cn_comm_info", "cn_comm_backend", "cn_allreduce_grads", "cn_loss_read_global",
     # include/currennt_hip_debug.h
-    "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits",
+    "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits", "cn_dbg_gemm_tn_group", "cn_dbg_fold",
     # include/currennt_hip.h, section Adam
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -57,6 +57,25 @@ class Fraction(C.Structure):
                 ("input_pattern_size", C.c_int), ("output_pattern_size", C.c_int),
                 ("pat_types", C.c_void_p), ("inputs", C.c_void_p),
                 ("target_classes", C.c_void_p), ("targets", C.c_void_p)]
+
+
+# include/currennt_hip_debug.h: cn_dbg_tn_item, cn_dbg_fold_item (every pointer a c_void_p: an int would be cut to 32 bits)
+DBG_WS_SENTINEL = -1234.5
+DBG_MAX_SPLITS = 8
+
+
+class DbgTnItem(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("rows_a", C.c_int), ("lda", C.c_int),
+                ("B", C.c_void_p), ("rows_b", C.c_int), ("ldb", C.c_int),
+                ("a_row", C.c_int), ("a_col", C.c_int), ("b_row", C.c_int), ("b_col", C.c_int),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("C", C.c_void_p), ("ldc", C.c_int)]
+
+
+class DbgFoldItem(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("part", C.c_void_p), ("stride", C.c_longlong),
+                ("nparts", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int),
+                ("accumulate", C.c_int), ("clear", C.c_int)]
 
 
 def lib_path():
@@ -151,6 +170,8 @@ def load_library():
     L.cn_loss_read_global.argtypes = [vp, C.POINTER(cf), C.POINTER(C.c_int64), ci]
     L.cn_dbg_gemm_nt.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci]
     L.cn_dbg_gemm_tn.argtypes = [vp, vp, vp, vp, ci, ci, ci]
+    L.cn_dbg_gemm_tn_group.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    L.cn_dbg_fold.argtypes = [vp, vp, ci]
     L.cn_dbg_row_map_counts.argtypes = [vp, vp]
     L.cn_dbg_prefetch_hits.argtypes = [vp, C.POINTER(C.c_int)]
     _LIB = L

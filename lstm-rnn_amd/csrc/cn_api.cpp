@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -2459,6 +2460,149 @@ int cn_dbg_gemm_tn(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
         launch_gemm_tn(ctx->stream, ctx->prec, g);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+static_assert(CN_DBG_MAX_SPLITS == DET_MAX_SPLITS, "currennt_hip_debug.h states the workspace depth of cn_internal.h");
+
+// a host fold item of the test hooks on the device: checked, uploaded, and read back behind the launch
+struct DbgFold {
+    std::deque<Scratch> mem;
+    FoldItem f{};
+    const cn_dbg_fold_item *h = nullptr;
+    size_t dst_n = 0, part_n = 0;
+    static void validate(const cn_dbg_fold_item &h, const char *who)
+    {
+        const std::string w(who);
+        if (h.nparts < 1 || h.rows < 0 || h.cols < 0 || h.ld < 0) throw cn_error(CN_ERR_BAD_ARG, w + ": fold item with nparts < 1 or a negative size");
+        if (h.cols > h.ld) throw cn_error(CN_ERR_SHAPE, w + ": fold item with cols > ld");
+        if (h.rows && h.cols && h.stride < (long long)(h.rows - 1) * h.ld + h.cols) throw cn_error(CN_ERR_SHAPE, w + ": fold item whose partials overlap (stride)");
+        if (h.rows && h.cols && (!h.dst || !h.part)) throw cn_error(CN_ERR_BAD_ARG, w + ": fold item with a NULL dst or part");
+    }
+    void upload(cn_ctx *ctx, const cn_dbg_fold_item &item)
+    {
+        h = &item;
+        dst_n = (size_t)item.rows * item.ld;
+        part_n = (item.rows && item.cols) ? (size_t)item.nparts * (size_t)item.stride : 0;
+        float *dst = (float *)mem.emplace_back(std::max<size_t>(dst_n * 4, 16)).get();
+        float *part = (float *)mem.emplace_back(std::max<size_t>(part_n * 4, 16)).get();
+        if (dst_n) HIP_CHECK(hipMemcpyAsync(dst, item.dst, dst_n * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (part_n) HIP_CHECK(hipMemcpyAsync(part, item.part, part_n * 4, hipMemcpyHostToDevice, ctx->stream));
+        f = FoldItem{dst, part, (long)item.stride, item.nparts, item.rows, item.cols, item.ld, item.accumulate, item.clear};
+    }
+    void download(cn_ctx *ctx) const
+    {
+        if (dst_n) HIP_CHECK(hipMemcpyAsync(h->dst, f.dst, dst_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (part_n && h->clear) HIP_CHECK(hipMemcpyAsync(h->part, f.part, part_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int cn_dbg_gemm_tn_group(cn_ctx *ctx, const cn_dbg_tn_item *items, int n, int cu_budget, int flags, int *splits_out,
+                         const cn_dbg_fold_item *extra)
+{
+    if (!ctx || (n > 0 && !items)) { g_last_error = "cn_dbg_gemm_tn_group: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        const char *who = "cn_dbg_gemm_tn_group";
+        const std::string w(who);
+        const bool defer = flags & 1;
+        const int e = (int)ctx->esz(), al = 16 / e;
+        if (n < 0 || n > 3) throw cn_error(CN_ERR_BAD_ARG, w + ": 0 to 3 items");
+        if (cu_budget < 0 || (flags & ~1)) throw cn_error(CN_ERR_BAD_ARG, w + ": negative cu_budget or unknown flag");
+        if (defer && !ctx->det) throw cn_error(CN_ERR_BAD_ARG, w + ": the deferred form needs the deterministic option");
+        if (defer && !splits_out) throw cn_error(CN_ERR_BAD_ARG, w + ": the deferred form needs splits_out");
+        auto live = [](const cn_dbg_tn_item &it) { return it.M > 0 && it.N > 0 && it.K > 0; };
+        for (int i = 0; i < n; ++i) {
+            const cn_dbg_tn_item &it = items[i];
+            if (it.M < 0 || it.N < 0 || it.K < 0) throw cn_error(CN_ERR_BAD_ARG, w + ": negative M, N or K");
+            if (it.M % 32 || it.N % 32) throw cn_error(CN_ERR_SHAPE, w + ": M and N must be multiples of 32");
+            if (!live(it)) continue;
+            if (!it.A || !it.B || !it.C) throw cn_error(CN_ERR_BAD_ARG, w + ": NULL A, B or C");
+            if (it.ldc < it.N) throw cn_error(CN_ERR_SHAPE, w + ": ldc < N");
+            if (it.a_row < 0 || it.a_col < 0 || it.b_row < 0 || it.b_col < 0 || it.rows_a < 0 || it.rows_b < 0 ||
+                (long)it.a_row + it.K > it.rows_a || (long)it.a_col + it.M > it.lda ||
+                (long)it.b_row + it.K > it.rows_b || (long)it.b_col + it.N > it.ldb)
+                throw cn_error(CN_ERR_SHAPE, w + ": a view leaves its parent");
+            if (it.lda % al || it.ldb % al || it.a_col % al || it.b_col % al)
+                throw cn_error(CN_ERR_SHAPE, w + ": pitches and column offsets must keep the views 16-byte aligned in the operand type");
+        }
+        if (extra) DbgFold::validate(*extra, who);
+
+        // one device copy per distinct host parent, converted whole
+        std::deque<Scratch> mem;
+        struct Parent { const float *host; int rows, ld; char *op; };
+        std::vector<Parent> parents;
+        auto parent = [&](const float *host, int rows, int ld) -> char * {
+            for (const Parent &p : parents) if (p.host == host && p.rows == rows && p.ld == ld) return p.op;
+            const size_t count = (size_t)rows * ld;
+            const Scratch stage(count * 4);
+            char *op = mem.emplace_back(count * e).get<char>();
+            HIP_CHECK(hipMemcpyAsync(stage.get(), host, count * 4, hipMemcpyHostToDevice, ctx->stream));
+            launch_pad_convert(ctx->stream, ctx->f32, stage.get(), rows, ld, op, ld);
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));        // (the staging copy goes with this scope)
+            parents.push_back(Parent{host, rows, ld, op});
+            return op;
+        };
+        GemmTN gs[3]; int used[3] = {0, 0, 0};
+        float *dC[3] = {nullptr, nullptr, nullptr}, *dWs[3] = {nullptr, nullptr, nullptr};
+        for (int i = 0; i < n; ++i) {
+            const cn_dbg_tn_item &it = items[i];
+            GemmTN g{};
+            g.M = it.M; g.N = it.N; g.K = it.K; g.lda = it.lda; g.ldb = it.ldb; g.ldc = it.ldc;
+            if (live(it)) {
+                g.A = parent(it.A, it.rows_a, it.lda) + ((size_t)it.a_row * it.lda + it.a_col) * e;
+                g.B = parent(it.B, it.rows_b, it.ldb) + ((size_t)it.b_row * it.ldb + it.b_col) * e;
+                const size_t cn = (size_t)it.M * it.ldc;
+                dC[i] = mem.emplace_back(cn * 4).get();
+                if (!defer) HIP_CHECK(hipMemcpyAsync(dC[i], it.C, cn * 4, hipMemcpyHostToDevice, ctx->stream));
+                g.C = dC[i];
+                if (ctx->det) {
+                    dWs[i] = mem.emplace_back((size_t)DET_MAX_SPLITS * cn * 4).get();
+                    const float sentinel = CN_DBG_WS_SENTINEL; int bits; memcpy(&bits, &sentinel, 4);
+                    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dWs[i], bits, (size_t)DET_MAX_SPLITS * cn, ctx->stream));
+                    g.ws = dWs[i]; g.ws_splits = DET_MAX_SPLITS; g.ws_used = defer ? &used[i] : nullptr;
+                }
+            }
+            gs[i] = g;
+        }
+        DbgFold xf;
+        if (extra) xf.upload(ctx, *extra);
+        launch_gemm_tn_group(ctx->stream, ctx->prec, gs, n, cu_budget, extra ? &xf.f : nullptr);
+        HIP_CHECK(hipGetLastError());
+        for (int i = 0; i < n; ++i) {
+            if (splits_out) splits_out[i] = used[i];
+            if (!dC[i]) continue;
+            const size_t cn = (size_t)items[i].M * items[i].ldc;
+            if (defer) HIP_CHECK(hipMemcpyAsync(items[i].C, dWs[i], (size_t)DET_MAX_SPLITS * cn * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else HIP_CHECK(hipMemcpyAsync(items[i].C, dC[i], cn * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (extra) xf.download(ctx);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int cn_dbg_fold(cn_ctx *ctx, const cn_dbg_fold_item *items, int n)
+{
+    if (!ctx || (n > 0 && !items)) { g_last_error = "cn_dbg_fold: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        if (n < 0) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_fold: negative item count");
+        for (int i = 0; i < n; ++i) DbgFold::validate(items[i], "cn_dbg_fold");
+        std::deque<DbgFold> dev;
+        std::vector<FoldItem> fs;
+        for (int i = 0; i < n; ++i) { dev.emplace_back().upload(ctx, items[i]); fs.push_back(dev.back().f); }
+        launch_fold(ctx->stream, fs.data(), n);
+        HIP_CHECK(hipGetLastError());
+        for (const DbgFold &d : dev) d.download(ctx);
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
 }
