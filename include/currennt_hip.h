@@ -74,7 +74,11 @@ typedef enum cn_layer_kind {
     CN_LAYER_SSE_MASK,                    /* "wf"                         SseMaskPostOutputLayer.cu        */
     CN_LAYER_CE,                          /* "ce"                         CePostOutputLayer.cu             */
     CN_LAYER_RMSE,                        /* "rmse"                       RmsePostOutputLayer.cu           */
-    CN_LAYER_BINARY_CLASSIFICATION        /* "binary_classification"      BinaryClassificationLayer.cu     */
+    CN_LAYER_BINARY_CLASSIFICATION,       /* "binary_classification"      BinaryClassificationLayer.cu     */
+    /* Connectionist Temporal Classification (Graves et al. 2006; no counterpart in the reference): behind a softmax layer of the
+     * same size (>= 2) whose LAST unit is the blank.  It reads nothing from cn_fraction.target_classes / targets (and
+     * output_pattern_size is not checked against it); its targets are label sequences, cn_layer_set_label_sequences below. */
+    CN_LAYER_CTC                          /* "ctc"                        csrc/cn_ctc.hip                  */
 } cn_layer_kind;
 
 /* which device vector cn_layer_read / cn_layer_device_ptr addresses */
@@ -215,9 +219,22 @@ int  cn_fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, c
 int  cn_layer_forward(cn_layer *layer);
 int  cn_layer_backward(cn_layer *layer);
 
+/* The label sequences of the fraction loaded last, for a CN_LAYER_CTC layer: `labels` holds the sequences of slots
+ * 0 .. num_sequences-1 one behind the other, label_lengths[s] labels for slot s, every label in [0, size - 2] (size - 1 is the
+ * blank).  num_sequences must equal the loaded fraction's.  Both host arrays are copied before the call returns; the upload is
+ * ordered on the context's stream.  The labels belong to that fraction: every cn_fraction_load* (a prefetch hit included)
+ * invalidates them, and cn_loss_eval / cn_loss_accumulate / cn_layer_backward of a ctc layer without labels fail with
+ * CN_ERR_STATE.  A label outside the range, a negative length or another num_sequences: CN_ERR_BAD_ARG.  A sequence longer than
+ * the layer's cap -- min(max_seq_length, 512) labels, or the context option "ctc_max_labels" as it stood when the layer was
+ * created (it sizes the workspace) -- : CN_ERR_SHAPE.
+ * The error of a fraction is the sum of -log p(labels | inputs) over its sequences.  A sequence without an alignment (length 0, or
+ * more labels + adjacent repeats than frames) contributes 0 and gets zero output errors.                          [async] */
+int  cn_layer_set_label_sequences(cn_layer *ctc, const int *labels, const int *label_lengths, int num_sequences);
+
 /* PostOutputLayer::calculateError() and, for multiclass_classification,
  * countCorrectClassifications() (MulticlassClassificationLayer.cu:159-177,194-213).
- * `correct` may be NULL; it is set to -1 for layers without a class count.        [sync] */
+ * `correct` may be NULL; it is set to -1 for layers without a class count.  For a ctc layer it is the number of sequences
+ * that contributed to the error (those with an alignment), and so is the count cn_loss_accumulate adds.        [sync] */
 int  cn_loss_eval(cn_layer *post_output, float *error, int *correct);
 
 /* Asynchronous form for the training loop: add this fraction's error / #correct to device-side

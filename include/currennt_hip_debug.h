@@ -65,6 +65,14 @@ int cn_dbg_row_map_counts(cn_ctx *ctx, int out[3]);
  * buffers. */
 int cn_dbg_prefetch_hits(cn_ctx *ctx, int *hits);
 
+/* The launches of a CN_LAYER_CTC layer (csrc/cn_ctc.hip: the sweeps, then the output errors) on posteriors of the caller's choice.
+ * Host arrays in the reference layout: y [T * PS][C] posteriors (blank = C - 1), pat [T * PS] pattern types, the labels as for
+ * cn_layer_set_label_sequences with one length per slot (PS of them); out: loss_out [PS] = -log p per slot (0 for a sequence
+ * without an alignment), err_out [T * PS][C] = dL/dy.  The device buffer of the output errors starts as NaNs, and the hook fails
+ * with CN_ERR_STATE when a pad slot or pad column of it is not exactly 0.  [sync] */
+int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
+               float *loss_out, float *err_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ LAYER_KINDS = {
     "feedforward_tanh": 3, "feedforward_logistic": 4, "feedforward_identity": 5,
     "softmax": 6, "sse": 7, "multiclass_classification": 8,
     "weightedsse": 9, "wf": 10, "ce": 11, "rmse": 12, "binary_classification": 13,
+    "ctc": 14,                # csrc/cn_ctc.hip; no counterpart in the reference
 }
 
 # cn_buffer
@@ -39,7 +40,9 @@ EXPORTS = [
     "cn_comm_unique_id", "cn_comm_init", "cn_comm_destroy", "cn_comm_info", "cn_comm_backend", "cn_allreduce_grads", "cn_loss_read_global",
     # include/currennt_hip_debug.h
     "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits", "cn_dbg_gemm_tn_group", "cn_dbg_fold",
-    # include/currennt_hip.h, section Adam
+    # the CTC post output layer: include/currennt_hip.h and its kernel-level hook in include/currennt_hip_debug.h
+    "cn_layer_set_label_sequences", "cn_dbg_ctc",
+    # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
 
@@ -174,6 +177,8 @@ def load_library():
     L.cn_dbg_fold.argtypes = [vp, vp, ci]
     L.cn_dbg_row_map_counts.argtypes = [vp, vp]
     L.cn_dbg_prefetch_hits.argtypes = [vp, C.POINTER(C.c_int)]
+    L.cn_layer_set_label_sequences.argtypes = [vp, vp, vp, ci]
+    L.cn_dbg_ctc.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
     _LIB = L
     return L
 

@@ -253,6 +253,20 @@ struct cn_layer {
     float *gpart = nullptr; int gpart_slots = 0;   // LSTM: per-workgroup bias / peephole sums (LstmRec::gpart)
     float *det_colpart = nullptr;         // dense layers: per-workgroup column sums (det_colsum_part_floats)
 
+    // CTC post output layer (cn_ctc.hip): label sequences of the fraction loaded last, the sweeps' workspace
+    int ctc_cap = 0;                      // labels per sequence the buffers were sized for (option ctc_max_labels at creation)
+    int *ctc_labels = nullptr;            // [labels | next | first], ctc_stride ints each (the fraction's label total), then laboff [PSp + 1]
+    size_t ctc_stride = 1;
+    bool ctc_labels_valid = false;        // set by cn_layer_set_label_sequences, cleared by every cn_fraction_load*
+    bool ctc_swept = false;               // the sweeps of the current forward pass have been enqueued (error and output errors share them)
+    int ctc_maxS = 1;                     // 2 * (longest label sequence of the fraction) + 1
+    int2 *ctc_alpha = nullptr, *ctc_beta = nullptr; int ctc_Sp = 0;
+    int *ctc_info = nullptr;
+    float *ctc_rowstat = nullptr;         // [PSp][2]: {-log p, 1} or {0, 0} per slot
+    // two pinned images of ctc_labels, used in turn (the host packs fraction k + 1 while the upload of fraction k may still be
+    // queued); an image's last upload has read it when its event completes
+    int *ctc_hbuf[2] = {nullptr, nullptr}; hipEvent_t ctc_ev[2] = {nullptr, nullptr}; unsigned ctc_uploads = 0;
+
     std::vector<void *> owned;            // device allocations to free
 
     size_t maxN() const { return (size_t)PSp * maxT; }
@@ -980,6 +994,7 @@ void ff_forward(cn_layer *l)
         launch_gemm_nt(c->stream, c->prec, g);
     }
     if (softmax) {
+        for (cn_layer *p : c->layers) if (p->prev == l) p->ctc_swept = false;      // (a ctc layer's sweeps belonged to the old posteriors)
         flush_loss(c);                         // (the row statistics are about to be overwritten)
         Timed tm(c, KC_OTHER);
         const bool stat = c->d_rowstat != nullptr;
@@ -1179,6 +1194,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
             for (void *p : l->owned) hipFree(p);
             if (l->ev_fork) { hipEventDestroy(l->ev_fork); hipEventDestroy(l->ev_join); }
             if (l->ev_pack) hipEventDestroy(l->ev_pack);
+            for (int b = 0; b < 2; ++b) if (l->ctc_hbuf[b]) { hipHostFree(l->ctc_hbuf[b]); hipEventDestroy(l->ctc_ev[b]); }
             delete l;
         }
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
@@ -1566,6 +1582,25 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
                 if (!ctx->d_rowstat) HIP_CHECK(hipMalloc((void **)&ctx->d_rowstat, maxN * 2 * sizeof(float)));
             }
             break; }
+        case CN_LAYER_CTC: {
+            if (preceding->kind != CN_LAYER_SOFTMAX) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: a ctc layer needs a softmax layer as its preceding layer");
+            if (size != preceding->size) throw cn_error(CN_ERR_SHAPE, "Size mismatch: " + std::to_string(size) + " vs. " + std::to_string(preceding->size));
+            if (size < 2) throw cn_error(CN_ERR_SHAPE, "The ctc post output layer needs at least one label and the blank (output layer size >= 2)");
+            l->post = true; l->Lp = preceding->Lp;
+            const long cap = opt().ctc_max_labels > 0 ? opt().ctc_max_labels : std::min(l->maxT, 512);
+            if (!ctc_shape_fits((int)std::min<long>(cap, CTC_MAX_STATES), l->Lp) || cap > CTC_MAX_STATES)
+                throw cn_error(CN_ERR_SHAPE, "cn_layer_create: a ctc layer with " + std::to_string(cap) + " labels per sequence (option ctc_max_labels) and " +
+                                             std::to_string(size) + " units does not fit a workgroup (2 * labels + 1 <= " + std::to_string(CTC_MAX_STATES) +
+                                             " states, 2 * (2 * labels + 1) + padded units <= 15360 floats of LDS)");
+            l->ctc_cap = (int)cap;
+            const size_t nlab = (size_t)l->ctc_cap * l->PS;
+            l->ctc_labels = (int *)dalloc(l, (3 * nlab + l->PSp + 1) * sizeof(int));
+            l->ctc_Sp = round_up(2 * l->ctc_cap + 1, 64);
+            l->ctc_alpha = (int2 *)dalloc(l, (size_t)l->PSp * l->maxT * l->ctc_Sp * sizeof(int2));
+            l->ctc_beta = (int2 *)dalloc(l, (size_t)l->PSp * l->maxT * l->ctc_Sp * sizeof(int2));
+            l->ctc_info = (int *)dalloc(l, (size_t)l->PSp * 2 * sizeof(int));
+            l->ctc_rowstat = (float *)dalloc(l, (size_t)l->PSp * 2 * sizeof(float));
+            break; }
         default:
             throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: unknown layer kind");
         }
@@ -1591,6 +1626,7 @@ int cn_layer_destroy(cn_layer *layer)
         for (void *p : layer->owned) hipFree(p);
         if (layer->ev_fork) { hipEventDestroy(layer->ev_fork); hipEventDestroy(layer->ev_join); }
         if (layer->ev_pack) hipEventDestroy(layer->ev_pack);
+        for (int b = 0; b < 2; ++b) if (layer->ctc_hbuf[b]) { hipHostFree(layer->ctc_hbuf[b]); hipEventDestroy(layer->ctc_ev[b]); }
         if (c->rowstat_of == layer) c->rowstat_of = nullptr;
         for (size_t i = 0; i < c->layers.size(); ++i)
             if (c->layers[i] == layer) { c->layers.erase(c->layers.begin() + i); break; }
@@ -1613,7 +1649,7 @@ static void check_fraction(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
                        " != data input pattern size of " + std::to_string(f->input_pattern_size));
     if (post_output) {
         if (!post_output->post) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: `post_output` is not a post output layer");
-        if (f->output_pattern_size != post_output->size)                                          // PostOutputLayer.cpp:70-73
+        if (post_output->kind != CN_LAYER_CTC && f->output_pattern_size != post_output->size)                                          // PostOutputLayer.cpp:70-73
             throw cn_error(CN_ERR_SHAPE, "Output layer size of " + std::to_string(post_output->size) +
                            " != data target pattern size of " + std::to_string(f->output_pattern_size));
     }
@@ -1701,12 +1737,18 @@ static void swap_in_prefetched(cn_ctx *ctx, cn_layer *input, cn_layer *post_outp
     std::swap(input->out_op, pf.in_op);
     if (post_output && post_output->targets) std::swap(post_output->targets, pf.targets);
 }
+// a CTC layer takes no targets from the fraction (cn_layer_set_label_sequences brings its labels): the data paths below see none
+static cn_layer *target_taker(cn_layer *post_output)
+{
+    return post_output && post_output->kind == CN_LAYER_CTC ? nullptr : post_output;
+}
 static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, const cn_fraction *f, bool resident)
 {
     if (!ctx || !input || !f) { g_last_error = "cn_fraction_load: NULL argument"; return CN_ERR_BAD_ARG; }
     return guarded([&] {
         enter(ctx);
         check_fraction(ctx, input, post_output, f);
+        post_output = target_taker(post_output);
         const int T = f->max_seq_length;
         finalize(ctx);
         join_side(ctx);                      // gradient GEMMs of the previous fraction still read the activations
@@ -1753,6 +1795,7 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
             HIP_CHECK(hipStreamSynchronize(ctx->stream));     // the caller may reuse its host buffers on return
         }
         set_current(ctx, f);
+        for (cn_layer *l : ctx->layers) l->ctc_labels_valid = l->ctc_swept = false;      // the labels belonged to the fraction that has been replaced
     });
 }
 
@@ -1779,6 +1822,7 @@ static int fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output
     return guarded([&] {
         enter(ctx);
         check_fraction(ctx, input, post_output, f);
+        post_output = target_taker(post_output);
         if (host && !ctx->overlap) return;            // CN_NO_OVERLAP: no copy stream, no side streams: the load does it all
         require_targets("cn_fraction_prefetch_resident", post_output, f);
         cn_ctx::Prefetch &pf = ctx->pf;
@@ -1821,6 +1865,52 @@ static int post_kind(const cn_layer *l)
     }
 }
 
+// ---- CTC (cn_ctc.hip) ---------------------------------------------------------------------------
+// Host side of a label set: per slot the offsets, per label the chain of later occurrences of the same label in its sequence
+// buf: [labels | next | first] of `stride` ints each, then laboff [PSp + 1] (CtcArgs); returns 2 * (longest sequence) + 1
+static int ctc_pack_labels(int *buf, const int *labels, const int *lengths, int num_sequences, int PSp, size_t stride, int C)
+{
+    int *lab = buf, *next = lab + stride, *first = next + stride, *off = first + stride;
+    std::vector<int> last(C, -1);                 // position of the label's latest occurrence in the current sequence
+    int pos = 0, maxS = 1;
+    for (int s = 0; s < PSp; ++s) {
+        off[s] = pos;
+        const int U = s < num_sequences ? lengths[s] : 0;
+        for (int u = 0; u < U; ++u) {
+            const int k = labels[pos + u], v = last[k];
+            lab[pos + u] = k; next[pos + u] = -1; first[pos + u] = v < 0;
+            if (v >= 0) next[pos + v] = u;
+            last[k] = u;
+        }
+        for (int u = 0; u < U; ++u) last[labels[pos + u]] = -1;
+        maxS = std::max(maxS, 2 * U + 1);
+        pos += U;
+    }
+    off[PSp] = pos;
+    return maxS;
+}
+static CtcArgs ctc_args(cn_layer *post)
+{
+    cn_ctx *c = post->ctx;
+    cn_layer *o = post->prev;
+    const size_t stride = post->ctc_stride;
+    CtcArgs a{};
+    a.y = posteriors(o); a.pat = c->d_pat; a.T = c->T; a.PSp = c->PSp; a.C = post->size; a.Lp = o->Lp;
+    a.labels = post->ctc_labels; a.next = a.labels + stride; a.first = a.next + stride; a.laboff = a.first + stride;
+    a.maxS = post->ctc_maxS; a.alpha = post->ctc_alpha; a.beta = post->ctc_beta; a.Sp = round_up(post->ctc_maxS, 64);
+    a.info = post->ctc_info; a.rowstat = post->ctc_rowstat; a.err = o->err;
+    return a;
+}
+// the sweeps of the current forward pass: enqueued by whoever needs them first (the error or the output errors), once
+static CtcArgs ctc_swept(cn_layer *post, const char *who)
+{
+    if (!post->ctc_labels_valid)
+        throw cn_error(CN_ERR_STATE, std::string(who) + ": the ctc layer has no label sequences for the loaded fraction (call cn_layer_set_label_sequences after cn_fraction_load)");
+    const CtcArgs a = ctc_args(post);
+    if (!post->ctc_swept) { launch_ctc_sweeps(post->ctx->stream, a); post->ctc_swept = true; }
+    return a;
+}
+
 int cn_layer_forward(cn_layer *layer)
 {
     if (!layer) { g_last_error = "cn_layer_forward: layer is NULL"; return CN_ERR_BAD_ARG; }
@@ -1854,6 +1944,8 @@ int cn_layer_backward(cn_layer *layer)
             cn_layer *o = layer->prev;
             if (layer->kind == CN_LAYER_MULTICLASS_CLASSIFICATION)
                 o->mcc_pending = true;         // injected inside the output layer's backward pass (fused kernel)
+            else if (layer->kind == CN_LAYER_CTC)
+                launch_ctc_errors(c->stream, ctc_swept(layer, "cn_layer_backward"));
             else
                 launch_post_backward(c->stream, post_kind(layer), posteriors(o), layer->targets, c->d_pat, c->N, o->size, o->Lp, o->err);
         }
@@ -1867,6 +1959,11 @@ static void launch_loss(cn_layer *post, float *dst, bool per_call)
     cn_layer *o = post->prev;
     if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION && c->rowstat_of == o) {      // the softmax forward pass left the row statistics
         launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, dst, per_call);
+        return;
+    }
+    if (post->kind == CN_LAYER_CTC) {                                                   // its own rows: -log p in the row of t = 0 of every slot
+        const CtcArgs a = ctc_swept(post, per_call ? "cn_loss_eval" : "cn_loss_accumulate");
+        launch_rowstat_reduce(c->stream, a.rowstat, c->PSp, dst, per_call, 1.0f);
         return;
     }
     flush_loss(c);                     // (the row statistics are about to be overwritten)
@@ -1902,7 +1999,7 @@ int cn_loss_eval(cn_layer *post, float *error, int *correct)
         }
         int cc = 0;
         read_loss_sums(c, c->d_loss, false, error, &cc);
-        if (correct) *correct = is_class_post(post) ? cc : -1;
+        if (correct) *correct = (is_class_post(post) || post->kind == CN_LAYER_CTC) ? cc : -1;
     });
 }
 
@@ -1925,6 +2022,46 @@ int cn_loss_accumulate(cn_layer *post)
         }
         Timed tm(c, KC_OTHER);
         launch_loss(post, c->d_loss_acc, false);       // (nothing is deferred any more: its flush_loss does nothing)
+    });
+}
+
+int cn_layer_set_label_sequences(cn_layer *ctc, const int *labels, const int *label_lengths, int num_sequences)
+{
+    if (!ctc || (!label_lengths && num_sequences > 0)) { g_last_error = "cn_layer_set_label_sequences: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = ctc->ctx;
+        enter(c);
+        if (ctc->kind != CN_LAYER_CTC) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_label_sequences: not a ctc layer");
+        require_loaded(c);
+        if (num_sequences != c->numSeqs)
+            throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_label_sequences: " + std::to_string(num_sequences) + " label sequences for a fraction of " +
+                                           std::to_string(c->numSeqs) + " sequences");
+        size_t total = 0;
+        for (int s = 0; s < num_sequences; ++s) {
+            if (label_lengths[s] < 0) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_label_sequences: negative label sequence length");
+            if (label_lengths[s] > ctc->ctc_cap)
+                throw cn_error(CN_ERR_SHAPE, "cn_layer_set_label_sequences: a label sequence of " + std::to_string(label_lengths[s]) +
+                                             " labels exceeds this layer's cap of " + std::to_string(ctc->ctc_cap) +
+                                             " (set the context option ctc_max_labels before the layer is created)");
+            total += (size_t)label_lengths[s];
+        }
+        if (total && !labels) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_label_sequences: labels missing");
+        for (size_t i = 0; i < total; ++i)
+            if (labels[i] < 0 || labels[i] > ctc->size - 2)
+                throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_label_sequences: label " + std::to_string(labels[i]) + " outside [0, " +
+                                               std::to_string(ctc->size - 2) + "] (the last unit is the blank)");
+        // packed with the fraction's own label total as the stride: what is uploaded is what is used
+        const size_t stride = std::max<size_t>(total, 1), ints = 3 * stride + c->PSp + 1;
+        const unsigned b = ctc->ctc_uploads++ & 1u;
+        if (!ctc->ctc_hbuf[b]) {
+            HIP_CHECK(hipHostMalloc((void **)&ctc->ctc_hbuf[b], (3 * (size_t)ctc->ctc_cap * ctc->PS + c->PSp + 1) * sizeof(int), hipHostMallocDefault));
+            HIP_CHECK(hipEventCreateWithFlags(&ctc->ctc_ev[b], hipEventDisableTiming));
+        } else HIP_CHECK(hipEventSynchronize(ctc->ctc_ev[b]));        // the upload two fractions ago has read this image
+        ctc->ctc_maxS = ctc_pack_labels(ctc->ctc_hbuf[b], labels, label_lengths, num_sequences, c->PSp, stride, ctc->size);
+        ctc->ctc_stride = stride;
+        HIP_CHECK(hipMemcpyAsync(ctc->ctc_labels, ctc->ctc_hbuf[b], ints * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipEventRecord(ctc->ctc_ev[b], c->stream));
+        ctc->ctc_labels_valid = true; ctc->ctc_swept = false;
     });
 }
 
@@ -2418,6 +2555,65 @@ int cn_dbg_gemm_nt(cn_ctx *ctx, const float *A, const float *B, float *C, int M,
             HIP_CHECK(hipMemcpyAsync(C, dC2 ? dC2 : dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIP_CHECK(hipStreamSynchronize(ctx->stream));
         }
+    });
+}
+
+int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
+               float *loss_out, float *err_out)
+{
+    if (!ctx || !y || !pat || !label_lengths || !loss_out || !err_out) { g_last_error = "cn_dbg_ctc: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        if (T <= 0 || PS <= 0 || C < 2) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc: T, PS must be positive and C >= 2");
+        int maxU = 0; size_t total = 0;
+        for (int s = 0; s < PS; ++s) {
+            if (label_lengths[s] < 0) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc: negative label sequence length");
+            maxU = std::max(maxU, label_lengths[s]); total += (size_t)label_lengths[s];
+        }
+        if (total && !labels) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc: labels missing");
+        for (size_t i = 0; i < total; ++i)
+            if (labels[i] < 0 || labels[i] > C - 2) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc: label outside [0, C - 2]");
+        const int PSp = round_up(PS, 4), Lp = round_up(C, 32), N = T * PSp;
+        if (!ctc_shape_fits(maxU, Lp)) throw cn_error(CN_ERR_SHAPE, "cn_dbg_ctc: label sequences or rows too long for a workgroup");
+        const size_t stride = std::max<size_t>(total, 1);
+        std::vector<int> packed(3 * stride + PSp + 1, 0);
+        const int maxS = ctc_pack_labels(packed.data(), labels, label_lengths, PS, PSp, stride, C);
+        const int Sp = round_up(maxS, 64);
+        // the caller's [T][PS] rows in the device's [T][PSp] pitch: pad slots are PATTYPE_NONE, pad columns zero
+        std::vector<float> hy((size_t)N * Lp, 0.f); std::vector<char> hpat(N, 0);
+        for (int t = 0; t < T; ++t)
+            for (int s = 0; s < PS; ++s) {
+                hpat[(size_t)t * PSp + s] = pat[(size_t)t * PS + s];
+                memcpy(&hy[((size_t)t * PSp + s) * Lp], y + ((size_t)t * PS + s) * C, C * sizeof(float));
+            }
+        Scratch dy(hy.size() * sizeof(float)), dpat(N), dlab(packed.size() * sizeof(int)), dal((size_t)PSp * T * Sp * sizeof(int2)),
+            dbe((size_t)PSp * T * Sp * sizeof(int2)), dinfo((size_t)PSp * 2 * sizeof(int)), drs((size_t)PSp * 2 * sizeof(float)), derr((size_t)N * Lp * sizeof(float));
+        hipStream_t st = ctx->stream;
+        HIP_CHECK(hipMemcpyAsync(dy.p, hy.data(), hy.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dpat.p, hpat.data(), N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dlab.p, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(drs.p, 0xFF, (size_t)PSp * 2 * sizeof(float), st));         // NaNs: the sweeps write every slot's pair
+        HIP_CHECK(hipMemsetAsync(derr.p, 0xFF, (size_t)N * Lp * sizeof(float), st));        // NaNs: an element the launches leave out shows
+        CtcArgs a{};
+        a.y = dy.get(); a.pat = dpat.get<char>(); a.T = T; a.PSp = PSp; a.C = C; a.Lp = Lp;
+        a.labels = dlab.get<int>(); a.next = a.labels + stride; a.first = a.next + stride; a.laboff = a.first + stride;
+        a.maxS = maxS; a.alpha = dal.get<int2>(); a.beta = dbe.get<int2>(); a.Sp = Sp;
+        a.info = dinfo.get<int>(); a.rowstat = drs.get(); a.err = derr.get();
+        launch_ctc_sweeps(st, a);
+        launch_ctc_errors(st, a);
+        std::vector<float> hrs((size_t)PSp * 2), herr((size_t)N * Lp);
+        HIP_CHECK(hipMemcpyAsync(hrs.data(), drs.p, hrs.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(herr.data(), derr.p, herr.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        // pad slots and pad columns are not part of the caller's layout: the hook itself holds them to the contract (exactly 0)
+        for (int t = 0; t < T; ++t)
+            for (int s = 0; s < PSp; ++s)
+                for (int j = 0; j < Lp; ++j) {
+                    const float v = herr[((size_t)t * PSp + s) * Lp + j];
+                    if (s < PS && j < C) err_out[((size_t)t * PS + s) * C + j] = v;
+                    else if (!(v == 0.f)) throw cn_error(CN_ERR_STATE, "cn_dbg_ctc: a pad slot or pad column of the output errors is not 0");
+                }
+        for (int s = 0; s < PS; ++s) loss_out[s] = hrs[2 * s];
     });
 }
 

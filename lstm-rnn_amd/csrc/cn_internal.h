@@ -45,7 +45,10 @@ enum Prec { P_BF16 = 0, P_F32 = 1, P_X3 = 2 };
     FLAG(no_s2) FLAG(no_s2w) FLAG(no_s2w_asm) FLAG(pre16)                                                                           \
     /* step structure */                                                                                                          \
     FLAG(softmax_exact) FLAG(tail_on_side) FLAG(no_side_rule) FLAG(no_lazy_softmax) FLAG(lazy_softmax) FLAG(comm_test_double)     \
-    FLAG(no_loss_defer) FLAG(no_pack_group) FLAG(no_sgd_fuse) NUM(comm_cu_margin, 32)
+    FLAG(no_loss_defer) FLAG(no_pack_group) FLAG(no_sgd_fuse) NUM(comm_cu_margin, 32)                                           \
+    /* CTC: label cap per sequence of a CTC layer created afterwards (0: min(max_seq_length, 512)); A/B: the beta sweep as a     \
+       launch of its own behind the alpha sweep instead of beside it */                                                          \
+    NUM(ctc_max_labels, 0) FLAG(ctc_serial_sweeps)
 struct Options {
 #define CN_OPT_FIELD(name) int name = 0;
 #define CN_OPT_FIELD_NUM(name, dflt) long name = dflt;
@@ -332,6 +335,30 @@ void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, f
 struct AdamScalars { float b1, omb1, b2, omb2, alpha_t, eps_t; };
 void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done = nullptr);
 void launch_accumulate(hipStream_t s, float *acc, const float *wu, size_t n, bool first);
+
+// ---- CTC post output layer (cn_ctc.hip; the arithmetic is stated in that file's header) -----------------------------------------
+struct CtcArgs {
+    const float *y; const char *pat;      // posteriors [T * PSp][Lp], pattern types [T * PSp]
+    int T, PSp, C, Lp;
+    // label sequences in slot order: slot s owns entries laboff[s] .. laboff[s + 1) (laboff has PSp + 1 entries; empty and pad
+    // slots own none); next[u]: the next position of the same slot with the same label, relative to laboff[s], or -1;
+    // first[u]: no earlier position of the slot has this label
+    const int *labels, *next, *first, *laboff;
+    int maxS;                             // 2 * (longest label sequence of the fraction) + 1
+    int2 *alpha, *beta; int Sp;           // the sweeps' columns, [PSp][T][Sp] pairs {mantissa bits, exponent} each, Sp >= maxS
+    int *info;                            // [PSp][2]: {len, 1 if the sequence has an alignment with p > 0}
+    float *rowstat;                       // [PSp][2]: slot s receives {-log p, 1} or {0, 0}
+    float *err;                           // [T * PSp][Lp] dL/dy (launch_ctc_errors)
+    int only;                             // launch_ctc_sweeps sets it: 0 both sweeps in this launch (blockIdx.y), 1 alpha alone, 2 beta alone
+};
+constexpr int CTC_MAX_STATES = 4096;      // sixteen states per thread of a 256-thread workgroup
+// can a layer with this label cap and output pitch run (states per workgroup, LDS of the error kernel)?
+bool ctc_shape_fits(int max_labels, int Lp);
+// alpha and beta sweeps of every slot, concurrently (option ctc_serial_sweeps: two launches, one behind the other); fills alpha,
+// beta, info and rowstat
+void launch_ctc_sweeps(hipStream_t s, const CtcArgs &a);
+// behind the sweeps: every row and column of err
+void launch_ctc_errors(hipStream_t s, const CtcArgs &a);
 // gather a padded row-major fp32/op matrix into the reference layout [N][L]
 // (host row n = t*PS + s maps to device row t*PSp + s)
 void launch_unpad(hipStream_t s, bool src_is_bf16, const void *src, long ld, int col0, int cstride, int N, int L, float *dst, long ldd, int dcol0, int PS, int PSp);

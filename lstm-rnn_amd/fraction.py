@@ -11,11 +11,13 @@ PATTYPE_NONE, PATTYPE_FIRST, PATTYPE_NORMAL, PATTYPE_LAST = 0, 1, 2, 3
 
 
 def make_fraction(inputs, targets, parallel_sequences, classification=True, output_size=None,
-                  context_left=0, context_right=0, output_lag=0):
+                  context_left=0, context_right=0, output_lag=0, labels=None):
     """inputs: list of [len_i][P] float arrays; targets: list of [len_i] int arrays (classification)
     or [len_i][L] float arrays.  Returns the dict layout used by NeuralNetwork.load_sequences.
     context_left/right splice neighbouring frames into each input pattern (edge frames repeated) and
-    output_lag delays the targets (class 0 / value 1.0 before the lag), DataSet.cpp:302-305,346-397."""
+    output_lag delays the targets (class 0 / value 1.0 before the lag), DataSet.cpp:302-305,346-397.
+    labels: list of int arrays, the label sequence of each sequence for a ctc net (no counterpart in the reference); `targets`
+    may then be None (the per-frame classes stay -1)."""
     PS = int(parallel_sequences)
     if not inputs or len(inputs) > PS:
         raise ValueError("need 1..parallel_sequences sequences")
@@ -26,6 +28,12 @@ def make_fraction(inputs, targets, parallel_sequences, classification=True, outp
     x = np.zeros((T, PS, P), np.float32)                       # :330
     pat = np.full((T, PS), PATTYPE_NONE, np.int8)              # :331
     frac = {"T": T, "Tmin": Tmin, "PS": PS, "numSeqs": len(inputs), "seqLengths": lengths}
+    if labels is not None:
+        if len(labels) != len(inputs):
+            raise ValueError("need one label sequence per sequence")
+        frac["labels"] = [np.asarray(l, np.int32).reshape(-1) for l in labels]
+    if targets is None:
+        targets = [None] * len(inputs)
     if classification:
         tc = np.full((T, PS), -1, np.int32)                    # :333-334
     else:
@@ -36,7 +44,9 @@ def make_fraction(inputs, targets, parallel_sequences, classification=True, outp
             src = np.clip(np.arange(n) + off, 0, n - 1)
             x[:n, i, k * P0:(k + 1) * P0] = np.asarray(xi)[src]
         lag = min(int(output_lag), n)
-        if classification:
+        if ti is None:
+            pass
+        elif classification:
             tc[:lag, i] = 0                                    # :372-380
             tc[lag:n, i] = np.asarray(ti)[:n - lag]
         else:

@@ -67,6 +67,7 @@ public:
     int dpWorld() const { return m_dpWorld; }
     bool help() const { return m_help; }
     bool dumpFractions() const { return m_dumpFractions; }
+    bool dumpLabels() const { return m_dumpLabels; }          // --dump_fractions rows also print the label sequences' counts
     int dumpEpochs() const { return m_dumpEpochs; }
     // data/noise options of Configuration.cpp:139-146,171-176
     real_t inputNoiseSigma() const { return m_inputNoiseSigma; }
@@ -85,7 +86,7 @@ public:
 
 private:
     int m_dumpEpochs = 1;
-    bool m_dumpFractions = false, m_autosave = false, m_autosaveBest = false;
+    bool m_dumpFractions = false, m_dumpLabels = false, m_autosave = false, m_autosaveBest = false;
     real_t m_inputNoiseSigma = 0, m_weightNoiseSigma = 0;
     int m_inputLeftContext = 0, m_inputRightContext = 0, m_outputTimeLag = 0;
     std::string m_autosavePrefix, m_continueFile, m_serializedOptions;

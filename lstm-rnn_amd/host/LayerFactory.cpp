@@ -19,7 +19,7 @@ layers::Layer *LayerFactory::createLayer(cn_ctx *ctx, const std::string &layerTy
     if (layerType == "lstm") return new LstmLayer(ctx, layerChild, weightsSection, *precedingLayer, false);
     if (layerType == "blstm") return new LstmLayer(ctx, layerChild, weightsSection, *precedingLayer, true);
     if (layerType == "sse" || layerType == "weightedsse" || layerType == "rmse" || layerType == "ce" || layerType == "wf" ||
-        layerType == "binary_classification" || layerType == "multiclass_classification") {
+        layerType == "binary_classification" || layerType == "multiclass_classification" || layerType == "ctc") {
         if (!precedingLayer->isTrainable())                                                      // LayerFactory.cu:68-70
             throw std::runtime_error("Cannot add post output layer after a non trainable layer");
         if (layerType == "sse") return new SsePostOutputLayer(ctx, layerChild, *precedingLayer);
@@ -28,6 +28,7 @@ layers::Layer *LayerFactory::createLayer(cn_ctx *ctx, const std::string &layerTy
         if (layerType == "ce") return new CePostOutputLayer(ctx, layerChild, *precedingLayer);
         if (layerType == "wf") return new SseMaskPostOutputLayer(ctx, layerChild, *precedingLayer);
         if (layerType == "binary_classification") return new BinaryClassificationLayer(ctx, layerChild, *precedingLayer);
+        if (layerType == "ctc") return new CtcPostOutputLayer(ctx, layerChild, *precedingLayer);
         return new MulticlassClassificationLayer(ctx, layerChild, *precedingLayer);
     }
     throw std::runtime_error("Unknown layer type '" + layerType + "'");                          // LayerFactory.cu:86

@@ -122,6 +122,8 @@ void NeuralNetwork::loadSequences(const data_sets::DataSetFraction &fraction)
     // (no synchronisation: cn_fraction_load has copied the host vectors into pinned staging memory when it returns, so
     // the caller may release them, and the upload runs under the previous fraction's compute)
     hipCheck(cn_fraction_load(m_ctx, m_layers.front()->handle(), m_layers.back()->handle(), &f), m_ctx);
+    // a ctc layer's labels belong to the fraction just loaded (with --gpus N: this rank's slots of the global fraction)
+    if (layers::CtcPostOutputLayer *ctc = dynamic_cast<layers::CtcPostOutputLayer *>(m_layers.back().get())) ctc->setLabelSequences(fraction);
 }
 
 void NeuralNetwork::initDataParallel(const char *id, int rank, int world)

@@ -43,7 +43,7 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
         if (firstFile) {                                                                       // :489-500
             m_isClassificationData = nc.hasDimension("numLabels");
             m_inputPatternSize = nc.dimension("inputPattSize");
-            if (m_isClassificationData) { int numLabels = nc.dimension("numLabels"); m_outputPatternSize = (numLabels == 2 ? 1 : numLabels); }
+            if (m_isClassificationData) { int numLabels = nc.dimension("numLabels"); m_numLabels = numLabels; m_outputPatternSize = (numLabels == 2 ? 1 : numLabels); }
             else m_outputPatternSize = nc.dimension("targetPattSize");
         } else {                                                                               // :502-515
             if (m_isClassificationData) {
@@ -166,6 +166,14 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
         if (globalIdx(i) >= (int)m_sequences.size()) continue;
         const sequence_t &seq = m_sequences[globalIdx(i)];
         const float *src = m_inputData.data() + seq.inputsBegin;
+        if (m_isClassificationData) {                                                          // the label sequence: runs collapsed
+            std::vector<int> labels;
+            for (int t = 0; t < seq.length; ++t) {
+                const int k = m_classData[seq.targetsBegin + t];
+                if (labels.empty() || labels.back() != k) labels.push_back(k);
+            }
+            frac->m_labelSeqs.push_back(labels);
+        }
         if (m_augment.noiseDeviation) {                                                        // _addNoise, :250-265
             // the reference draws from boost::mt19937 + boost::normal_distribution (absent here);
             // std::mt19937 seeded from --random_seed keeps runs reproducible per seed

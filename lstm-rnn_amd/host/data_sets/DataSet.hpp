@@ -28,6 +28,10 @@ public:
     const Hip::real_vector &inputs() const { return m_inputs; }
     const Hip::real_vector &outputs() const { return m_outputs; }
     const Hip::int_vector &targetClasses() const { return m_targetClasses; }
+    // classification data: the label sequence of each sequence of the fraction, slot by slot -- its per-frame target classes
+    // with every run collapsed (a a a b b a -> a b a); what a ctc post output layer trains against (no counterpart in the
+    // reference).  A label that repeats without another one in between cannot be expressed this way.
+    const std::vector<std::vector<int> > &labelSeqs() const { return m_labelSeqs; }
 
 private:
     friend class DataSet;
@@ -36,6 +40,7 @@ private:
     Hip::real_vector m_inputs, m_outputs;
     Hip::pattype_vector m_patTypes;
     Hip::int_vector m_targetClasses;
+    std::vector<std::vector<int> > m_labelSeqs;
 };
 
 // what the reference pulls from Configuration::instance() inside _makeFractionTask / _addNoise
@@ -73,13 +78,14 @@ public:
     int inputPatternSize() const { return m_inputPatternSize; }                        // per frame, before context splicing
     int fractionInputPatternSize() const { return m_inputPatternSize * (m_augment.contextLeft + m_augment.contextRight + 1); }
     int outputPatternSize() const { return m_outputPatternSize; }
+    int numLabels() const { return m_numLabels; }                                     // classification data: the numLabels dimension
     const Hip::real_vector &outputMeans() const { return m_outputMeans; }
     const Hip::real_vector &outputStdevs() const { return m_outputStdevs; }
 
 private:
     bool m_fractionShuffling = false, m_sequenceShuffling = false, m_isClassificationData = false;
     int m_parallelSequences = 0, m_totalSequences = 0, m_totalTimesteps = 0, m_minSeqLength = 0, m_maxSeqLength = 0,
-        m_inputPatternSize = 0, m_outputPatternSize = 0, m_curFirstSeqIdx = -1, m_rank = 0, m_world = 1;
+        m_inputPatternSize = 0, m_outputPatternSize = 0, m_numLabels = 0, m_curFirstSeqIdx = -1, m_rank = 0, m_world = 1;
     unsigned m_rngState = 0;
     Hip::real_vector m_outputMeans, m_outputStdevs, m_inputData, m_targetData;
     Hip::int_vector m_classData;

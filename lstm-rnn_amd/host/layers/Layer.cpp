@@ -183,6 +183,30 @@ int MulticlassClassificationLayer::countCorrectClassifications()
     return c;
 }
 
+CtcPostOutputLayer::CtcPostOutputLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer)
+    : PostOutputLayer(ctx, layerChild, CN_LAYER_CTC, precedingLayer) {}
+const std::string &CtcPostOutputLayer::type() const { static const std::string s("ctc"); return s; }
+void CtcPostOutputLayer::loadSequences(const data_sets::DataSetFraction &fraction)
+{
+    Layer::loadSequences(fraction);        // (labels are optional here: a forward pass over unlabelled data needs none)
+}
+void CtcPostOutputLayer::setLabelSequences(const data_sets::DataSetFraction &fraction)
+{
+    if ((int)fraction.labelSeqs().size() != fraction.numSequences()) return;    // no classification data: the error calls will say so
+    std::vector<int> labels, lengths;
+    for (size_t i = 0; i < fraction.labelSeqs().size(); ++i) {
+        lengths.push_back((int)fraction.labelSeqs()[i].size());
+        labels.insert(labels.end(), fraction.labelSeqs()[i].begin(), fraction.labelSeqs()[i].end());
+    }
+    hipCheck(cn_layer_set_label_sequences(m_handle, labels.data(), lengths.data(), (int)lengths.size()), m_ctx);
+}
+int CtcPostOutputLayer::countCorrectClassifications()
+{
+    float e = 0; int c = 0;
+    hipCheck(cn_loss_eval(m_handle, &e, &c), m_ctx);
+    return c;
+}
+
 #define CN_POST_LAYER(CLASS, KIND, TYPE)                                                                         \
     CLASS::CLASS(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer)                              \
         : PostOutputLayer(ctx, layerChild, KIND, precedingLayer) {}                                              \

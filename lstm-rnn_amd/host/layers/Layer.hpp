@@ -144,6 +144,17 @@ public:
     int countCorrectClassifications();
 };
 
+// Connectionist Temporal Classification (no counterpart in the reference): behind a softmax layer of numLabels + 1 units, the
+// last one the blank; trains against the fraction's label sequences (DataSetFraction::labelSeqs)
+class CtcPostOutputLayer : public PostOutputLayer {
+public:
+    CtcPostOutputLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer);
+    const std::string &type() const;
+    void loadSequences(const data_sets::DataSetFraction &fraction);
+    void setLabelSequences(const data_sets::DataSetFraction &fraction);     // behind cn_fraction_load: cn_layer_set_label_sequences
+    int countCorrectClassifications();                                      // sequences that contributed to the error
+};
+
 // The remaining post output layers of LayerFactory.cu:52-87; each is a thin handle on the C ABI kind.
 class WeightedSsePostOutputLayer : public PostOutputLayer {   // layers/WeightedSsePostOutputLayer.{hpp,cu}; size = 2 x output layer
 public:

@@ -238,12 +238,38 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                         pieces += (i ? "," : "") + std::to_string(frac.seqInfo(i).originalSeqIdx);
                     }
                     const bool any = frac.numSequences() > 0;
-                    printf("FRACTION %d T=%d Tmin=%d seqs=%d none=%d sum_inputs=%.6f sum_targets=%ld first_tag=%s tags=%s lens=%s pieces=%s\n", idx++,
+                    printf("FRACTION %d T=%d Tmin=%d seqs=%d none=%d sum_inputs=%.6f sum_targets=%ld first_tag=%s tags=%s lens=%s pieces=%s", idx++,
                            frac.maxSeqLength(), frac.minSeqLength(), frac.numSequences(), none, sx, st, any ? frac.seqInfo(0).seqTag.c_str() : "-",
                            any ? order.c_str() : "-", any ? lens.c_str() : "-", any ? pieces.c_str() : "-");
+                    if (config.dumpLabels()) {      // --dump_labels: the label sequences a ctc layer would train against
+                        long total = 0, sum = 0;
+                        for (size_t i = 0; i < frac.labelSeqs().size(); ++i)
+                            for (size_t k = 0; k < frac.labelSeqs()[i].size(); ++k) { ++total; sum += frac.labelSeqs()[i][k]; }
+                        printf(" label_seqs=%d labels_total=%ld sum_labels=%ld", (int)frac.labelSeqs().size(), total, sum);
+                    }
+                    printf("\n");
                 }
             }
             return 0;
+        }
+
+        // A ctc network (last layer of type "ctc") has one output unit per label and the blank behind them; held against the data
+        // before the device is touched.
+        bool ctcTask = false;
+        if (netDoc.isObject() && netDoc.hasMember("layers") && netDoc["layers"].isArray() && netDoc["layers"].size() > 0) {
+            const json::Value &last = netDoc["layers"][netDoc["layers"].size() - 1];
+            ctcTask = last.isObject() && last.hasMember("type") && last["type"].getString() == "ctc";
+            const int units = ctcTask && last.hasMember("size") ? last["size"].getInt() : 0;
+            auto checkSet = [&](const data_sets::DataSet &set, const char *which, bool labelsOptional) {
+                if (!ctcTask || set.empty()) return;
+                if (!set.isClassificationData() && labelsOptional) return;       // forward pass over unlabelled data
+                if (!set.isClassificationData()) throw std::runtime_error(std::string("A ctc network needs classification data: the ") + which + " set has none");
+                if (set.numLabels() + 1 != units)
+                    throw std::runtime_error("Number of classes mismatch: a ctc network needs numLabels + 1 = " + std::to_string(set.numLabels() + 1) +
+                                             " output units (the blank last), the network has " + std::to_string(units) + " (" + which + " set)");
+            };
+            checkSet(*trainingSet, "training", false); checkSet(*validationSet, "validation", false); checkSet(*testSet, "test", false);
+            checkSet(*feedForwardSet, "feed forward input", true);
         }
 
         printf("Creating the neural network... ");
@@ -280,18 +306,21 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             if (testHook("CN_DP_TEST_FAIL_RANK") && atoi(testHook("CN_DP_TEST_FAIL_RANK")) == dp.rank)
                 throw std::runtime_error("test hook CN_DP_TEST_FAIL_RANK: this rank fails on purpose");
         }
-        if (!trainingSet->empty() && trainingSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
-            throw std::runtime_error("Post output layer size != target pattern size of the training set");
-        if (!validationSet->empty() && validationSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
-            throw std::runtime_error("Post output layer size != target pattern size of the validation set");
-        if (!testSet->empty() && testSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
-            throw std::runtime_error("Post output layer size != target pattern size of the test set");
+        if (!ctcTask) {
+            if (!trainingSet->empty() && trainingSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
+                throw std::runtime_error("Post output layer size != target pattern size of the training set");
+            if (!validationSet->empty() && validationSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
+                throw std::runtime_error("Post output layer size != target pattern size of the validation set");
+            if (!testSet->empty() && testSet->outputPatternSize() != neuralNetwork.postOutputLayer().size())
+                throw std::runtime_error("Post output layer size != target pattern size of the test set");
+        }
         printf("done.\nLayers:\n");
         printLayers(neuralNetwork);
         printf("\n");
 
+        // (ctc: the percentage column is the label error rate of best-path decoding, on the validation and test sets only)
         const bool classificationTask = dynamic_cast<layers::MulticlassClassificationLayer *>(&neuralNetwork.postOutputLayer()) != 0 ||
-                                        dynamic_cast<layers::BinaryClassificationLayer *>(&neuralNetwork.postOutputLayer()) != 0;   // main.cpp:165-166
+                                        dynamic_cast<layers::BinaryClassificationLayer *>(&neuralNetwork.postOutputLayer()) != 0 || ctcTask;   // main.cpp:165-166
 
         if (config.trainingMode()) {
             printf("Creating the optimizer... ");
@@ -347,7 +376,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 // CN_DRIVER_TIMING=1: the epoch's wall time with microsecond resolution on stderr (the table above keeps the
                 // reference's format, one decimal); bench.py's driver leg reads it
                 if (getenv("CN_DRIVER_TIMING")) fprintf(stderr, "TIMING epoch %d %.6f s %d frames\n", optimizer.currentEpoch(), duration, trainingSet->totalTimesteps());
-                if (classificationTask) infoRows += printfRow(errFormat, (double)optimizer.curTrainingClassError() * 100.0, (double)optimizer.curTrainingError());
+                if (ctcTask) infoRows += printfRow("      -%10.3lf |", (double)optimizer.curTrainingError());     // (decoding every training fraction would put a D2H copy on the hot path)
+                else if (classificationTask) infoRows += printfRow(errFormat, (double)optimizer.curTrainingClassError() * 100.0, (double)optimizer.curTrainingError());
                 else infoRows += printfRow(errFormat, (double)optimizer.curTrainingError());
                 const bool validated = !validationSet->empty() && optimizer.currentEpoch() % config.validateEvery() == 0;
                 if (validated) {

@@ -14,7 +14,7 @@ from . import binding as B
 
 _TRAINABLE = ("lstm", "blstm", "softmax", "feedforward_tanh", "feedforward_logistic",
               "feedforward_identity")
-_POST = ("sse", "multiclass_classification", "weightedsse", "wf", "ce", "rmse", "binary_classification")
+_POST = ("sse", "multiclass_classification", "weightedsse", "wf", "ce", "rmse", "binary_classification", "ctc")
 
 
 class Layer:
@@ -110,7 +110,7 @@ class Layer:
 
 class NeuralNetwork:
     def __init__(self, layers, weights=None, parallel_sequences=1, max_seq_length=1,
-                 precision=B.PREC_F32, device=0, stream=None, seed=None, deterministic=None):
+                 precision=B.PREC_F32, device=0, stream=None, seed=None, deterministic=None, options=None):
         self.lib = B.load_library()
         self.parallel_sequences, self.max_seq_length = int(parallel_sequences), int(max_seq_length)
         self.PS = self.parallel_sequences
@@ -121,6 +121,8 @@ class NeuralNetwork:
         self.ctx = ctx
         if deterministic is not None:                 # None: the library's default (on in the parity modes, off for bf16)
             self.set_option("deterministic", 1 if deterministic else 0)
+        for name, value in (options or {}).items():   # options that size allocations ("ctc_max_labels") belong before the layers
+            self.set_option(name, value)
         self.layers = []
         self.T = self.Tmin = self.N = 0
         try:
@@ -230,6 +232,15 @@ class NeuralNetwork:
         B.check(self.lib.cn_fraction_load(self.ctx, self.layers[0].handle, self.layers[-1].handle, C.byref(f)), self.ctx)
         self.T, self.Tmin = f.max_seq_length, f.min_seq_length
         self.N = self.T * self.PS
+        if self.layers[-1].type == "ctc" and frac.get("labels") is not None:
+            self.set_label_sequences(frac["labels"])
+
+    def set_label_sequences(self, labels):
+        """cn_layer_set_label_sequences: one int array of labels per sequence of the fraction loaded last (a ctc net)."""
+        lens = np.asarray([len(l) for l in labels], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32).reshape(-1) for l in labels] + [np.zeros(0, np.int32)]))
+        B.check(self.lib.cn_layer_set_label_sequences(self.layers[-1].handle, flat.ctypes.data_as(C.c_void_p),
+                                                      lens.ctypes.data_as(C.c_void_p), len(labels)), self.ctx)
 
     def prefetch_sequences(self, frac):
         """cn_fraction_prefetch: `frac` (host arrays, as for load_sequences) is what the next load_sequences will load -- the
