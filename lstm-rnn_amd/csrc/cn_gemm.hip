@@ -15,60 +15,38 @@
 //             Split-K over frames, fp32 atomics into the pre-zeroed gradient.
 // Operand type: bf16 (v_mfma_f32_32x32x16_bf16) or fp32 (v_mfma_f32_32x32x2_f32, exact fp32).
 #include "cn_internal.h"
-#include "cn_lstm_device.h"      // vector types, split_bf16
+#include "cn_gemm_device.h"     // the pieces every GEMM kernel shares: activation, mma32, tile order, C/D map, store_out4
 
 #include <cstdlib>
 
 namespace cn {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-__device__ __forceinline__ float act_apply(int act, float x)
+// ---------------------------------------------------------------------------------------------
+// host helpers of all GEMM launchers
+// ---------------------------------------------------------------------------------------------
+int device_cus()
 {
-    // activation_functions/Logistic.cuh:33-44, Tanh.cuh:33-36 (tanh(x) = 2*logistic(2x) - 1)
-    if (act == ACT_IDENTITY) return x;
-    float z = (act == ACT_TANH) ? 2.0f * x : x;
-    float s;
-    if (z < 88.722839f) s = (z > -88.722839f) ? 1.0f / (1.0f + __expf(-z)) : 0.0f;
-    else s = 1.0f;
-    return (act == ACT_TANH) ? 2.0f * s - 1.0f : s;
+    static int cus_of[64] = {0};
+    int dev = 0; (void)hipGetDevice(&dev);
+    int &cus = cus_of[dev & 63];
+    if (!cus && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)) cus = 256;
+    return cus;
 }
 
-// one K-group (32 bytes of K per row: 16 bf16 or 8 fp32) of a 32x32 tile product
-template <bool F32>
-__device__ __forceinline__ void mma32(f32x16 &acc, const u32x4 &a, const u32x4 &b)
+bool rows_aligned(const void *base, long ld, int elt, int align) { return (uintptr_t)base % align == 0 && ld * elt % align == 0; }
+bool rows_fit(long rows, long ld, int elt, unsigned long long limit) { return (unsigned long long)rows * ld * elt < limit; }
+bool nt_out_rows_aligned(const GemmNT &g)
 {
-    if constexpr (F32) {
-        // K order inside the group is permuted identically for A and B (lane half h holds
-        // k = 4h..4h+3), which leaves the dot product unchanged.
-        // (bit_cast the whole vector: a bit_cast of a single ext_vector element picks element 0)
-        const f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[i], acc, 0, 0, 0);
-    } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                      __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
+    return (!g.C || rows_aligned(g.C, g.ldc, 4, 16)) && (!g.C2 || rows_aligned(g.C2, g.ldc2, 2, 8));
 }
 
-// split-bf16 product of one 16-element K-group of a 32x32 tile (P_X3): three bf16 MFMAs, small terms first
-__device__ __forceinline__ void mma32_x3(f32x16 &acc, const u32x4 &ah, const u32x4 &al, const u32x4 &bh, const u32x4 &bl)
+int tn_plan_splits(const GemmTN &g, int splits, int bk, int *kchunk, FoldItem *fold, int *nfold)
 {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, bh), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bl), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bh), acc, 0, 0, 0);
-}
-// four fp32 -> 4 bf16 hi and 4 bf16 lo (8 bytes each)
-__device__ __forceinline__ void split4(const u32x4 &x, u32x2 &hi, u32x2 &lo)
-{
-    const f32x4 f = __builtin_bit_cast(f32x4, x);
-    bf16x4 h, l;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { __bf16 a, b; split_bf16(f[i], a, b); h[i] = a; l[i] = b; }
-    hi = __builtin_bit_cast(u32x2, h); lo = __builtin_bit_cast(u32x2, l);
+    *kchunk = ((g.K + splits - 1) / splits + bk - 1) / bk * bk;
+    splits = (g.K + *kchunk - 1) / *kchunk;
+    if (g.ws && g.ws_used) *g.ws_used = splits;        // (the caller's consumer adds the partials itself)
+    else if (g.ws) fold[(*nfold)++] = FoldItem{g.C, g.ws, (long)g.M * g.ldc, splits, g.M, g.N, (int)g.ldc, 0, 0};
+    return splits;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -122,28 +100,16 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p, int tiles_n, int
             for (int i = 0; i < 256 && drow[i] >= 0; ++i) {
                 const long m = drow[i];
                 for (int n = tid * 4; n < p.N; n += 1024) {
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    if (p.bias) v = *(const f32x4 *)(p.bias + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = act_apply(p.act, 0.f + v[e]);       // (0 + bias: what the epilogue computes for a zero sum)
-                    if (p.C) *(f32x4 *)(p.C + m * p.ldc + n) = v;
-                    if (p.C2) {
-                        if constexpr (PREC != P_BF16) *(f32x4 *)((float *)p.C2 + m * p.ldc2 + n) = v;
-                        else *(bf16x4 *)((__bf16 *)p.C2 + m * p.ldc2 + n) = bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    }
+                    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+                    if (p.bias) bv = *(const f32x4 *)(p.bias + n);
+                    store_out4<ELT == 4>(p, m, n, f32x4{0.f, 0.f, 0.f, 0.f}, bv);          // (0 + bias: what the epilogue computes for a zero sum)
                 }
             }
         }
         return;
     }
 
-    // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous
-    // run of tiles so the N-tiles of one A panel hit the same L2 (bijective remap).
-    int bid = blockIdx.x - ndw;
-    {
-        int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
+    const int bid = xcd_tile_order(blockIdx.x - ndw, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * NT_BN;
 
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p, int tiles_n, int
         }
     };
 
-    f32x16 acc[TI][2];
+    f32x16 acc[TI][2];                          // (zeroed element by element: `= {}` compiles to another schedule of gload(0) here)
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -253,7 +219,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p, int tiles_n, int
         __syncthreads();
     }
 
-    // epilogue.  C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5): a lane owns
+    // epilogue.  By the C/D map of the 32x32 MFMA (mfma32_row) a lane owns
     // single dwords of 16 different rows, and stored straight from the registers the tile leaves the CU as 64
     // dword stores per lane (2.3 TB/s of output at best, measured with K = 64).  The tile is transposed through
     // the operand LDS instead (free after the last k step) and written as whole 512-byte rows,
@@ -274,7 +240,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p, int tiles_n, int
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        *(float *)(smem + (i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * EP + (wn * 64 + j * 32 + fr) * 4) = acc[i][j][r];
+                        *(float *)(smem + mfma32_row(r, fh, i * 32) * EP + (wn * 64 + j * 32 + fr) * 4) = acc[i][j][r];
         }
         __syncthreads();
         if (n < p.N) {
@@ -283,17 +249,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNT p, int tiles_n, int
                 const int row = (tid >> 5) + 8 * k, mt = m0 + h * ROWS + row;
                 if (mt >= nreal) break;
                 const long m = crow[h * ROWS + row];
-                f32x4 v = *(const f32x4 *)(smem + row * EP + c4 * 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = act_apply(p.act, v[e] + bv[e]);
-                if (p.C) *(f32x4 *)(p.C + m * p.ldc + n) = v;
-                if (p.C2) {
-                    if constexpr (ELT == 4) *(f32x4 *)((float *)p.C2 + m * p.ldc2 + n) = v;
-                    else {
-                        const bf16x4 hh = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                        *(bf16x4 *)((__bf16 *)p.C2 + m * p.ldc2 + n) = hh;
-                    }
-                }
+                store_out4<ELT == 4>(p, m, n, *(const f32x4 *)(smem + row * EP + c4 * 16), bv);
             }
         }
     }
@@ -316,14 +272,7 @@ void launch_gemm_nt(hipStream_t s, int prec, const GemmNT &g_in, hipEvent_t done
 {
     if (g_in.M <= 0 || g_in.N <= 0) return;
     GemmNT g = g_in;
-    {
-        // CUs of the current device, once per device
-        static int cus_of[64] = {0};
-        int dev = 0; (void)hipGetDevice(&dev);
-        int &cus = cus_of[dev & 63];
-        if (!cus) { hipDeviceProp_t prop; cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
-        if (gemm_nt_panel_applies(prec, g, cus)) { launch_gemm_nt_panel(s, g, done); return; }
-    }
+    if (gemm_nt_panel_applies(prec, g, device_cus())) { launch_gemm_nt_panel(s, g, done); return; }
     // The tiled kernels below multiply every row unless asked otherwise: gemm_nt_kernel takes the row map too (option
     // nt_rowmap_tiled; tests/test_gpu_rowmap.py runs it), but 15 % fewer rows buy it nothing inside the headline step (input
     // projections 27 -> 27 us: store-bound, and the dummy rows are written all the same; softmax products 10.3 -> 11-13)
@@ -394,9 +343,7 @@ __global__ __launch_bounds__(tn_threads(BM)) void gemm_tn_kernel(GemmTNGroup grp
     constexpr int ELT = G::ELT, PA = G::PITCH_A, PB = G::PITCH_B, TI = G::TI, TJ = G::TJ, NT = G::NT;
     constexpr int CH = 16 / ELT, RM = BM / G::WM, RN = BN / G::WN;      // rows / columns of the output a wave owns
 
-    int gi = 0;
-#pragma unroll
-    for (int i = 1; i < TN_GROUP; ++i) if ((int)blockIdx.x >= grp.first_block[i]) gi = i;
+    const int gi = tn_group_member(grp.first_block, blockIdx.x);
     // a COPY of the product's description: through a reference into the kernel-argument struct (the index is dynamic) hipcc re-loaded
     // M / N / lda / ldb with an s_load + wait in front of every global load of the K loop (ISA, round 5)
     const GemmTN p = grp.p[gi];
@@ -456,13 +403,7 @@ __global__ __launch_bounds__(tn_threads(BM)) void gemm_tn_kernel(GemmTNGroup grp
         }
     };
 
-    f32x16 acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[TI][TJ] = {};
 
     const int fr = lane & 31, fh = lane >> 5;
     gload(0);
@@ -542,7 +483,7 @@ __global__ __launch_bounds__(tn_threads(BM)) void gemm_tn_kernel(GemmTNGroup grp
         for (int i = 0; i < TI; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * RM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = mfma32_row(r, fh, m0 + wm * RM + i * 32);
                 if (m >= p.M) continue;
                 // deterministic mode: this split's partial goes to its own copy of C, folded in split order afterwards (launch_fold)
                 if (p.ws) p.ws[(long)split * p.M * p.ldc + (long)m * p.ldc + n] = acc[i][j][r];
@@ -580,12 +521,9 @@ static void launch_tn(hipStream_t s, const GemmTN *gs, int n, const FoldItem *ex
         if (splits > cap_atomic && !g.ws) splits = (int)cap_atomic;
         if (g.ws && splits > g.ws_splits) splits = g.ws_splits;
         if (splits < 1) splits = 1;
-        int kchunk = ((g.K + splits - 1) / splits + G::BK - 1) / G::BK * G::BK;
-        splits = (g.K + kchunk - 1) / kchunk;
-        grp.p[i] = g; grp.tiles_n[i] = tiles_n; grp.ntiles[i] = ntiles; grp.kchunk[i] = kchunk;
+        splits = tn_plan_splits(g, splits, G::BK, &grp.kchunk[i], fold, &nfold);
+        grp.p[i] = g; grp.tiles_n[i] = tiles_n; grp.ntiles[i] = ntiles;
         blocks += ntiles * splits;
-        if (g.ws && g.ws_used) *g.ws_used = splits;        // (the caller's consumer adds the partials itself)
-        else if (g.ws) fold[nfold++] = FoldItem{g.C, g.ws, (long)g.M * g.ldc, splits, g.M, g.N, (int)g.ldc, 0, 0};
     }
     grp.first_block[TN_GROUP] = blocks;
     if (extra) fold[nfold++] = *extra;

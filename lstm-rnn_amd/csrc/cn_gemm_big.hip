@@ -20,42 +20,14 @@
 // The epilogue transposes the accumulators through the (then free) LDS in four passes of 64 rows and writes whole
 // 1 KB rows, 16 B per lane, as gemm_nt_kernel does.
 #include "cn_internal.h"
+#include "cn_gemm_device.h"     // activation, mma32, tile order, C/D map, store_out4, buffer_resource
 #include <type_traits>
 #include <algorithm>
 #include <cstdint>
 
 namespace cn {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 namespace {
-
-__device__ __forceinline__ float big_act(int act, float x)
-{
-    // activation_functions/Logistic.cuh:33-44, Tanh.cuh:33-36 (as act_apply in cn_gemm.hip)
-    if (act == ACT_IDENTITY) return x;
-    float z = (act == ACT_TANH) ? 2.0f * x : x;
-    float s;
-    if (z < 88.722839f) s = (z > -88.722839f) ? 1.0f / (1.0f + __expf(-z)) : 0.0f;
-    else s = 1.0f;
-    return (act == ACT_TANH) ? 2.0f * s - 1.0f : s;
-}
-
-template <bool F32>
-__device__ __forceinline__ void big_mma(f32x16 &acc, const u32x4 &a, const u32x4 &b)
-{
-    if constexpr (F32) {
-        const f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[i], acc, 0, 0, 0);
-    } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
-}
 
 constexpr int BG_BM = 256, BG_BN = 256, BG_ROWB = 128;          // tile, bytes of K per tile row and k-tile
 constexpr int BG_OPER = BG_BM * BG_ROWB;                        // one operand k-tile: 32 KB
@@ -74,18 +46,9 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmNT p, int tiles_n,
     const int wm = wave >> 2, wn = wave & 3;
     const int fr = lane & 31, fh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {   // XCD-aware bijective tile order (see gemm_nt_kernel)
-        int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    // ... and inside an XCD's run, tiles in groups of BG_GROUP_M tile rows walked column by column: the ~32 workgroups
-    // an XCD runs at a time then share 4 A panels and 8 B panels in its L2 instead of 1 and 32 (B is the whole weight
-    // matrix and does not fit the 4 MB L2: with row-major order every tile row streamed it from the Infinity Cache again)
-    const int tiles_m = (p.M + BG_BM - 1) / BG_BM;
-    const int per_group = BG_GROUP_M * tiles_n, grp = bid / per_group, first_m = grp * BG_GROUP_M;
-    const int gm = min(BG_GROUP_M, tiles_m - first_m), in_grp = bid % per_group;
-    const int m0 = (first_m + in_grp % gm) * BG_BM, n0 = (in_grp / gm) * BG_BN;
+    // (groups of BG_GROUP_M tile rows: the ~32 workgroups an XCD runs at a time share 4 A panels and 8 B panels instead of 1 and 32)
+    int m0, n0;
+    grouped_tile<BG_GROUP_M, BG_BM, BG_BN>(xcd_tile_order(blockIdx.x, nwg), (p.M + BG_BM - 1) / BG_BM, tiles_n, m0, n0);
     const int nk = p.K / KB;                                    // the launcher guarantees K % KB == 0
 
     // fill: instruction q = 4 * wave + j (j < 4) of an operand covers tile rows [8q, 8q + 8); lane l brings the chunk
@@ -110,13 +73,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmNT p, int tiles_n,
         }
     };
 
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[4][2] = {};
 
     // fragment addresses inside an operand k-tile (bytes): row * 128 + ((chunk ^ swizzle(row)) << 4), chunk = 2 g + fh
     int offA[4], offB[2], swA[4], swB[2];
@@ -141,14 +98,13 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmNT p, int tiles_n,
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) big_mma<F32>(acc[i][j], a[i], b[j]);
+                for (int j = 0; j < 2; ++j) mma32<F32>(acc[i][j], a[i], b[j]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                        // next fill landed; this buffer is free for the fill after it
     }
 
-    // epilogue: four passes of 64 rows through LDS (C/D map of the 32x32 MFMA: col = lane & 31,
-    // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
+    // epilogue: four passes of 64 rows through LDS
     const int c4 = lane, n = n0 + c4 * 4;
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (p.bias && n < p.N) bv = *(const f32x4 *)(p.bias + n);
@@ -162,7 +118,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmNT p, int tiles_n,
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        *(float *)(smem + (i2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * BG_EP + (wn * 64 + j * 32 + fr) * 4) = acc[2 * (h & 1) + i2][j][r];
+                        *(float *)(smem + mfma32_row(r, fh, i2 * 32) * BG_EP + (wn * 64 + j * 32 + fr) * 4) = acc[2 * (h & 1) + i2][j][r];
         }
         __syncthreads();
         if (n < p.N) {
@@ -170,17 +126,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmNT p, int tiles_n,
             for (int k = 0; k < 8; ++k) {
                 const int row = wave + 8 * k, m = m0 + 64 * h + row;
                 if (m >= p.M) break;
-                f32x4 v = *(const f32x4 *)(smem + row * BG_EP + c4 * 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = big_act(p.act, v[e] + bv[e]);
-                if (p.C) *(f32x4 *)(p.C + (long)m * p.ldc + n) = v;
-                if (p.C2) {
-                    if constexpr (F32) *(f32x4 *)((float *)p.C2 + (long)m * p.ldc2 + n) = v;
-                    else {
-                        const bf16x4 hh = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                        *(bf16x4 *)((__bf16 *)p.C2 + (long)m * p.ldc2 + n) = hh;
-                    }
-                }
+                store_out4<F32>(p, m, n, *(const f32x4 *)(smem + row * BG_EP + c4 * 16), bv);
             }
         }
     }
@@ -246,27 +192,19 @@ __global__ __launch_bounds__(512) void gemm_nt_big8_kernel(GemmNT p, int tiles_n
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
 
-    // this workgroup's tiles: slot s of XCD x takes every nslots-th tile of the XCD's run (see gemm_nt_big_kernel)
-    const int tiles_m = (p.M + BG_BM - 1) / BG_BM, per_group = BG_GROUP_M * tiles_n;
+    // this workgroup's tiles: slot s of XCD x takes every nslots-th tile of the XCD's run (the tile order of gemm_nt_big_kernel)
+    const int tiles_m = (p.M + BG_BM - 1) / BG_BM;
     const int xcd = blockIdx.x % 8, slot = blockIdx.x / 8, nslots = gridDim.x / 8;
-    const int run_q = nwg / 8, run_r = nwg % 8;
-    const int run_n = run_q + (xcd < run_r ? 1 : 0);
-    const int run_0 = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
+    int run_0, run_n;
+    xcd_run(xcd, nwg, run_0, run_n);
     if (slot >= run_n) return;
     const int ntl = (run_n - slot + nslots - 1) / nslots;
-    auto tile_at = [&](int i, int &m0, int &n0) {
-        const int bid = run_0 + slot + i * nslots;
-        const int grp = bid / per_group, first_m = grp * BG_GROUP_M;
-        const int gm = min(BG_GROUP_M, tiles_m - first_m), in_grp = bid - grp * per_group;
-        m0 = (first_m + in_grp % gm) * BG_BM; n0 = (in_grp / gm) * BG_BN;
-    };
+    auto tile_at = [&](int i, int &m0, int &n0) { grouped_tile<BG_GROUP_M, BG_BM, BG_BN>(run_0 + slot + i * nslots, tiles_m, tiles_n, m0, n0); };
 
     // fill: instruction jj (0, 1) of this wave covers rows [8 g8, 8 g8 + 8) of a piece, g8 = 2 * wave + jj; buffer loads:
     // a 32-bit byte offset per lane off the operand's resource, the k-tile as the scalar offset.
     // pieces: 0 A-lo, 1 B-hi, 2 A-hi, 3 B-lo
-    auto resource = [](const void *base, long bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)(unsigned)(bytes > 0xfffffff0l ? 0xfffffff0l : bytes), 0x00020000);
-    };
+    auto resource = [](const void *base, long bytes) { return buffer_resource(base, bytes > 0xfffffff0l ? 0xfffffff0l : bytes); };
     const __amdgpu_buffer_rsrc_t resA = resource(p.A, (long)p.M * p.lda * 2), resB = resource(p.B, (long)p.N * p.ldb * 2);
     int prow[4][2], dst[4][2];
 #pragma unroll
@@ -335,11 +273,11 @@ __global__ __launch_bounds__(512) void gemm_nt_big8_kernel(GemmNT p, int tiles_n
             if (p.act == ACT_IDENTITY) {                          // (one uniform branch per block instead of one per element)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    *(float *)(xp + ((r & 1) ? xw_o : xw_e) + ((r & 3) + 8 * (r >> 2)) * 128) = acc[i][j][r] + biasv[j];
+                    *(float *)(xp + ((r & 1) ? xw_o : xw_e) + mfma32_row(r, 0) * 128) = acc[i][j][r] + biasv[j];
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    *(float *)(xp + ((r & 1) ? xw_o : xw_e) + ((r & 3) + 8 * (r >> 2)) * 128) = big_act(p.act, acc[i][j][r] + biasv[j]);
+                    *(float *)(xp + ((r & 1) ? xw_o : xw_e) + mfma32_row(r, 0) * 128) = act_apply(p.act, acc[i][j][r] + biasv[j]);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -352,7 +290,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big8_kernel(GemmNT p, int tiles_n
                 if (p.C2) {
                     const unsigned off = vC2 + (mrow * (unsigned)p.ldc2 + ncol) * 2u;
                     const bf16x4 hh = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hh), resC2, (int)(ok ? off : 0xfffffff0u), 0, 0);
                 }
             }
@@ -438,7 +375,7 @@ __global__ __launch_bounds__(512) void gemm_nt_big8_kernel(GemmNT p, int tiles_n
                     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     acc[ib + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, aF[i][g]), __builtin_bit_cast(bf16x8, j ? bHi[g] : bLo[g]), zero, 0, 0, 0);
                 } else {
-                    big_mma<false>(acc[ib + i][j], aF[i][g], j ? bHi[g] : bLo[g]);
+                    mma32<false>(acc[ib + i][j], aF[i][g], j ? bHi[g] : bLo[g]);
                 }
 #endif
             }
@@ -544,14 +481,11 @@ void launch_gemm_nt_big(hipStream_t s, int prec, const GemmNT &g, hipEvent_t don
     const bool f32 = prec != P_BF16;
     const int tiles_m = (g.M + BG_BM - 1) / BG_BM, tiles_n = (g.N + BG_BN - 1) / BG_BN, nwg = tiles_m * tiles_n;
     static DeviceOnce attr_once;
-    static int cus = 0;
     if (attr_once.first()) {
         (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BG_LDS);
         (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BG_LDS);
         (void)hipFuncSetAttribute((const void *)gemm_nt_big8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, B8_LDS);
         (void)hipFuncSetAttribute((const void *)gemm_nt_big8_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, B8_LDS);
-        int dev = 0; (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     }
     const bool no8 = opt().no_big8;
     // the persistent kernel: 32-bit byte offsets into every operand, whole 16-byte stores, and at least a dozen k-tiles per tile
@@ -560,14 +494,15 @@ void launch_gemm_nt_big(hipStream_t s, int prec, const GemmNT &g, hipEvent_t don
     // tools/probe/gemm_bench, us non-persistent / persistent: 51 200 x 2048 203.4 / 193.8, 35 200 x 2048 138.8 / 134.9,
     // 51 200 x 8000 710.8 / 652.7; reading B's 15 600 x 2048, 488 tiles: 51.5 / 54.7 and stays)
     const int min_k = opt().big8_min_k > 0 ? (int)opt().big8_min_k : (nwg >= 1000 ? 8 * 64 : 12 * 64);
-    const bool fits = (unsigned long long)g.M * g.lda * 2 < 0xfffffff0ull && (unsigned long long)g.N * g.ldb * 2 < 0xfffffff0ull &&
-                      (!g.C || ((unsigned long long)g.M * g.ldc * 4 < 0xfffffff0ull && g.ldc % 4 == 0 && (uintptr_t)g.C % 16 == 0)) &&
-                      (!g.C2 || ((unsigned long long)g.M * g.ldc2 * 2 < 0xfffffff0ull && g.ldc2 % 4 == 0 && (uintptr_t)g.C2 % 8 == 0)) &&
+    // (unlike gemm_nt_mid_applies / gemm_nt_panel_applies, this does not ask for 16-byte aligned rows of A and B)
+    const unsigned long long lim = 0xfffffff0ull;
+    const bool fits = rows_fit(g.M, g.lda, 2, lim) && rows_fit(g.N, g.ldb, 2, lim) &&
+                      (!g.C || rows_fit(g.M, g.ldc, 4, lim)) && (!g.C2 || rows_fit(g.M, g.ldc2, 2, lim)) && nt_out_rows_aligned(g) &&
                       g.N % 4 == 0 && (g.C || g.C2) &&
                       g.K >= min_k;
     if (f32) hipExtLaunchKernelGGL(gemm_nt_big_kernel<true>, dim3(nwg), dim3(512), BG_LDS, s, nullptr, done, 0, g, tiles_n, nwg);
     else if (!no8 && fits) {
-        const int grid = std::min(nwg, std::max(8, cus / 8 * 8)) / 8 * 8;
+        const int grid = std::min(nwg, std::max(8, device_cus() / 8 * 8)) / 8 * 8;
         if (g.C && g.C2) hipExtLaunchKernelGGL(gemm_nt_big8_kernel<2>, dim3(grid), dim3(512), B8_LDS, s, nullptr, done, 0, g, tiles_n, nwg);
         else             hipExtLaunchKernelGGL(gemm_nt_big8_kernel<1>, dim3(grid), dim3(512), B8_LDS, s, nullptr, done, 0, g, tiles_n, nwg);
     }

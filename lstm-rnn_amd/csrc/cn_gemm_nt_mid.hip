@@ -15,14 +15,11 @@
 // front of them).  The epilogue transposes the accumulators through the (then free) LDS in two passes of 64 rows and writes
 // whole 1 KB rows, 16 B per lane, bias / activation / operand-type copy on the way out, as gemm_nt_big_kernel does.
 #include "cn_internal.h"
+#include "cn_gemm_device.h"     // tile order, C/D map, store_out4, buffer_resource, fragment clobber list
 #include <algorithm>
 #include <cstdint>
 
 namespace cn {
-
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
@@ -35,41 +32,20 @@ constexpr int NM_EP = NM_BN * 4 + 16;                           // epilogue stag
 constexpr int NM_GROUP_M = 8;                                   // tile rows per L2 group
 static_assert(64 * NM_EP <= NM_LDS, "epilogue staging does not fit");
 
-__device__ __forceinline__ float mid_act(int act, float x)
-{
-    // activation_functions/Logistic.cuh:33-44, Tanh.cuh:33-36 (as act_apply in cn_gemm.hip)
-    if (act == ACT_IDENTITY) return x;
-    float z = (act == ACT_TANH) ? 2.0f * x : x;
-    float s;
-    if (z < 88.722839f) s = (z > -88.722839f) ? 1.0f / (1.0f + __expf(-z)) : 0.0f;
-    else s = 1.0f;
-    return (act == ACT_TANH) ? 2.0f * s - 1.0f : s;
-}
-
 __global__ __launch_bounds__(256, 2) void gemm_nt_mid_kernel(GemmNT p, int tiles_n, int nwg)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;       // wave = wn: its 64 columns of the tile
     const int fr = lane & 31, fh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {   // XCD-aware bijective tile order (see gemm_nt_kernel)
-        int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    const int tiles_m = (p.M + NM_BM - 1) / NM_BM;
-    const int per_group = NM_GROUP_M * tiles_n, grp = bid / per_group, first_m = grp * NM_GROUP_M;
-    const int gm = min(NM_GROUP_M, tiles_m - first_m), in_grp = bid % per_group;
-    const int m0 = (first_m + in_grp % gm) * NM_BM, n0 = (in_grp / gm) * NM_BN;
+    int m0, n0;
+    grouped_tile<NM_GROUP_M, NM_BM, NM_BN>(xcd_tile_order(blockIdx.x, nwg), (p.M + NM_BM - 1) / NM_BM, tiles_n, m0, n0);
     const int nk = p.K / NM_BK;                                 // the launcher guarantees K % 32 == 0
 
     // fill: instruction q of an operand covers tile rows [16 q, 16 q + 16); lane l brings the chunk that belongs in LDS slot l & 3
     // of row 16 q + (l >> 2).  A: 8 instructions (wave w: 2w, 2w + 1), B: 16 (wave w: 4w .. 4w + 3).  Rows past the edge: clamped
     // (their results are not stored).
-    auto resource = [](const void *base, long bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t resA = resource(p.A, (long)p.M * p.lda * 2), resB = resource(p.B, (long)p.N * p.ldb * 2);
+    const __amdgpu_buffer_rsrc_t resA = buffer_resource(p.A, (long)p.M * p.lda * 2), resB = buffer_resource(p.B, (long)p.N * p.ldb * 2);
     unsigned voffA[2], voffB[4];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -92,13 +68,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_mid_kernel(GemmNT p, int tiles
             __builtin_amdgcn_raw_ptr_buffer_load_lds(resB, (__attribute__((address_space(3))) void *)(lb + j * 1024), 16, voffB[j], koff, 0, 0);
     };
 
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[4][2] = {};
 
     // fragment addresses inside a stage (bytes): row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4), chunk = 2 s + fh for k-step s;
     // the second k-step's address is the first one's with bit 5 flipped
@@ -157,16 +127,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_mid_kernel(GemmNT p, int tiles
               [c20] "+v"(acc[2][0]), [c21] "+v"(acc[2][1]), [c30] "+v"(acc[3][0]), [c31] "+v"(acc[3][1])
             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [b0] "v"(b0), [b1] "v"(b1),
               [a0x] "v"(a0x), [a1x] "v"(a1x), [a2x] "v"(a2x), [a3x] "v"(a3x), [b0x] "v"(b0x), [b1x] "v"(b1x)
-            : "memory", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215",
-              "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231",
-              "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247");
+            : "memory", CN_FRAG_V200_247);
     }
     // (the accumulators were last written inside an asm statement: the compiler's hazard recognizer has not seen those MFMAs;
     // the fills issued past the end must not outlive the stage they target, which the epilogue reuses)
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 
-    // epilogue: two passes of 64 rows through LDS (C/D map of the 32x32 MFMA: col = lane & 31,
-    // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
+    // epilogue: two passes of 64 rows through LDS
     const int c4 = lane, n = n0 + c4 * 4;
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (p.bias && n < p.N) bv = *(const f32x4 *)(p.bias + n);
@@ -179,21 +146,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_mid_kernel(GemmNT p, int tiles
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    *(float *)(smem + (i2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * NM_EP + (wave * 64 + j * 32 + fr) * 4) = acc[2 * h + i2][j][r];
+                    *(float *)(smem + mfma32_row(r, fh, i2 * 32) * NM_EP + (wave * 64 + j * 32 + fr) * 4) = acc[2 * h + i2][j][r];
         __syncthreads();
         if (n < p.N) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int row = wave + 4 * k, m = m0 + 64 * h + row;
                 if (m >= p.M) break;
-                f32x4 v = *(const f32x4 *)(smem + row * NM_EP + c4 * 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = mid_act(p.act, v[e] + bv[e]);
-                if (p.C) *(f32x4 *)(p.C + (long)m * p.ldc + n) = v;
-                if (p.C2) {
-                    const bf16x4 hh = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-                    *(bf16x4 *)((__bf16 *)p.C2 + (long)m * p.ldc2 + n) = hh;
-                }
+                store_out4<false>(p, m, n, *(const f32x4 *)(smem + row * NM_EP + c4 * 16), bv);
             }
         }
     }
@@ -211,8 +171,9 @@ bool gemm_nt_mid_applies(int prec, const GemmNT &g)
     const bool off = opt().no_nt_mid;
     if (off || prec != P_BF16) return false;
     if (g.K % NM_BK != 0 || g.K < 4 * NM_BK || g.K >= 768 || g.N > 4096) return false;
-    if (g.N % 4 != 0 || (g.C && (g.ldc % 4 || (uintptr_t)g.C % 16)) || (g.C2 && (g.ldc2 % 4 || (uintptr_t)g.C2 % 8)) || (uintptr_t)g.A % 16 || (uintptr_t)g.B % 16 || (g.bias && (uintptr_t)g.bias % 16) || !(g.C || g.C2) || g.lda % 8 || g.ldb % 8) return false;
-    if ((unsigned long long)g.M * g.lda * 2 >= 0xfffffff0ull || (unsigned long long)g.N * g.ldb * 2 >= 0xfffffff0ull) return false;
+    if (g.N % 4 != 0 || !(g.C || g.C2) || !nt_out_rows_aligned(g) || (g.bias && (uintptr_t)g.bias % 16)) return false;
+    if (!rows_aligned(g.A, g.lda, 2, 16) || !rows_aligned(g.B, g.ldb, 2, 16)) return false;
+    if (!rows_fit(g.M, g.lda, 2, 0xfffffff0ull) || !rows_fit(g.N, g.ldb, 2, 0xfffffff0ull)) return false;
     // (from 1000 tiles on and K >= 512 the persistent 256 x 256 kernel takes the product: launch_gemm_nt_big)
     const long tiles = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
     return tiles >= opt().nt_mid_min_tiles && (tiles < 1000 || g.K < 512);

@@ -32,16 +32,11 @@
 // 25.5 -> 20-21 us each, the input projections 27 -> 28-33, the softmax products 10.3 -> 12-13: the dispatch takes K >= 512 on at
 // most two column tiles (options nt_panel_min_ktiles / nt_panel_max_ntiles).  Reading B (N = 512, K = 2048): gemm_wide -11 %.
 #include "cn_internal.h"
+#include "cn_gemm_device.h"     // vector types, buffer_resource
 #include <algorithm>
 #include <cstdint>
 
 namespace cn {
-
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 namespace {
 
@@ -57,6 +52,7 @@ constexpr int NP_ROWS = NP_BIAS + NP_MAX_N * 4;                 // the panel's 6
 constexpr int NP_STG = NP_ROWS + 1024;                          // output staging: 32 rows x 64 columns of fp32 per multiplying wave
 constexpr int NP_STG_WAVE = 32 * 256;
 constexpr int NP_LDS = NP_STG + 4 * NP_STG_WAVE;                // 160 KB: one workgroup per CU
+static_assert(NP_MAX_N % NP_BN == 0 && NP_LDS <= 160 * 1024, "the bias of whole column tiles, and a layout that fits a CU's LDS");
 
 __global__ __launch_bounds__(512) void gemm_nt_panel_kernel(GemmNT p, int tiles_n, int nk, int no_touch)
 {
@@ -75,11 +71,8 @@ __global__ __launch_bounds__(512) void gemm_nt_panel_kernel(GemmNT p, int tiles_
     if (tid < NP_BM) ((int *)(smem + NP_ROWS))[tid] = m0 + tid < nreal ? (p.rowmap ? p.rowmap[m0 + tid] : m0 + tid) : -1;
     __syncthreads();
 
-    auto resource = [](const void *base, long bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t resA = resource(p.A, (long)p.M * p.lda * 2), resB = resource(p.B, (long)p.N * p.ldb * 2);
-    const __amdgpu_buffer_rsrc_t resC = resource(p.C, p.C ? (long)p.M * p.ldc * 4 : 0), resC2 = resource(p.C2, p.C2 ? (long)p.M * p.ldc2 * 2 : 0);
+    const __amdgpu_buffer_rsrc_t resA = buffer_resource(p.A, (long)p.M * p.lda * 2), resB = buffer_resource(p.B, (long)p.N * p.ldb * 2);
+    const __amdgpu_buffer_rsrc_t resC = buffer_resource(p.C, p.C ? (long)p.M * p.ldc * 4 : 0), resC2 = buffer_resource(p.C2, p.C2 ? (long)p.M * p.ldc2 * 2 : 0);
 
     // fill: piece q of an operand covers its tile rows [8 q, 8 q + 8); lane l brings the chunk that belongs in LDS slot l & 7 of
     // row 8 q + (l >> 3).  A: 8 pieces (loader w: 2w, 2w + 1), B: 32 (loader w: 8w .. 8w + 7).  Rows past the edge: clamped (their
@@ -109,13 +102,7 @@ __global__ __launch_bounds__(512) void gemm_nt_panel_kernel(GemmNT p, int tiles_
             __builtin_amdgcn_raw_ptr_buffer_load_lds(resB, (__attribute__((address_space(3))) void *)(lb + j * 1024), 16, voffB[j], koff, 0, 0);
     };
 
-    f32x16 acc[2][2];                                           // [32 rows of the panel][32 columns of the wave's 64]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[2][2] = {};                                      // [32 rows of the panel][32 columns of the wave's 64]
 
     // fragment addresses inside a stage (bytes): row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4) with chunk = 2 g + fh for k-group g:
     // = base ^ (g << 5), base = row * 128 + ((fh ^ (s & 1)) << 4) + ((s >> 1) << 5), s = (row >> 1) & 7 (the same for every
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(512) void gemm_nt_panel_kernel(GemmNT p, int tiles_
     // dword per 128-byte line, loaded into a spare LDS word by LDS-DMA (no destination register to keep alive, nothing the
     // compiler sees).  Waves 1 .. 3: this workgroup's share of the whole of B, once, at the start (block ids 8 apart share an
     // XCD under round-robin placement -- speed only); wave 0: the panel's k-tiles NP_TOUCH_A ahead, one instruction per k-tile.
-    auto words = [](const void *base, long bytes) {            // the same descriptor as resource(), as four dwords for the asm
+    auto words = [](const void *base, long bytes) {            // the same descriptor as buffer_resource(), as four dwords for the asm
         const unsigned long long a = (unsigned long long)(uintptr_t)base;
         return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, (unsigned)bytes, 0x00020000u};
     };
@@ -297,7 +284,7 @@ __global__ __launch_bounds__(512) void gemm_nt_panel_kernel(GemmNT p, int tiles_
 }  // namespace
 
 // bf16 products with the identity activation whose row panels of 64 are at most a round and a half of the chip's CUs (beyond that
-// the tiled kernels' rounds even out and their larger tiles re-read less), K in whole k-tiles of 64, N <= 2048, operands and
+// the tiled kernels' rounds even out and their larger tiles re-read less), K in whole k-tiles of 64, N <= NP_MAX_N = 1792, operands and
 // outputs addressable with 31-bit byte offsets, 16-byte rows.
 bool gemm_nt_panel_applies(int prec, const GemmNT &g, int cus)
 {
@@ -307,9 +294,10 @@ bool gemm_nt_panel_applies(int prec, const GemmNT &g, int cus)
     // operands; tools/gemm_in_step.sh): K = 1024, N = 256: 25.5 -> 21-23 us; N = 1024, K = 256 (61 MB of result, store-bound either
     // way): 27 -> 28-33 us; N = 192 / 256, K = 256 / 192: 10.3 -> 12-13 us.
     if (g.K / NP_BK < opt().nt_panel_min_ktiles || (g.N + NP_BN - 1) / NP_BN > opt().nt_panel_max_ntiles) return false;
-    if ((g.C && (g.ldc % 4 || (uintptr_t)g.C % 16)) || (g.C2 && (g.ldc2 % 4 || (uintptr_t)g.C2 % 8)) || (uintptr_t)g.A % 16 || (uintptr_t)g.B % 16 || g.lda % 8 || g.ldb % 8) return false;
-    const unsigned long long lim = 0x7fff0000ull, rows = (unsigned long long)g.M + NP_BM;
-    if (rows * g.lda * 2 >= lim || (unsigned long long)g.N * g.ldb * 2 >= lim || (g.C && rows * g.ldc * 4 >= lim) || (g.C2 && rows * g.ldc2 * 2 >= lim)) return false;
+    if (!nt_out_rows_aligned(g) || !rows_aligned(g.A, g.lda, 2, 16) || !rows_aligned(g.B, g.ldb, 2, 16)) return false;
+    const unsigned long long lim = 0x7fff0000ull;          // 31-bit byte offsets, counted over M + one panel of rows
+    const long rows = (long)g.M + NP_BM;
+    if (!rows_fit(rows, g.lda, 2, lim) || !rows_fit(g.N, g.ldb, 2, lim) || (g.C && !rows_fit(rows, g.ldc, 4, lim)) || (g.C2 && !rows_fit(rows, g.ldc2, 2, lim))) return false;
     // one round of workgroups: the (estimated) real rows in panels of 64 must not outnumber the CUs -- a second round of a
     // few panels doubles the launch (seen on the headline: 281 panels on 256 CUs, every product slower than the tiled kernel)
     const long rows_est = g.rowmap && g.m_est > 0 ? std::min(g.m_est, g.M) : g.M, panels = (rows_est + NP_BM - 1) / NP_BM;

@@ -20,15 +20,11 @@
 // on side by side walk the same frames: a panel is fetched into that L2 once and served to the tiles of its row / column from
 // there.  fp32 atomics into the pre-zeroed gradient like gemm_tn_kernel.
 #include "cn_internal.h"
+#include "cn_gemm_device.h"     // vector types, buffer_resource, C/D map, fragment clobber list, tn_group_member
 #include <algorithm>
 #include <cstdint>
 
 namespace cn {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
 
@@ -47,9 +43,7 @@ struct TnBigGroup {
 __global__ __launch_bounds__(512) void gemm_tn_big_kernel(TnBigGroup grp)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int gi = 0;
-#pragma unroll
-    for (int i = 1; i < TB_GROUP; ++i) if ((int)blockIdx.x >= grp.first_block[i]) gi = i;
+    const int gi = tn_group_member(grp.first_block, blockIdx.x);
     const GemmTN p = grp.p[gi];
     const int ntiles = grp.ntiles[gi], tiles_n = grp.tiles_n[gi], kchunk = grp.kchunk[gi];
     const int local = blockIdx.x - grp.first_block[gi];
@@ -71,10 +65,7 @@ __global__ __launch_bounds__(512) void gemm_tn_big_kernel(TnBigGroup grp)
     // fill: wave w brings tile rows 4w .. 4w+3 of both operands, two rows per instruction; lane l of instruction j brings the
     // chunk that belongs in LDS slot l & 31 of row 4w + 2j + (l >> 5).  Buffer loads: a 32-bit byte offset per lane off a
     // resource that ends behind frame kend - 1 (the launcher checks that the operands are smaller than 4 GB).
-    auto resource = [](const void *base, long bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const __amdgpu_buffer_rsrc_t resA = resource(p.A, (long)kend * p.lda * 2), resB = resource(p.B, (long)kend * p.ldb * 2);
+    const __amdgpu_buffer_rsrc_t resA = buffer_resource(p.A, (long)kend * p.lda * 2), resB = buffer_resource(p.B, (long)kend * p.ldb * 2);
     unsigned voffA[2], voffB[2];
     const unsigned stepA = (unsigned)(TB_BK * p.lda * 2), stepB = (unsigned)(TB_BK * p.ldb * 2);
 #pragma unroll
@@ -95,7 +86,7 @@ __global__ __launch_bounds__(512) void gemm_tn_big_kernel(TnBigGroup grp)
         }
     };
 
-    f32x16 acc[4][2];
+    f32x16 acc[4][2];                                          // (zeroed element by element: `= {}` moves an instruction of the prologue)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -183,13 +174,13 @@ __global__ __launch_bounds__(512) void gemm_tn_big_kernel(TnBigGroup grp)
             : [c00] "+v"(acc[0][0]), [c01] "+v"(acc[0][1]), [c10] "+v"(acc[1][0]), [c11] "+v"(acc[1][1]),
               [c20] "+v"(acc[2][0]), [c21] "+v"(acc[2][1]), [c30] "+v"(acc[3][0]), [c31] "+v"(acc[3][1])
             : [pA0] "v"(adA[0]), [pA1] "v"(adA[1]), [pA2] "v"(adA[2]), [pA3] "v"(adA[3]), [pB0] "v"(adB[0]), [pB1] "v"(adB[1])
-            : "memory", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247");
+            : "memory", CN_FRAG_V200_247);
     }
     // (the accumulators were last written inside an asm statement: the compiler's hazard recognizer has not seen those MFMAs)
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the fills issued past the end (zeros) must not outlive the workgroup's LDS
 
-    // split-K: fp32 atomics (C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
+    // split-K: fp32 atomics
     const int fr = lane & 31, fh = lane >> 5;
     const bool whole = m0 + TB_BM <= p.M;
     // deterministic mode: this split's partial is stored to its own copy of C and folded in split order afterwards (launch_fold)
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(512) void gemm_tn_big_kernel(TnBigGroup grp)
             float *c0 = cbase + (long)mb * p.ldc + n;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int dm = (r & 3) + 8 * (r >> 2);
+                const int dm = mfma32_row(r, 0);                // (4 fh is in mb)
                 if (whole || mb + dm < p.M) {
                     if (p.ws) c0[(long)dm * p.ldc] = acc[i][j][r];
                     else atomicAdd(c0 + (long)dm * p.ldc, acc[i][j][r]);
@@ -223,9 +214,9 @@ bool gemm_tn_big_can(int prec, const GemmTN &g)
 {
     const bool off = opt().no_big_tn;
     if (off || prec != P_BF16) return false;
-    if (g.lda % 8 || g.ldb % 8 || g.M % 8 || g.N % 8 || (uintptr_t)g.A % 16 || (uintptr_t)g.B % 16) return false;
+    if (!rows_aligned(g.A, g.lda, 2, 16) || !rows_aligned(g.B, g.ldb, 2, 16) || g.M % 8 || g.N % 8) return false;
     if (g.K < 4096 || g.M < 512) return false;
-    if ((unsigned long long)g.K * g.lda * 2 >= 0xfffffff0ull || (unsigned long long)g.K * g.ldb * 2 >= 0xfffffff0ull) return false;   // 32-bit fill offsets
+    if (!rows_fit(g.K, g.lda, 2, 0xfffffff0ull) || !rows_fit(g.K, g.ldb, 2, 0xfffffff0ull)) return false;   // 32-bit fill offsets
     const int rem = g.N % TB_BN;
     return g.N >= 192 && (rem == 0 || rem >= 192);
 }
@@ -242,12 +233,8 @@ void launch_gemm_tn_big_group(hipStream_t s, const GemmTN *gs, int n, int cu_bud
 {
     if (n <= 0) { if (extra) launch_fold(s, extra, 1); return; }
     static DeviceOnce attr_once;
-    static int cus = 256;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void *)gemm_tn_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
-        int dev = 0; (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    }
+    if (attr_once.first()) (void)hipFuncSetAttribute((const void *)gemm_tn_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS);
+    const int cus = device_cus();
     TnBigGroup grp{};
     FoldItem fold[TB_GROUP + 1]; int nfold = 0;
     long all_tiles = 0;
@@ -272,12 +259,9 @@ void launch_gemm_tn_big_group(hipStream_t s, const GemmTN *gs, int n, int cu_bud
         if (!g.ws) splits = (int)std::min<long>(splits, cap_atomic);
         else splits = std::min(splits, g.ws_splits);
         splits = std::min(splits, std::max(1, g.K / (16 * TB_BK)));
-        int kchunk = ((g.K + splits - 1) / splits + TB_BK - 1) / TB_BK * TB_BK;
-        splits = (g.K + kchunk - 1) / kchunk;
-        grp.p[i] = g; grp.tiles_n[i] = tiles_n; grp.ntiles[i] = ntiles; grp.kchunk[i] = kchunk; grp.splits[i] = splits;
+        splits = tn_plan_splits(g, splits, TB_BK, &grp.kchunk[i], fold, &nfold);
+        grp.p[i] = g; grp.tiles_n[i] = tiles_n; grp.ntiles[i] = ntiles; grp.splits[i] = splits;
         blocks += 8 * ((ntiles * splits + 7) / 8);
-        if (g.ws && g.ws_used) *g.ws_used = splits;
-        else if (g.ws) fold[nfold++] = FoldItem{g.C, g.ws, (long)g.M * g.ldc, splits, g.M, g.N, (int)g.ldc, 0, 0};
     }
     grp.first_block[TB_GROUP] = blocks;
     hipLaunchKernelGGL(gemm_tn_big_kernel, dim3(blocks), dim3(512), TB_LDS, s, grp);

@@ -111,6 +111,18 @@ constexpr int DET_MAX_SPLITS = 8;
 struct FoldItem { float *dst; float *part; long stride; int nparts, rows, cols, ld, accumulate, clear; };
 constexpr int FOLD_MAX = 4;
 void launch_fold(hipStream_t s, const FoldItem *items, int n);
+// ---- what the GEMM launchers share (cn_gemm.hip) ----
+int device_cus();                                        // CUs of the current device (looked up once per device)
+// eligibility of the LDS-DMA kernels: rows of `elt`-byte elements, `ld` elements apart from `base`, start on multiples of `align` bytes
+bool rows_aligned(const void *base, long ld, int elt, int align);
+// ... `rows` such rows end below byte offset `limit` (what a 32-bit buffer offset reaches)
+bool rows_fit(long rows, long ld, int elt, unsigned long long limit);
+// ... the result rows take whole 16-byte stores of four columns: fp32 C and / or bf16 C2 (a null pointer passes)
+bool nt_out_rows_aligned(const GemmNT &g);
+// The tail of split-K planning, the same for every gemm_tn launcher: cut K into about `splits` chunks of whole k-tiles (bk frames),
+// return the number of chunks that makes (*kchunk frames each), and hand the deterministic mode its count: to *g.ws_used, or as a
+// fold of the partials appended to fold[*nfold].  (How many splits to ASK for is each launcher's own policy.)
+int tn_plan_splits(const GemmTN &g, int splits, int bk, int *kchunk, FoldItem *fold, int *nfold);
 // `done`: optional event that completes with the kernel itself (hipExtLaunchKernelGGL stop event): a fork point for
 // another stream without a marker packet on this stream (an hipEventRecord between two kernels costs the second one ~7 us)
 void launch_gemm_nt(hipStream_t s, int prec, const GemmNT &g, hipEvent_t done = nullptr);
