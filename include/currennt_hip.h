@@ -388,6 +388,37 @@ int  cn_adam_update_all(cn_ctx *ctx, float learning_rate, float beta1, float bet
  * learning rate of its own passes that), else CN_ERR_STATE; cn_ctx_accumulate_updates is refused while it is armed.   [async] */
 int  cn_ctx_arm_adam(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step);
 
+/* ---- Dropout on the connections between layers (no counterpart in the reference; Pham et al. 2014, Zaremba et al. 2014) -------
+ * Dropout belongs to a trainable layer and acts on that layer's INPUT, the connections from the preceding layer: the layer's input
+ * products (forward, and the input-weight gradient) read a masked, rescaled copy of the preceding layer's outputs, and the error
+ * handed back to the preceding layer passes the same mask.  The preceding layer's own outputs, its recurrence and CN_BUF_OUTPUTS
+ * are untouched; nothing inside a time loop drops.
+ *
+ * The mask.  rate in [0, 1).  n = t*PS + ps is the frame in the reference layout (PS = parallel_sequences as given to the input
+ * layer), i the unit of the preceding layer in the reference layout, 0 <= i < P (blstm: the forward units, then the backward ones).
+ *      (w0,w1,w2,w3) = Philox4x32-10( counter = (i >> 2, n, pass_lo, pass_hi),
+ *                                     key     = ((seed_lo + ordinal) mod 2^32, seed_hi) )
+ *      keep(n,i)     = w[i & 3] >= thr        thr   = (uint32) floor((double)rate * 2^32)
+ *      x'(n,i)       = keep ? x(n,i) * scale : 0        scale = (float)(1.0 / (1.0 - (double)rate))
+ * (Philox4x32-10 of Salmon et al. 2011: multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten rounds; counter
+ * and key words in the order written, _lo / _hi the halves of the 64-bit values.)  `ordinal` is the index of the dropping layer in
+ * the context's creation order, the input layer being 0.  `seed` and `pass` are the caller's: the library keeps no clock, as with
+ * Adam's `step`.  The product is ONE fp32 multiplication, then rounded to the operand type (CN_PREC_BF16: to nearest even;
+ * CN_PREC_F32 / CN_PREC_BF16X3: kept as fp32).  Backward: e'(n,i) = keep ? e(n,i) * scale : 0, one fp32 multiplication, the same
+ * mask.  The mask is a function of (seed, pass, ordinal, n, i, rate) alone: not of any padding, the precision mode or the kernels
+ * chosen.
+ *
+ * With dropout disabled, or every rate 0, the library launches exactly what it launches without these calls and allocates
+ * nothing for them. */
+/* The JSON "dropout" of a layer.  lstm, blstm, feedforward_* and softmax layers; any other kind, and a rate outside [0, 1):
+ * CN_ERR_BAD_ARG.  May be called between fractions.  The first non-zero rate allocates the layer's masked operand copy (the size
+ * of the preceding layer's operand copy); rate 0 takes the layer off the dropout path again. */
+int  cn_layer_set_dropout(cn_layer *layer, float rate);
+/* Whether the forward passes that follow drop (enable != 0), and with which (seed, pass), until the next call; a fresh context
+ * does not.  Each layer records in its forward pass whether it dropped and with which key, rate included, and its backward pass
+ * uses that record: a call between forward and backward cannot tear a step. */
+int  cn_ctx_set_dropout_pass(cn_ctx *ctx, int enable, uint64_t seed, uint64_t pass);
+
 #ifdef __cplusplus
 }
 #endif

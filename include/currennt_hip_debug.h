@@ -73,6 +73,11 @@ int cn_dbg_prefetch_hits(cn_ctx *ctx, int *hits);
 int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
                float *loss_out, float *err_out);
 
+/* The masked operand copy a dropping layer's input products read (include/currennt_hip.h, section Dropout), as its last forward
+ * pass left it: reference layout [T * PS][P], P the preceding layer's size, widened to float; count = T * PS * P.  CN_ERR_STATE
+ * when that pass did not drop.  [sync] */
+int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count);
+
 #ifdef __cplusplus
 }
 #endif

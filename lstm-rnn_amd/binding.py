@@ -42,6 +42,8 @@ EXPORTS = [
     "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits", "cn_dbg_gemm_tn_group", "cn_dbg_fold",
     # the CTC post output layer: include/currennt_hip.h and its kernel-level hook in include/currennt_hip_debug.h
     "cn_layer_set_label_sequences", "cn_dbg_ctc",
+    # include/currennt_hip.h, section Dropout, and its hook in include/currennt_hip_debug.h
+    "cn_layer_set_dropout", "cn_ctx_set_dropout_pass", "cn_dbg_dropout_input",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -179,6 +181,9 @@ def load_library():
     L.cn_dbg_prefetch_hits.argtypes = [vp, C.POINTER(C.c_int)]
     L.cn_layer_set_label_sequences.argtypes = [vp, vp, vp, ci]
     L.cn_dbg_ctc.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+    L.cn_layer_set_dropout.argtypes = [vp, cf]
+    L.cn_ctx_set_dropout_pass.argtypes = [vp, ci, C.c_uint64, C.c_uint64]
+    L.cn_dbg_dropout_input.argtypes = [vp, vp, C.c_size_t]
     _LIB = L
     return L
 

@@ -174,6 +174,11 @@ struct cn_ctx {
     int family = FAMILY_NONE;
     float *adam_v = nullptr;              // Adam's second moments, [total] like a part of the arena, zeroed; allocated at the first Adam call
 
+    // cn_ctx_set_dropout_pass: whether the forward passes that follow drop, and the caller's (seed, pass) of their masks
+    bool drop_enable = false;
+    uint64_t drop_seed = 0, drop_pass = 0;
+    int next_ordinal = 0;                 // layers created so far (cn_layer::ordinal)
+
     // parameter arena [weights | weightUpdates | weightDeltas]
     bool finalized = false;
     float *arena = nullptr;
@@ -219,6 +224,13 @@ struct cn_layer {
     float *err = nullptr;                 // [maxN][Lp] outputErrors
     float *stage_in = nullptr;            // input layer: [maxN][size] fp32 as loaded
     float *targets = nullptr;             // sse: [maxN][size]
+
+    // dropout on this layer's input (include/currennt_hip.h, section Dropout)
+    int ordinal = 0;                      // index in the context's creation order: part of the mask's key
+    float drop_rate = 0.f;                // cn_layer_set_dropout
+    void *in_drop = nullptr;              // [maxN][Pp] masked operand copy of prev->out_op, allocated at the first non-zero rate
+    bool dropped = false;                 // the last forward pass dropped ...
+    DropArgs drop{};                      // ... with this key: what its backward pass masks the handed-back error with
 
     // lstm internals
     float *acts = nullptr, *cell = nullptr, *th = nullptr;
@@ -859,11 +871,42 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule
 // armed update without a communicator: unpack + update + operand copies ride on ONE launch behind the gradient GEMMs
 bool armed_fused(const cn_layer *l) { return l->ctx->armed && !l->ctx->has_comm(); }
 
+// ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
+// The operand a layer's input products read in this forward pass: the preceding layer's operand copy, or -- when the pass drops --
+// the masked copy, written here in front of K1.  The layer records whether it dropped and with which key: its backward pass
+// (the input-weight gradient's operand, the mask of the error it hands back) goes by the record, not by the context's state then.
+const void *forward_input(cn_layer *l)
+{
+    cn_ctx *c = l->ctx;
+    l->dropped = c->drop_enable && l->drop_rate > 0.f;
+    if (!l->dropped) return l->prev->out_op;
+    DropArgs &a = l->drop;
+    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.P = l->P; a.Pp = l->Pp;
+    a.prevH = l->prev->lstm ? l->prev->H : 0; a.prevHp = l->prev->lstm ? l->prev->Hp : 0; a.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
+    a.k0 = (uint32_t)c->drop_seed + (uint32_t)l->ordinal; a.k1 = (uint32_t)(c->drop_seed >> 32);
+    a.pass_lo = (uint32_t)c->drop_pass; a.pass_hi = (uint32_t)(c->drop_pass >> 32);
+    a.thr = (uint32_t)std::floor((double)l->drop_rate * 4294967296.0);
+    a.scale = (float)(1.0 / (1.0 - (double)l->drop_rate));
+    Timed tm(c, KC_OTHER);
+    launch_dropout_fwd(c->stream, c->f32, a, l->prev->out_op, l->in_drop);
+    return l->in_drop;
+}
+// the same operand for the input-weight gradient of the backward pass
+const void *backward_input(const cn_layer *l) { return l->dropped ? l->in_drop : l->prev->out_op; }
+// behind K8 on the main stream: the error handed to the preceding layer passes the forward pass's mask
+void mask_handed_back_error(cn_layer *l)
+{
+    if (!l->dropped) return;
+    Timed tm(l->ctx, KC_OTHER);
+    launch_dropout_bwd(l->ctx->stream, l->drop, l->prev->err);
+}
+
 void lstm_forward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     const int R = l->dirs * 4 * l->Hp;
     repack(l);
+    const void *x = forward_input(l);
     // bf16 mode, two-sequence forward kernels: the pre-activations leave the product as bf16 (8 instead of 16 bytes per unit and
     // frame -- the product is bound by that store: 72 of the 88 MB a headline launch moved) and the recurrent kernel widens them
     bool pre16 = false;
@@ -874,7 +917,7 @@ void lstm_forward(cn_layer *l)
     {   // K1: gate pre-activations of all frames, 4 gates x dirs packed into one N = R product
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
-        g.A = l->prev->out_op; g.lda = l->Pp; g.B = l->Win; g.ldb = l->Pp;
+        g.A = x; g.lda = l->Pp; g.B = l->Win; g.ldb = l->Pp;
         g.C = l->acts; g.ldc = R; g.C2 = nullptr; g.ldc2 = 0; g.bias = l->bias_p; g.act = ACT_IDENTITY;
         if (pre16) { g.C = nullptr; g.C2 = l->pre16; g.ldc2 = R; }
         g.M = c->N; g.N = R; g.K = l->Pp;
@@ -925,6 +968,7 @@ void lstm_backward(cn_layer *l)
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
     }
+    if (l->prev->trainable) mask_handed_back_error(l);    // (K8 carries the fork: K9 does not read prev->err and starts beside this)
     // K9 runs on the side stream: it only feeds weightUpdates, forked AFTER K8 so the critical-path GEMM has the chip to itself, and running beside the
     // preceding layer's recurrent kernel (which occupies ~10 % of the CUs)
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
@@ -937,7 +981,7 @@ void lstm_backward(cn_layer *l)
             Timed tm(c, KC_GEMM_GRAD, st);
             GemmTN gs[3]; int ng = 0;
             GemmTN g{};
-            g.A = l->delta_op; g.lda = R; g.B = l->prev->out_op; g.ldb = l->Pp;
+            g.A = l->delta_op; g.lda = R; g.B = backward_input(l); g.ldb = l->Pp;
             g.C = l->dWin; g.ldc = l->Pp; g.M = R; g.N = l->Pp; g.K = N;
             if (c->det) { g.ws = l->det_ws; g.ws_splits = DET_MAX_SPLITS; g.ws_used = defer ? &used_in : nullptr; }
             gs[ng++] = g;
@@ -982,10 +1026,11 @@ void ff_forward(cn_layer *l)
     cn_ctx *c = l->ctx;
     repack(l);
     const bool softmax = l->kind == CN_LAYER_SOFTMAX;
+    const void *x = forward_input(l);
     {
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
-        g.A = l->prev->out_op; g.lda = l->Pp; g.B = l->Win; g.ldb = l->Pp;
+        g.A = x; g.lda = l->Pp; g.B = l->Win; g.ldb = l->Pp;
         g.C = l->out_f32; g.ldc = l->Lp;
         g.C2 = (!c->f32 && !softmax) ? l->out_op : nullptr; g.ldc2 = l->Lp;
         g.bias = l->bias_p; g.act = ff_act(l->kind);
@@ -1057,6 +1102,7 @@ void ff_backward(cn_layer *l)
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
     }
+    if (l->prev->trainable) mask_handed_back_error(l);
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
         const bool fused = armed_fused(l);
         const bool defer = c->det && fused;
@@ -1064,7 +1110,7 @@ void ff_backward(cn_layer *l)
         {   // FeedForwardLayer.cu:200-207
             Timed tm(c, KC_GEMM_GRAD, st);
             GemmTN g{};
-            g.A = l->delta_op; g.lda = l->Lp; g.B = l->prev->out_op; g.ldb = l->Pp;
+            g.A = l->delta_op; g.lda = l->Lp; g.B = backward_input(l); g.ldb = l->Pp;
             g.C = l->dWin; g.ldc = l->Pp; g.M = l->Lp; g.N = l->Pp; g.K = N;
             if (c->det) { g.ws = l->det_ws; g.ws_splits = DET_MAX_SPLITS; g.ws_used = defer ? &used_in : nullptr; }
             launch_gemm_tn(st, c->prec, g, c->tn_cus, (colfold.nparts && !defer) ? &colfold : nullptr);
@@ -1457,6 +1503,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
         }
         l = new cn_layer;
         l->ctx = ctx; l->kind = kind; l->prev = preceding; l->size = size; l->bias = bias;
+        l->ordinal = ctx->next_ordinal;
         l->PS = preceding ? preceding->PS : parallel_sequences;
         l->maxT = preceding ? preceding->maxT : max_seq_length;
         if (!preceding) {
@@ -1606,6 +1653,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
         }
         if (preceding && l->trainable) preceding->has_follower = true;
         ctx->layers.push_back(l);
+        ++ctx->next_ordinal;
     });
     if (rc != CN_OK) { if (l) { for (void *p : l->owned) hipFree(p); delete l; } return rc; }
     *out = l;
@@ -2392,6 +2440,51 @@ int cn_layer_set_learning_rate(cn_layer *layer, float learning_rate)
     if (!layer->trainable) { g_last_error = "cn_layer_set_learning_rate: layer has no weights"; return CN_ERR_BAD_ARG; }
     layer->own_lr = learning_rate;
     return CN_OK;
+}
+
+// ---- dropout (include/currennt_hip.h, section Dropout) ----
+int cn_layer_set_dropout(cn_layer *layer, float rate)
+{
+    if (!layer) { g_last_error = "cn_layer_set_dropout: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_dropout: only lstm, blstm, feedforward_* and softmax layers take dropout on their input");
+        if (!(rate >= 0.f && rate < 1.f)) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_dropout: the rate must lie in [0, 1)");
+        if (rate > 0.f && !layer->in_drop) {      // like the preceding layer's out_op: same size, cleared once
+            enter(layer->ctx);
+            layer->in_drop = dalloc(layer, layer->maxN() * layer->Pp * layer->ctx->esz());
+        }
+        layer->drop_rate = rate;
+    });
+}
+
+int cn_ctx_set_dropout_pass(cn_ctx *ctx, int enable, uint64_t seed, uint64_t pass)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_dropout_pass: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    ctx->drop_enable = enable != 0; ctx->drop_seed = seed; ctx->drop_pass = pass;
+    return CN_OK;
+}
+
+int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_dbg_dropout_input: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        require_loaded(c);
+        if (!layer->trainable || !layer->dropped) throw cn_error(CN_ERR_STATE, "cn_dbg_dropout_input: the layer's last forward pass did not drop");
+        // the geometry of the forward pass that wrote the copy (its record), not of whatever fraction is loaded now
+        const DropArgs &a = layer->drop;
+        const int frames = a.N / a.PSp * a.PS;
+        if (count != (size_t)frames * a.P) throw cn_error(CN_ERR_SHAPE, "cn_dbg_dropout_input: count != T*PS*size of the preceding layer (of that forward pass)");
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
+        const bool opbf = !c->f32;
+        if (a.prevH)
+            for (int d = 0; d < a.prevDirs; ++d) launch_unpad(c->stream, opbf, layer->in_drop, a.Pp, d * a.prevHp, 1, frames, a.prevH, tmp, a.P, d * a.prevH, a.PS, a.PSp);
+        else launch_unpad(c->stream, opbf, layer->in_drop, a.Pp, 0, 1, frames, a.P, tmp, a.P, 0, a.PS, a.PSp);
+        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
 }
 
 // cn_sgd_update_all / cn_adam_update_all: one sequence for both rules (r.lr: the call's learning rate)

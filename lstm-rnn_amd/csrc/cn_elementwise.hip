@@ -10,6 +10,7 @@
 //   layers/SsePostOutputLayer.cu:39-88 and the other post output layers -> post_rows_kernel, post_backward_kernel
 //   optimizers/SteepestDescentOptimizer.cu:39-59 UpdateWeightFn  -> sgd_kernel
 //   (no counterpart in the reference) the Adam step of include/currennt_hip.h -> adam_kernel, pack_group_adam_kernel
+//   (no counterpart in the reference) dropout on a layer's input, include/currennt_hip.h -> dropout_fwd_kernel, dropout_bwd_kernel
 #include "cn_internal.h"
 
 #include <float.h>
@@ -485,6 +486,109 @@ void launch_pad_f32(hipStream_t s, const float *src, int N, int L, float *dst, l
     long total = (long)N * L; if (total <= 0) return;
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pad_f32_kernel, dim3(blocks), dim3(256), 0, s, src, N, L, dst, ld, prevH, prevHp, PS, PSp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// dropout on a layer's input (include/currennt_hip.h, section Dropout): the mask is a pure function of (key, frame, unit) in the
+// REFERENCE layout, so both kernels first undo the padding of their element.  Plain streaming kernels: one thread owns four
+// neighbouring padded columns of one row (Pp and every direction's pitch are multiples of 4, so the four lie in one direction)
+// and moves them with one 8-byte (bf16) or 16-byte (fp32) load and store.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+// Bit k of the result: padded element (row, pc + k) is a kept unit of a real slot.  Four reference units share one Philox call
+// (counter word 0 = unit >> 2).  The four columns are the units base .. base + 3 of the reference layout; they straddle two
+// calls only where a backward direction starts at a unit that is no multiple of 4 (H % 4 != 0).
+__device__ __forceinline__ unsigned drop_keep4(const DropArgs &a, long row, int pc)
+{
+    const long t = row / a.PSp; const int ps = (int)(row % a.PSp);
+    if (ps >= a.PS) return 0u;
+    int base, cnt;                                        // first unit, units among the four columns
+    if (a.prevH == 0) { base = pc; cnt = a.P - pc; }
+    else {
+        const int dd = pc / a.prevHp, jj = pc % a.prevHp;
+        base = dd * a.prevH + jj; cnt = dd < a.prevDirs ? a.prevH - jj : 0;
+    }
+    if (cnt <= 0) return 0u;
+    cnt = min(cnt, 4);
+    const uint32_t n = (uint32_t)(t * a.PS + ps);
+    const int sh = base & 3;
+    const uint4 w0 = philox4x32_10(make_uint4((uint32_t)(base >> 2), n, a.pass_lo, a.pass_hi), a.k0, a.k1);
+    uint4 w1 = make_uint4(0u, 0u, 0u, 0u);
+    if (sh + cnt > 4) w1 = philox4x32_10(make_uint4((uint32_t)(base >> 2) + 1u, n, a.pass_lo, a.pass_hi), a.k0, a.k1);
+    // the words of units base .. base + 3: the eight words shifted down by sh (selects on registers, no indexed array)
+    uint32_t a0 = w0.x, a1 = w0.y, a2 = w0.z, a3 = w0.w, a4 = w1.x, a5 = w1.y, a6 = w1.z;
+    if (sh & 1) { a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6; }
+    if (sh & 2) { a0 = a2; a1 = a3; a2 = a4; a3 = a5; }
+    unsigned keep = 0u;
+    if (a0 >= a.thr) keep |= 1u;
+    if (cnt > 1 && a1 >= a.thr) keep |= 2u;
+    if (cnt > 2 && a2 >= a.thr) keep |= 4u;
+    if (cnt > 3 && a3 >= a.thr) keep |= 8u;
+    return keep;
+}
+template <bool F32>
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(DropArgs a, const void *__restrict__ src, void *__restrict__ dst)
+{
+    const int q = a.Pp >> 2;
+    const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (idx >= (long)a.N * q) return;
+    const long row = idx / q; const int pc = (int)(idx % q) << 2;
+    const long off = row * a.Pp + pc;
+    const unsigned keep = drop_keep4(a, row, pc);
+    if constexpr (F32) {
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (keep) x = *(const float4 *)((const float *)src + off);
+        x.x = (keep & 1u) ? x.x * a.scale : 0.f; x.y = (keep & 2u) ? x.y * a.scale : 0.f;
+        x.z = (keep & 4u) ? x.z * a.scale : 0.f; x.w = (keep & 8u) ? x.w * a.scale : 0.f;
+        *(float4 *)((float *)dst + off) = x;
+    } else {
+        uint2 x = make_uint2(0u, 0u);
+        if (keep) x = *(const uint2 *)((const unsigned short *)src + off);
+        const float f[4] = {__uint_as_float(x.x << 16), __uint_as_float(x.x & 0xFFFF0000u), __uint_as_float(x.y << 16), __uint_as_float(x.y & 0xFFFF0000u)};
+        unsigned short o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const __bf16 b = (__bf16)((keep >> k & 1u) ? f[k] * a.scale : 0.f);     // (round to nearest even)
+            o[k] = __builtin_bit_cast(unsigned short, b);
+        }
+        *(uint2 *)((unsigned short *)dst + off) = make_uint2((unsigned)o[0] | (unsigned)o[1] << 16, (unsigned)o[2] | (unsigned)o[3] << 16);
+    }
+}
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(DropArgs a, float *__restrict__ err)
+{
+    const int q = a.Pp >> 2;
+    const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (idx >= (long)a.N * q) return;
+    const long row = idx / q; const int pc = (int)(idx % q) << 2;
+    float4 *p = (float4 *)(err + row * a.Pp + pc);
+    const unsigned keep = drop_keep4(a, row, pc);
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (keep) x = *p;
+    x.x = (keep & 1u) ? x.x * a.scale : 0.f; x.y = (keep & 2u) ? x.y * a.scale : 0.f;
+    x.z = (keep & 4u) ? x.z * a.scale : 0.f; x.w = (keep & 8u) ? x.w * a.scale : 0.f;
+    *p = x;
+}
+static int dropout_blocks(const DropArgs &a) { return (int)(((long)a.N * (a.Pp >> 2) + 255) / 256); }
+void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *src, void *dst)
+{
+    const int blocks = dropout_blocks(a); if (blocks <= 0) return;
+    if (f32) hipLaunchKernelGGL(dropout_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, a, src, dst);
+    else     hipLaunchKernelGGL(dropout_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, a, src, dst);
+}
+void launch_dropout_bwd(hipStream_t s, const DropArgs &a, float *err)
+{
+    const int blocks = dropout_blocks(a); if (blocks <= 0) return;
+    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(blocks), dim3(256), 0, s, a, err);
 }
 
 // ---------------------------------------------------------------------------------------------

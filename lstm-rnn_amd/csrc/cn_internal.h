@@ -265,6 +265,19 @@ void launch_rowmap(hipStream_t s, const char *dpat, int N, int *rm, int maxN, in
 void launch_fraction_load(hipStream_t s, bool f32, int T, int PS, int PSp, const char *pat, char *dpat, const int *tcls, int *dtcls,
                           const float *tgt, float *dtgt, int W, const float *in, int P, void *dst, int Pp, int *rm = nullptr, int maxN = 0, int Tmin = 0);
 void launch_pad_convert(hipStream_t s, bool f32, const float *src, int N, int P, void *dst, int Pp);
+// ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
+// The key of one forward pass of one layer, and the geometry that maps a padded element to the reference (frame, unit) the mask
+// is stated in: row r = t * PSp + ps <-> frame n = t * PS + ps (pad slots ps >= PS: zeros); column -> unit as unpad_col does
+// (prevH = 0: dense, units [0, P); else direction d's units at columns [d * prevHp, d * prevHp + prevH)).  Pp is a multiple of 4.
+struct DropArgs {
+    int N, PS, PSp, P, Pp, prevH, prevHp, prevDirs;
+    uint32_t k0, k1, pass_lo, pass_hi, thr;    // Philox key ((seed_lo + ordinal), seed_hi), counter words 2 and 3, keep threshold
+    float scale;
+};
+// dst[N][Pp] (op) = masked, rescaled src[N][Pp] (op); pad rows and pad columns are written as zeros
+void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *src, void *dst);
+// err[N][Pp] (fp32) masked and rescaled in place with the same key
+void launch_dropout_bwd(hipStream_t s, const DropArgs &a, float *err);
 // delta = act'(y) * err (in place on err, all N slots: FeedForwardLayer.cu:72-79), op copy for the GEMMs
 void launch_ff_delta(hipStream_t s, bool f32, int act, const float *y, float *err, void *delta_op, int N, int L, int Lp);
 // column sums of delta over the N slots (FeedForwardLayer.cu:82-102): colsum[j] += sum_n err[n][j]

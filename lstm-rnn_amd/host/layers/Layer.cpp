@@ -21,6 +21,12 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
     if (!layerChild.hasMember("name")) throw std::runtime_error("Missing value 'name' in layer description");       // Layer.cpp:52-53
     if (m_name.empty()) throw std::runtime_error("Empty layer name in layer description");                           // :54-55
     if (!layerChild.hasMember("size")) throw std::runtime_error("Missing value 'size' in layer '" + m_name + "'");  // :56-57
+    // "dropout" acts on a trainable layer's input (TrainableLayer reads it): on an input or post output layer it is an error, not
+    // a member to ignore (the Python mirror refuses the same file)
+    const bool trainableKind = kind == CN_LAYER_LSTM || kind == CN_LAYER_BLSTM || kind == CN_LAYER_FF_TANH || kind == CN_LAYER_FF_LOGISTIC ||
+                               kind == CN_LAYER_FF_IDENTITY || kind == CN_LAYER_SOFTMAX;
+    if (layerChild.hasMember("dropout") && !trainableKind)
+        throw std::runtime_error("Invalid value 'dropout' in layer '" + m_name + "': only lstm, blstm, feedforward_* and softmax layers take dropout");
     hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
                              precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
 }
@@ -76,10 +82,14 @@ TrainableLayer::TrainableLayer(cn_ctx *ctx, const json::Value &layerChild, const
     , m_inputWeightsPerBlock(inputWeightsPerBlock), m_internalWeightsPerBlock(internalWeightsPerBlock)
     , m_bias(jsonBias(layerChild))
     , m_learningRate(layerChild.hasMember("learningRate") ? (real_t)layerChild["learningRate"].getDouble() : -1)
+    , m_dropout(layerChild.hasMember("dropout") ? (real_t)layerChild["dropout"].getDouble() : 0)
 {
     if (!layerChild.hasMember("bias")) throw std::runtime_error("Missing value 'bias' in layer '" + name() + "'");   // TrainableLayer.cu:61-62
     // the layer's own learning rate (TrainableLayer.cu:58) is also what an armed update (cn_ctx_arm_update) applies to it
     if (m_learningRate >= 0) cn_layer_set_learning_rate(m_handle, m_learningRate);
+    // dropout on this layer's input (include/currennt_hip.h, section Dropout; the reference has none)
+    if (!(m_dropout >= 0 && m_dropout < 1)) throw std::runtime_error("Invalid value 'dropout' in layer '" + name() + "': the rate must lie in [0, 1)");
+    if (m_dropout > 0) hipCheck(cn_layer_set_dropout(m_handle, m_dropout), m_ctx);
     if (weightsSection && weightsSection->hasMember(name())) {                                                    // :68-101
         const json::Value &w = (*weightsSection)[name()];
         if (!w.isObject()) throw std::runtime_error("Weights section for layer '" + name() + "' is not an object");
@@ -124,6 +134,7 @@ void TrainableLayer::exportLayer(json::Value *layersArray) const
 {
     Layer::exportLayer(layersArray);
     (*layersArray)[layersArray->size() - 1].addMember("bias", (double)m_bias);
+    if (m_dropout > 0) (*layersArray)[layersArray->size() - 1].addMember("dropout", (double)m_dropout);
 }
 
 // ---- FeedForward / Softmax / Lstm -----------------------------------------------------------

@@ -71,6 +71,7 @@ public:
     const Layer &precedingLayer() const { return m_precedingLayer; }
     real_t bias() const { return m_bias; }
     real_t learningRate() const { return m_learningRate; }
+    real_t dropout() const { return m_dropout; }        // JSON "dropout": rate of the dropout on this layer's input (0: none)
     Hip::real_vector weights() const;                     // TrainableLayer.hpp:119
     Hip::real_vector weightUpdates() const;               // TrainableLayer.hpp:133
     void setWeights(const Hip::real_vector &w);
@@ -81,7 +82,7 @@ public:
 private:
     Layer &m_precedingLayer;
     int m_inputWeightsPerBlock, m_internalWeightsPerBlock;
-    real_t m_bias, m_learningRate;
+    real_t m_bias, m_learningRate, m_dropout;
 };
 
 class FeedForwardLayer : public TrainableLayer {          // layers/FeedForwardLayer.{hpp,cu}

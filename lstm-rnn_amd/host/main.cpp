@@ -351,6 +351,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 printf("Momentum:                  %g\n\n", (double)config.momentum());
             }
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
+            // every rank its own masks: seed = --random_seed + rank * 0x9E3779B97F4A7C15 (mod 2^64)
+            optimizer.setDropoutSeed((uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull);
 
             std::string infoRows;
             if (!config.continueFile().empty()) {                                               // main.cpp:198-204

@@ -85,10 +85,22 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
     // (one D2H copy per fraction: not on the training pass, whose class error stays unset).  Data-parallel: of this rank's sequences.
     const bool ctc = dynamic_cast<layers::CtcPostOutputLayer *>(&m_neuralNetwork.postOutputLayer()) != 0;
     long labelErrors = 0, labelCount = 0;
+    // dropout: only training passes drop; the calls are skipped altogether when no layer has a rate
+    bool anyDropout = false;
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        const layers::TrainableLayer *layer = dynamic_cast<const layers::TrainableLayer *>(ls[i].get());
+        anyDropout = anyDropout || (layer && layer->dropout() > 0);
+    }
+    if (anyDropout && !calcWeightUpdates) hipCheck(cn_ctx_set_dropout_pass(m_neuralNetwork.context(), 0, 0, 0), m_neuralNetwork.context());
+    uint64_t fractionIndex = 0;
     data_sets::DataSetFraction frac, next;
     bool firstFraction = true;
     bool have = ds.getNextFraction(&frac);
     while (have) {
+        if (anyDropout && calcWeightUpdates)
+            hipCheck(cn_ctx_set_dropout_pass(m_neuralNetwork.context(), 1, m_dropoutSeed, ((uint64_t)m_curEpoch << 32) | (fractionIndex & 0xFFFFFFFFull)),
+                     m_neuralNetwork.context());
+        ++fractionIndex;
         m_neuralNetwork.loadSequences(frac);
         m_neuralNetwork.computeForwardPass();
         hipCheck(cn_loss_accumulate(m_neuralNetwork.postOutputLayer().handle()), m_neuralNetwork.context());

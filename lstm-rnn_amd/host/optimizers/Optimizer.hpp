@@ -22,6 +22,10 @@ public:
 
     // Gaussian weight noise during the backward pass (Optimizer.cu:58-68,82-84; --weight_noise_sigma)
     void setWeightNoise(real_t sigma, unsigned randomSeed) { m_weightNoiseSigma = sigma; m_noiseGen.seed(randomSeed); }
+    // Dropout (layers with a JSON "dropout"; include/currennt_hip.h, section Dropout): training passes drop with this seed and
+    // pass = (epoch << 32) | index of the fraction in the epoch -- derived, not stored, so --continue resumes the same masks;
+    // validation and test passes do not drop
+    void setDropoutSeed(uint64_t seed) { m_dropoutSeed = seed; }
     // autosave / --continue (Optimizer.cu:326-358)
     virtual void exportState(json::Value *jsonDoc) const;
     virtual void importState(const json::Value &jsonDoc);
@@ -67,6 +71,7 @@ private:
     std::vector<Hip::real_vector> m_bestWeights;
     real_t m_weightNoiseSigma = 0;
     std::mt19937 m_noiseGen;
+    uint64_t m_dropoutSeed = 0;
 protected:
     static void _exportWeights(json::Value *jsonDoc, const char *arrayName, const std::vector<Hip::real_vector> &weights);   // :106-123
     static void _importWeights(const json::Value &jsonDoc, const char *arrayName, std::vector<Hip::real_vector> *weights);   // :125-149

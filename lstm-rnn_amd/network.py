@@ -45,6 +45,15 @@ class Layer:
         self.weight_count = L.cn_layer_weight_count(h) if self.trainable else 0
         if self.trainable and self.learning_rate >= 0.0:       # cn_sgd_update_all honours it too (SteepestDescentOptimizer.cu:78-80)
             B.check(L.cn_layer_set_learning_rate(h, self.learning_rate), net.ctx)
+        # "dropout": rate of the dropout on this layer's input (include/currennt_hip.h, section Dropout); absent = none
+        self.dropout = float(desc.get("dropout", 0.0))
+        if "dropout" in desc:
+            # (the same two refusals, with the same texts, as the C++ driver's Layer / TrainableLayer constructors)
+            if not self.trainable:
+                raise RuntimeError("Invalid value 'dropout' in layer '%s': only lstm, blstm, feedforward_* and softmax layers take dropout" % self.name)
+            if not 0.0 <= self.dropout < 1.0:
+                raise RuntimeError("Invalid value 'dropout' in layer '%s': the rate must lie in [0, 1)" % self.name)
+            self.set_dropout(self.dropout)
         if self.type in ("lstm", "blstm"):
             self.dirs = 2 if self.type == "blstm" else 1
             self.H = self.size // self.dirs
@@ -82,6 +91,19 @@ class Layer:
         flat = np.ascontiguousarray(array, np.float32).reshape(-1)
         B.check(self.net.lib.cn_layer_upload(self.handle, B.BUF[which], flat.ctypes.data_as(C.c_void_p), flat.size),
                 self.net.ctx)
+
+    def set_dropout(self, rate):
+        """cn_layer_set_dropout: the rate of the dropout on this layer's input (0: none)."""
+        B.check(self.net.lib.cn_layer_set_dropout(self.handle, float(rate)), self.net.ctx)
+        self.dropout = float(rate)
+
+    def dropout_input(self):
+        """The masked operand copy this layer's input products read in its last forward pass, [T][PS][size of the preceding
+        layer] (cn_dbg_dropout_input); CN_ERR_STATE when that pass did not drop."""
+        n = self.net.N * self.prev.size
+        out = np.empty(n, np.float32)
+        B.check(self.net.lib.cn_dbg_dropout_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
+        return out.reshape(self.net.T, self.net.PS, self.prev.size)
 
     def weight_updates_tensor(self, torch):
         """The layer's weightUpdates in HBM as a torch tensor aliasing the library's memory (no copy)."""
@@ -445,6 +467,11 @@ class NeuralNetwork:
         """cn_ctx_arm_adam: the coming backward pass applies each layer's Adam step as soon as that layer's gradient is complete;
         follow the backward pass with update_weights_adam(same values), which completes the step."""
         B.check(self.lib.cn_ctx_arm_adam(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+
+    def set_dropout_pass(self, enable, seed=0, pass_=0):
+        """cn_ctx_set_dropout_pass: whether the forward passes that follow drop (on the layers with a "dropout" rate), and the
+        64-bit (seed, pass) of their masks.  The library keeps no clock: a training loop hands a new pass per fraction."""
+        B.check(self.lib.cn_ctx_set_dropout_pass(self.ctx, 1 if enable else 0, int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1)), self.ctx)
 
     def accumulate_updates(self, first):
         """Batch learning (Optimizer.cu:72-85): add this fraction's weightUpdates of all layers to the epoch sum on the device
