@@ -419,6 +419,54 @@ int  cn_layer_set_dropout(cn_layer *layer, float rate);
  * uses that record: a call between forward and backward cannot tear a step. */
 int  cn_ctx_set_dropout_pass(cn_ctx *ctx, int enable, uint64_t seed, uint64_t pass);
 
+/* ---- Gradient clipping by the global L2 norm (Pascanu et al. 2013; no counterpart in the reference, whose only guard is the
+ *      per-element delta clip inside the LSTM cell, which the kernels keep) ------------------------------------------------------
+ * One bound on the size of a step, in front of the momentum rule and the Adam rule alike.
+ *
+ * The gradient.  g is the weightUpdates part of the parameter arena: all n = `count` entries of cn_ctx_param_arena in arena order
+ * (every layer's flat vector, each rounded up to a multiple of four entries by pad entries that are zero), as the update is about
+ * to read it: after cn_allreduce_grads, and after cn_ctx_take_accumulated (batch learning clips the epoch sum).
+ *
+ * The sum.  S = sum of g[i]^2 is formed in DOUBLE; each square is formed in double from the float, so it is exact.  The order
+ * is a function of i and n alone -- not of the grid, the CU count, the precision mode or the "deterministic" option:
+ *      L = 16384 lanes.  lane[k] = ((0 + g[k]^2) + g[k + L]^2) + g[k + 2L]^2 + ...   ascending, entries i >= n count as +0
+ *      then fourteen levels over NEIGHBOURING lanes:  lane'[k] = lane[2k] + lane[2k + 1]  (L/2 sums, then L/4, ... then one) = S
+ * (numpy: pad g to a multiple of L, acc = zeros(L, float64); for each row r of g.reshape(-1, L): acc += r.astype(float64) ** 2;
+ * while len(acc) > 1: acc = acc[0::2] + acc[1::2].)
+ *
+ * The norm and the factor.  norm = (float) sqrt(S): a correctly rounded double square root, rounded once to float.
+ *      S not finite (an inf or NaN entry):  the step is SKIPPED
+ *      else norm > max_norm:                scale = max_norm / norm, one correctly rounded fp32 division, and every path uses
+ *                                           g' = scale * g (one fp32 multiplication) in place of g
+ *      else:                                no multiplication happens at all: a step whose norm stays at or below the bound is
+ *                                           bit-equal to the same step with clipping off
+ * A skipped step leaves the weights, the deltas / first moments, the second moments and the operand copies as they were, bit for
+ * bit.  The caller's Adam `step` still advances: the library keeps no clock.  weightUpdates itself is never rewritten:
+ * cn_layer_read(CN_BUF_WEIGHT_UPDATES) after the update returns the unclipped gradient.  Per-layer learning rates keep their
+ * meaning: the factor is global, the rates are per layer.
+ *
+ * When.  The norm is formed once per gradient, on the context's stream, by the first cn_sgd_update / cn_sgd_update_all /
+ * cn_adam_update / cn_adam_update_all after the gradient last changed (cn_layer_backward, cn_allreduce_grads,
+ * cn_ctx_take_accumulated, cn_layer_upload of CN_BUF_WEIGHT_UPDATES); later per-layer calls of the same step reuse it.  Nothing
+ * synchronises the host.  Data-parallel: every rank forms the norm of the same reduced gradient in the same order, so the replicas
+ * stay bit-identical without another exchange.
+ *
+ * Armed updates.  A global norm needs every layer's gradient, so the step cannot be applied layer by layer behind each gradient.
+ * With clipping on, cn_ctx_arm_update / cn_ctx_arm_adam are still accepted and checked, and the step is applied by the completing
+ * *_update* call (which must name the armed values, else CN_ERR_STATE); the caller's call sequence and the result -- backward on
+ * every layer, then *_update_all -- are unchanged, the overlap of the update with the backward pass is lost.
+ *
+ * With clipping off the library launches exactly what it launches without these calls and allocates nothing for them. */
+/* The bound; 0 = off, and a fresh context is off.  Negative, NaN or infinite: CN_ERR_BAD_ARG.  May be changed between steps; while an
+ * armed update is pending: CN_ERR_STATE.  max_norm = FLT_MAX makes a pure monitor: the norm is formed, nothing is ever scaled. */
+int  cn_ctx_set_grad_clip(cn_ctx *ctx, float max_norm);
+/* The record of the last step whose norm was formed -- *last_norm, *last_scale (the factor; 1 when the step was not clipped, 0 when
+ * it was skipped) -- and, since the last reset: the norms formed (*updates), the steps clipped and skipped, and the largest finite
+ * norm.  Any pointer may be NULL; reset != 0 clears the counters and the largest norm behind the read.  With clipping off it
+ * reports zeros.                                                                                                      [sync] */
+int  cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, int64_t *updates, int64_t *clipped, int64_t *skipped,
+                            float *max_norm_seen, int reset);
+
 #ifdef __cplusplus
 }
 #endif

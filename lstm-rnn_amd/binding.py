@@ -44,6 +44,8 @@ EXPORTS = [
     "cn_layer_set_label_sequences", "cn_dbg_ctc",
     # include/currennt_hip.h, section Dropout, and its hook in include/currennt_hip_debug.h
     "cn_layer_set_dropout", "cn_ctx_set_dropout_pass", "cn_dbg_dropout_input",
+    # include/currennt_hip.h, section Gradient clipping
+    "cn_ctx_set_grad_clip", "cn_ctx_grad_clip_stats",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -184,6 +186,8 @@ def load_library():
     L.cn_layer_set_dropout.argtypes = [vp, cf]
     L.cn_ctx_set_dropout_pass.argtypes = [vp, ci, C.c_uint64, C.c_uint64]
     L.cn_dbg_dropout_input.argtypes = [vp, vp, C.c_size_t]
+    L.cn_ctx_set_grad_clip.argtypes = [vp, cf]
+    L.cn_ctx_grad_clip_stats.argtypes = [vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(cf), ci]
     _LIB = L
     return L
 

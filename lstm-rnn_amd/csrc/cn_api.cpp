@@ -174,6 +174,16 @@ struct cn_ctx {
     int family = FAMILY_NONE;
     float *adam_v = nullptr;              // Adam's second moments, [total] like a part of the arena, zeroed; allocated at the first Adam call
 
+    // cn_ctx_set_grad_clip (include/currennt_hip.h, section Gradient clipping): the bound (0: off), the device record -- allocated
+    // by the first non-zero bound -- and whether the record still holds the norm of what weightUpdates holds now (cleared by
+    // everything that changes the gradient; the first update call behind that forms the norm again)
+    float clip_max = 0.f;
+    ClipRecord *clip_rec = nullptr;
+    bool clip_valid = false;
+    // ... an armed step cannot run layer by layer behind a GLOBAL norm: with clipping on, arming only records the rule (`arm`) and
+    // the completing *_update* call applies the step.  Layers whose completing per-layer call is still to come: cn_layer::deferred.
+    bool arm_deferred = false;
+
     // cn_ctx_set_dropout_pass: whether the forward passes that follow drop, and the caller's (seed, pass) of their masks
     bool drop_enable = false;
     uint64_t drop_seed = 0, drop_pass = 0;
@@ -246,6 +256,7 @@ struct cn_layer {
     std::vector<float> pending_w;         // set_weights before the arena exists
     bool dirty = true;                    // packed copies out of date
     bool updated = false;                 // armed update: this layer's step has been enqueued behind its gradient already
+    bool deferred = false;                // armed with clipping on (cn_ctx::arm_deferred): the completing call has not come yet
 
     // packed copies
     void *Win = nullptr, *WinT = nullptr, *Wrec = nullptr, *WrecT = nullptr;
@@ -1246,7 +1257,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -1441,6 +1452,7 @@ int cn_allreduce_grads(cn_ctx *ctx, cn_layer *const *layers, int n)
         require_comm(ctx, "cn_allreduce_grads");
         enter(ctx);
         finalize(ctx);
+        ctx->clip_valid = false;
         // CN_COMM_TEST_DOUBLE (tests/test_gpu_parallel.py): the collective is replaced by a kernel on the communication stream
         // that doubles the gradient -- what a two-rank all-reduce of equal shards does --, so that the ORDER of gradient work,
         // exchange and update can be checked on a one-GPU box: a reduction that starts early or an update that does not wait
@@ -1985,6 +1997,7 @@ int cn_layer_backward(cn_layer *layer)
             throw cn_error(CN_ERR_STATE, c->arm.adam
                 ? "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_adam_update_all / cn_adam_update first)"
                 : "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_sgd_update_all / cn_sgd_update first)");
+        if (layer->trainable) c->clip_valid = false;        // (the gradient changes: the next update call forms its norm)
         if (layer->lstm) lstm_backward(layer);
         else if (layer->trainable) ff_backward(layer);
         else if (layer->post) {
@@ -2183,6 +2196,7 @@ int cn_layer_upload(cn_layer *layer, cn_buffer which, const float *host, size_t 
         finalize(c);
         join_side(c);
         if (which == CN_BUF_ADAM_SECOND_MOMENTS) ensure_adam_v(c);
+        if (which == CN_BUF_WEIGHT_UPDATES) c->clip_valid = false;
         HIP_CHECK(hipMemcpyAsync(which == CN_BUF_ADAM_SECOND_MOMENTS ? c->adam_v + layer->woff : which == CN_BUF_WEIGHT_UPDATES ? layer->wu : layer->wd, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     });
@@ -2339,11 +2353,28 @@ static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
                                                           : ": learning rate / momentum differ from what cn_ctx_arm_update armed and applied"));
 }
 // the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in, at rate lr
-static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, hipEvent_t done = nullptr)
+// clip: the record of the step's norm (clip_record below), or null with clipping off -- then the launches are the ones they were
+static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, const ClipRecord *clip, hipEvent_t done = nullptr)
 {
     float *w = c->arena + off, *wu = w + c->total, *wd = w + 2 * c->total;
-    if (r.adam) launch_adam(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), done);
-    else        launch_sgd(c->stream, w, wu, wd, n, lr, r.mom, done);
+    if (clip) {
+        if (r.adam) launch_adam_clip(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), clip, done);
+        else        launch_sgd_clip(c->stream, w, wu, wd, n, lr, r.mom, clip, done);
+    }
+    else if (r.adam) launch_adam(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), done);
+    else             launch_sgd(c->stream, w, wu, wd, n, lr, r.mom, done);
+}
+// Behind begin_update (the main stream is ordered behind the side streams' gradient work and the reductions): the record the
+// update launches of this step read, or null with clipping off.  The norm is formed once per gradient: by the first update call
+// after the gradient last changed; the per-layer calls that follow reuse the record.
+static const ClipRecord *clip_record(cn_ctx *c)
+{
+    if (c->clip_max == 0.f || !c->total) return nullptr;
+    if (!c->clip_valid) {
+        launch_grad_norm(c->stream, c->arena + c->total, c->total, c->clip_max, c->clip_rec);
+        c->clip_valid = true;
+    }
+    return c->clip_rec;
 }
 
 // cn_ctx_arm_update / cn_ctx_arm_adam
@@ -2356,7 +2387,13 @@ static void arm(cn_ctx *ctx, const UpdateRule &r, const char *fn)
                                        (r.adam ? "cn_adam_update_all" : "cn_sgd_update_all") + ")");
     bind_family(ctx, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
     if (r.adam) ensure_adam_v(ctx);
-    ctx->armed = true; ctx->arm = r;
+    ctx->arm = r;
+    if (ctx->clip_max != 0.f) {      // clipping on: accepted and checked, applied by the completing call (a global norm needs every layer's gradient)
+        ctx->arm_deferred = true;
+        for (cn_layer *l : ctx->layers) l->deferred = l->trainable;
+        return;
+    }
+    ctx->armed = true;
 }
 
 int cn_ctx_arm_update(cn_ctx *ctx, float learning_rate, float momentum)
@@ -2388,8 +2425,17 @@ static void update_layer(cn_layer *layer, const UpdateRule &r, const char *fn)
         if (!any) c->armed = false;
         return;
     }
+    if (layer->deferred) {           // armed with clipping on: this is the call that applies the layer's step
+        UpdateRule armed = c->arm;
+        armed.lr = layer_lr(layer, c->arm);
+        if (!same_rule(r, armed)) throw_rule_mismatch(fn, r.adam);
+        layer->deferred = false;
+        bool any = false;
+        for (cn_layer *o : c->layers) any = any || o->deferred;
+        if (!any) c->arm_deferred = false;
+    }
     Timed tm(c, KC_OTHER);
-    launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr);
+    launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr, clip_record(c));
     layer->dirty = true;
 }
 
@@ -2411,7 +2457,7 @@ int cn_ctx_accumulate_updates(cn_ctx *ctx, int first)
     return guarded([&] {
         enter(ctx);
         finalize(ctx);
-        if (ctx->armed) throw cn_error(CN_ERR_STATE, "cn_ctx_accumulate_updates: an armed per-fraction update is pending (batch learning sums first, cn_ctx_arm_update is not for it)");
+        if (ctx->armed || ctx->arm_deferred) throw cn_error(CN_ERR_STATE, "cn_ctx_accumulate_updates: an armed per-fraction update is pending (batch learning sums first, cn_ctx_arm_update is not for it)");
         if (!first && !ctx->acc_valid) throw cn_error(CN_ERR_STATE, "cn_ctx_accumulate_updates: nothing accumulated yet (the first fraction of an epoch passes first != 0)");
         join_side(ctx);                     // the gradient GEMMs / unpack launches of the side streams write weightUpdates
         if (!ctx->acc) HIP_CHECK(hipMalloc((void **)&ctx->acc, ctx->total * sizeof(float)));
@@ -2430,7 +2476,50 @@ int cn_ctx_take_accumulated(cn_ctx *ctx)
         if (!ctx->acc_valid) throw cn_error(CN_ERR_STATE, "cn_ctx_take_accumulated: nothing accumulated (cn_ctx_accumulate_updates)");
         join_side(ctx);
         HIP_CHECK(hipMemcpyAsync(ctx->arena + ctx->total, ctx->acc, ctx->total * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->clip_valid = false;
         ctx->acc_valid = false;
+    });
+}
+
+// ---- gradient clipping (include/currennt_hip.h, section Gradient clipping) ----
+int cn_ctx_set_grad_clip(cn_ctx *ctx, float max_norm)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_grad_clip: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!(max_norm >= 0.f) || std::isinf(max_norm)) throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_set_grad_clip: max_norm must be finite and >= 0 (0 = off)");
+        bool pending = ctx->armed || ctx->arm_deferred;
+        for (cn_layer *l : ctx->layers) pending = pending || l->updated;
+        if (pending) throw cn_error(CN_ERR_STATE, "cn_ctx_set_grad_clip: an armed update is pending (complete it with the *_update* call first)");
+        if (max_norm != 0.f && !ctx->clip_rec) {
+            enter(ctx);
+            HIP_CHECK(hipMalloc((void **)&ctx->clip_rec, sizeof(ClipRecord)));
+            HIP_CHECK(hipMemsetAsync(ctx->clip_rec, 0, sizeof(ClipRecord), ctx->stream));
+        }
+        if (max_norm != ctx->clip_max) ctx->clip_valid = false;       // (the record's factor belongs to the bound it was formed with)
+        ctx->clip_max = max_norm;
+    });
+}
+
+int cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, int64_t *updates, int64_t *clipped, int64_t *skipped,
+                           float *max_norm_seen, int reset)
+{
+    if (!ctx) { g_last_error = "cn_ctx_grad_clip_stats: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        ClipRecord h{};
+        if (ctx->clip_max != 0.f && ctx->clip_rec) {
+            enter(ctx);
+            HIP_CHECK(hipMemcpyAsync(&h, ctx->clip_rec, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+            // reset: the counters and the largest norm; the record of the last step stays (a per-layer call may still read it)
+            if (reset) HIP_CHECK(hipMemsetAsync((char *)ctx->clip_rec + offsetof(ClipRecord, max_seen), 0,
+                                                offsetof(ClipRecord, arrivals) - offsetof(ClipRecord, max_seen), ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        }
+        if (last_norm) *last_norm = h.norm;
+        if (last_scale) *last_scale = h.scale;
+        if (updates) *updates = h.updates;
+        if (clipped) *clipped = h.clipped;
+        if (skipped) *skipped = h.skipped;
+        if (max_norm_seen) *max_norm_seen = h.max_seen;
     });
 }
 
@@ -2500,12 +2589,18 @@ void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
     bool any_updated = false;
     for (cn_layer *l : ctx->layers) any_updated = any_updated || l->updated;
     if (any_updated && !same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r.adam);
+    if (ctx->arm_deferred) {         // armed with clipping on: the step is applied here, all layers at once
+        if (!same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r.adam);
+        ctx->arm_deferred = false;
+        for (cn_layer *l : ctx->layers) l->deferred = false;
+    }
     ctx->armed = false;
     struct ClearUpdated { cn_ctx *c; ~ClearUpdated() { for (cn_layer *l : c->layers) l->updated = false; } } clear_updated{ctx};
     Timed tm(ctx, KC_OTHER);
     int ntrain = 0;
     for (cn_layer *l : ctx->layers) if (l->trainable && !l->updated) ++ntrain;
     if (ntrain == 0) return;
+    const ClipRecord *clip = clip_record(ctx);
     if (any_updated) {               // some layers were not reached by the armed pass (no backward call for them): one launch each
         for (cn_layer *l : ctx->layers)
             if (l->trainable && !l->updated) launch_layer_update(ctx->stream, l, 1, r, nullptr);
@@ -2526,10 +2621,10 @@ void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
         cn_layer *last = nullptr;
         for (cn_layer *l : ctx->layers)
             if (l->trainable) { own_rates = own_rates || l->own_lr >= 0.f; last = l; }
-        if (!own_rates) launch_flat(ctx, r, 0, ctx->total, r.lr, attach ? ctx->ev_sgd : nullptr);
+        if (!own_rates) launch_flat(ctx, r, 0, ctx->total, r.lr, clip, attach ? ctx->ev_sgd : nullptr);
         else            // a layer with a "learningRate" of its own: one launch per layer
             for (cn_layer *l : ctx->layers)
-                if (l->trainable) launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), (attach && l == last) ? ctx->ev_sgd : nullptr);
+                if (l->trainable) launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), clip, (attach && l == last) ? ctx->ev_sgd : nullptr);
     }
     for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
     if (grouped) {
@@ -2541,7 +2636,7 @@ void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
             if (fused) set_pack_update(grp, ad, 1, r, l);
             l->dirty = false; l->pack_pending = false;
         }
-        launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr);
+        launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr, fused ? clip : nullptr);
     } else if (ctx->overlap) {
         // (more layers than one group launch takes: the first trainable layer's copy on this stream, its forward pass
         // is next; the others on the side stream, each layer's forward pass waits for them in repack())

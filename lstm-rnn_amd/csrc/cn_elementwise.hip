@@ -96,11 +96,21 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
     }
     return t;
 }
+// Clipping on (UPD = 4, include/currennt_hip.h, section Gradient clipping): an update rule with the record of grad_norm_kernel in
+// front of it.  Types and an UPD of their own: the forms without it are instantiated as before.
+template <class B> struct PackClip : B { float scale; int state; };
 template <int UPD, class U>
 __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
                                             const PackFold *fold = nullptr, long foff = 0)
 {
-    if constexpr (UPD != 0) {
+    if constexpr (UPD == 4) {              // the gradient from the flat weightUpdates (as UPD = 1), scaled or the step skipped
+        if (u.state == CLIP_SKIP) return u.w_rw[fi];          // (the operand copies are still written, from the unchanged weight)
+        float g = u.wu[fi];
+        if (u.state == CLIP_SCALE) g = __fmul_rn(u.scale, g);
+        const float v = apply_update(u, fi, g);
+        u.w_rw[fi] = v;
+        return v;
+    } else if constexpr (UPD != 0) {
         float g;
         if constexpr (UPD == 3) {          // deterministic mode: this launch adds the stored partial sums itself (a variant of its own:
             if (fold->nparts) g = pack_fold(*fold, foff);        // with the loop inside the UPD = 2 code every launch of the default mode
@@ -304,7 +314,31 @@ __global__ void pack_group_adam_kernel(PackGroup grp, PackAdam ad)
         else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
     }
 }
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam)
+// ... and of update mode 1 with clipping on: the record is read once per workgroup (the norm launch is in front on the stream)
+template <bool F32, bool ADAM>
+__global__ void pack_group_clip_kernel(PackGroup grp, PackAdam ad, const ClipRecord *rec)
+{
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) i = k;
+    const PackItem it = grp.item[i];
+    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
+    const float scale = rec->scale; const int state = rec->state;
+    const PackUpd base{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
+    if constexpr (ADAM) {
+        float *v = ad.v[0];
+#pragma unroll
+        for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k == i) v = ad.v[k];
+        const PackClip<PackUpdAdam> upd{{base, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t}, scale, state};
+        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
+        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
+    } else {
+        const PackClip<PackUpd> upd{base, scale, state};
+        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
+        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
+    }
+}
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip)
 {
     int blocks = 0;
     for (int i = 0; i < grp.n; ++i) {
@@ -315,6 +349,18 @@ void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done,
         grp.first[i] = blocks; blocks += b;
     }
     if (blocks == 0) return;
+    if (clip) {
+        const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
+        const PackAdam a = ad ? *adam : PackAdam{};
+        if (ad) {
+            if (f32) hipExtLaunchKernelGGL((pack_group_clip_kernel<true, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
+            else     hipExtLaunchKernelGGL((pack_group_clip_kernel<false, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
+        } else {
+            if (f32) hipExtLaunchKernelGGL((pack_group_clip_kernel<true, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
+            else     hipExtLaunchKernelGGL((pack_group_clip_kernel<false, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
+        }
+        return;
+    }
     if (grp.item[0].optimizer == PACK_OPT_ADAM) {
         if (f32) hipExtLaunchKernelGGL(pack_group_adam_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
         else     hipExtLaunchKernelGGL(pack_group_adam_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
@@ -1588,6 +1634,115 @@ void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, s
     if (n == 0) return;
     int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipExtLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// global gradient-norm clipping (include/currennt_hip.h, section Gradient clipping)
+// ---------------------------------------------------------------------------------------------
+// S = sum g[i]^2 in double, in the order the header states: lane k = i mod CLIP_LANES adds its squares in ascending i, then
+// neighbouring lanes are added pairwise, level by level.  Thread t of the CLIP_WGS x 256 grid owns lanes 4t .. 4t + 3: one 16-byte
+// load per row of CLIP_LANES floats, eight rows' loads in flight in front of the eight dependent adds (the add chain of a lane is
+// the order; the loads are not part of it).  g^2 is exact in double, so the fused multiply-add rounds what a separate add would.
+// Entries behind n count as +0.0, which changes no sum (a square is never -0).
+// Cross-workgroup part: the last workgroup to arrive adds the CLIP_WGS sums (rowstat_reduce_wave's hand-off: agent-scope stores
+// drained by the counting thread in front of the counter, the reader acquires) -- one launch, not two, in front of the update on
+// the tail of the step.  The finishing thread writes {norm, scale, state} and the counters.
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float *__restrict__ g, size_t n, float max_norm, ClipRecord *rec)
+{
+    typedef __attribute__((ext_vector_type(4))) float f32x4;
+    constexpr int UNROLL = 8;
+    const size_t lane0 = 4 * ((size_t)blockIdx.x * 256 + threadIdx.x);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (size_t base = lane0; base < n; base += (size_t)UNROLL * CLIP_LANES) {
+        f32x4 v[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const size_t i = base + (size_t)u * CLIP_LANES;           // (n is a multiple of 4: a group of four is inside or outside)
+            v[u] = i < n ? *(const f32x4 *)(g + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const double d0 = v[u][0], d1 = v[u][1], d2 = v[u][2], d3 = v[u][3];
+            a0 = __fma_rn(d0, d0, a0); a1 = __fma_rn(d1, d1, a1); a2 = __fma_rn(d2, d2, a2); a3 = __fma_rn(d3, d3, a3);
+        }
+    }
+    __shared__ double sh[256];
+    sh[threadIdx.x] = __dadd_rn(__dadd_rn(a0, a1), __dadd_rn(a2, a3));
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {            // level by level over neighbours: w results, result t = pair (2t, 2t + 1)
+        double x = 0.0;
+        if (threadIdx.x < w) x = __dadd_rn(sh[2 * threadIdx.x], sh[2 * threadIdx.x + 1]);
+        __syncthreads();
+        if (threadIdx.x < w) sh[threadIdx.x] = x;
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(&rec->part[blockIdx.x], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (the partial must have arrived before this workgroup is counted: see rowstat_reduce_wave)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (__hip_atomic_fetch_add(&rec->arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != CLIP_WGS - 1) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    double p[CLIP_WGS];
+#pragma unroll
+    for (int k = 0; k < CLIP_WGS; ++k) p[k] = __hip_atomic_load(&rec->part[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int w = CLIP_WGS / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int k = 0; k < w; ++k) p[k] = __dadd_rn(p[2 * k], p[2 * k + 1]);
+    const double S = p[0];
+    const float norm = (float)__dsqrt_rn(S);       // correctly rounded in double, rounded once to float
+    int state = CLIP_NONE; float scale = 1.0f;
+    if (!(S <= 1.7976931348623157e308)) { state = CLIP_SKIP; scale = 0.0f; }          // inf or NaN: nothing is applied
+    else if (norm > max_norm) { state = CLIP_SCALE; scale = __fdiv_rn(max_norm, norm); }
+    rec->norm = norm; rec->scale = scale; rec->state = state;
+    rec->updates += 1;
+    if (state == CLIP_SKIP) rec->skipped += 1;
+    else {
+        if (state == CLIP_SCALE) rec->clipped += 1;
+        if (norm < __builtin_inff() && norm > rec->max_seen) rec->max_seen = norm;     // (the largest FINITE norm)
+    }
+    __hip_atomic_store(&rec->arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (zero again for the next launch)
+}
+void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, ClipRecord *rec)
+{
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(CLIP_WGS), dim3(256), 0, s, g, n, max_norm, rec);
+}
+
+// sgd_kernel / adam_kernel behind the record (kernels of their own: the plain ones keep their code)
+__global__ void sgd_clip_kernel(float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec)
+{
+    const int state = rec->state; const float scale = rec->scale;
+    if (state == CLIP_SKIP) return;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float g = wu[i];
+        if (state == CLIP_SCALE) g = __fmul_rn(scale, g);
+        const float dl = __fsub_rn(__fmul_rn(mom, wd[i]), __fmul_rn(lr, g));
+        wd[i] = dl;
+        w[i] = __fadd_rn(w[i], dl);
+    }
+}
+void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done)
+{
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    hipExtLaunchKernelGGL(sgd_clip_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, rec);
+}
+__global__ void adam_clip_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a, const ClipRecord *rec)
+{
+    const int state = rec->state; const float scale = rec->scale;
+    if (state == CLIP_SKIP) return;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float g = wu[i];
+        if (state == CLIP_SCALE) g = __fmul_rn(scale, g);
+        w[i] = adam_step(w[i], g, m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
+    }
+}
+void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done)
+{
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    hipExtLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, rec);
 }
 
 }  // namespace cn

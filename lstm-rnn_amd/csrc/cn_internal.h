@@ -253,7 +253,10 @@ enum { PACK_OPT_SGD = 0, PACK_OPT_ADAM = 1 };
 // they are): item i's second moments, and the scalars every layer shares (include/currennt_hip.h, cn_adam_update)
 struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
 // adam: required when the group's items say PACK_OPT_ADAM (all items of a group name the same optimizer)
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr);
+// clip (nullable; update == 1 items only): the record of grad_norm_kernel -- kernels of their own again (pack_group_clip_kernel),
+// the instantiations without it keep their code
+struct ClipRecord;
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr, const ClipRecord *clip = nullptr);
 void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const float *w,
                     void *W, void *WT, float *bias_p);
 void launch_ff_unpack_grads(hipStream_t s, const FfGeom &g, float bias, float *dW, float *colsum, float *wu, hipEvent_t done = nullptr);
@@ -360,6 +363,28 @@ void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, f
 struct AdamScalars { float b1, omb1, b2, omb2, alpha_t, eps_t; };
 void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done = nullptr);
 void launch_accumulate(hipStream_t s, float *acc, const float *wu, size_t n, bool first);
+
+// ---- global gradient-norm clipping (include/currennt_hip.h, section Gradient clipping) ----
+// The sum of squares runs over CLIP_LANES strided lanes (lane k: g[k]^2, g[k + L]^2, ... in ascending order, in double), then a
+// tree over NEIGHBOURING lanes.  A thread of grad_norm_kernel owns four neighbouring lanes (one 16-byte load per row), a
+// workgroup 1024, so the tree's first two levels are a thread's registers, the next eight the workgroup's LDS and the last four
+// the CLIP_WGS workgroup sums, which the last workgroup to arrive adds.
+constexpr int CLIP_LANES = 16384, CLIP_WGS = 16;
+enum { CLIP_NONE = 0, CLIP_SCALE = 1, CLIP_SKIP = 2 };
+// The device record of a context with clipping on (zeroed at allocation).  {norm, scale, state} is what the update launches
+// that follow read; the counters are the finishing thread's; part / arrivals belong to the hand-off (arrivals is zero between
+// launches).
+struct ClipRecord {
+    float norm, scale; int state; float max_seen;
+    long long updates, clipped, skipped;
+    unsigned arrivals, pad;
+    double part[CLIP_WGS];
+};
+// one pass over g[0 .. n) (n a multiple of 4, g 16-byte aligned: the weightUpdates part of the arena); fills *rec
+void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, ClipRecord *rec);
+// launch_sgd / launch_adam with the record in front of the rule: g' = scale * g on CLIP_SCALE, nothing touched on CLIP_SKIP
+void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done = nullptr);
+void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done = nullptr);
 
 // ---- CTC post output layer (cn_ctc.hip; the arithmetic is stated in that file's header) -----------------------------------------
 struct CtcArgs {

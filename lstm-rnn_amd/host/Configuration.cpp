@@ -1,6 +1,7 @@
 #include "Configuration.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <fstream>
 #include <sstream>
@@ -46,6 +47,8 @@ const char *Configuration::usage()
            "            --max_epochs N --max_epochs_no_best N --validate_every N --test_every N --learning_rate X\n"
            "            --optimizer steepest_descent|adam (adam: --learning_rate is its step size, --momentum is ignored)\n"
            "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
+           "            --max_grad_norm X (clip every update's gradient to this global L2 norm; a step with a non-finite gradient is\n"
+           "                      skipped; default 0 = off)\n"
            "            --momentum X --save_network F --train_file F[,F] --val_file F --test_file F --truncate_seq N\n"
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
@@ -87,6 +90,11 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "adam_beta1") m_adamBeta1 = (real_t)atof(v.c_str());
     else if (key == "adam_beta2") m_adamBeta2 = (real_t)atof(v.c_str());
     else if (key == "adam_epsilon") m_adamEpsilon = (real_t)atof(v.c_str());
+    else if (key == "max_grad_norm") {
+        m_maxGradNorm = (real_t)atof(v.c_str());
+        if (!(m_maxGradNorm >= 0) || std::isinf(m_maxGradNorm))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --max_grad_norm must be finite and >= 0 (0 = off)");
+    }
     else if (key == "save_network") m_trainedNetwork = v;
     else if (key == "train_file") m_trainingFiles = splitList(v);
     else if (key == "val_file") m_validationFiles = splitList(v);

@@ -39,6 +39,9 @@ public:
     real_t adamBeta1() const { return m_adamBeta1; }
     real_t adamBeta2() const { return m_adamBeta2; }
     real_t adamEpsilon() const { return m_adamEpsilon; }
+    // --max_grad_norm: bound on the global L2 norm of an update's gradient (include/currennt_hip.h, section Gradient clipping;
+    // no counterpart in the reference); 0 = off
+    real_t maxGradNorm() const { return m_maxGradNorm; }
     real_t featurePeriod() const { return m_featurePeriod; }
     real_t trainingFraction() const { return m_trainingFraction; }
     real_t validationFraction() const { return m_validationFraction; }
@@ -98,6 +101,7 @@ private:
     real_t m_learningRate = 1e-5f, m_momentum = 0.9f, m_featurePeriod = 10, m_trainingFraction = 1, m_validationFraction = 1,
            m_testFraction = 1, m_weightsUniformMin = -0.1f, m_weightsUniformMax = 0.1f, m_weightsNormalSigma = 0.1f, m_weightsNormalMean = 0;
     real_t m_adamBeta1 = 0.9f, m_adamBeta2 = 0.999f, m_adamEpsilon = 1e-8f;
+    real_t m_maxGradNorm = 0;
     std::string m_optimizer = "steepest_descent";
     feedforwardformat_type_t m_feedForwardFormat = FORMAT_SINGLE_CSV;
     std::string m_networkFile = "network.jsn", m_trainedNetwork = "trained_network.jsn", m_feedForwardOutputFile = "ff_output.csv";

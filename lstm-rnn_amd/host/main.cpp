@@ -350,6 +350,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             } else {
                 printf("Momentum:                  %g\n\n", (double)config.momentum());
             }
+            if (config.maxGradNorm() > 0) printf("Max. gradient norm:        %g\n\n", (double)config.maxGradNorm());
+            optimizer.setMaxGradNorm(config.maxGradNorm());
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
             // every rank its own masks: seed = --random_seed + rank * 0x9E3779B97F4A7C15 (mod 2^64)
             optimizer.setDropoutSeed((uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull);
@@ -402,6 +404,11 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                         if (root) saveNetwork(neuralNetwork, base + ".best.jsn");
                     }
                 } else infoRows += printfRow("        \n");
+                // --max_grad_norm: one line behind the epoch's row (not part of the table, nor of the rows an autosave keeps)
+                if (config.maxGradNorm() > 0) {
+                    const optimizers::Optimizer::ClipStats cs = optimizer.takeClipStats();
+                    printf("         gradient norm: max %g, clipped %lld, skipped %lld of %lld updates\n", (double)cs.maxNormSeen, cs.clipped, cs.skipped, cs.updates);
+                }
                 if (config.autosave() && root) saveState(config, neuralNetwork, optimizer, infoRows);  // main.cpp:275-277
             }
             printf("\n");

@@ -358,6 +358,20 @@ void SteepestDescentOptimizer::_updateWeights()
     }
 }
 
+void Optimizer::setMaxGradNorm(real_t maxNorm)
+{
+    hipCheck(cn_ctx_set_grad_clip(m_neuralNetwork.context(), maxNorm), m_neuralNetwork.context());
+}
+
+Optimizer::ClipStats Optimizer::takeClipStats()
+{
+    ClipStats s{};
+    int64_t updates = 0, clipped = 0, skipped = 0;
+    hipCheck(cn_ctx_grad_clip_stats(m_neuralNetwork.context(), nullptr, nullptr, &updates, &clipped, &skipped, &s.maxNormSeen, 1), m_neuralNetwork.context());
+    s.updates = updates; s.clipped = clipped; s.skipped = skipped;
+    return s;
+}
+
 AdamOptimizer::AdamOptimizer(NeuralNetwork &neuralNetwork, data_sets::DataSet &trainingSet, data_sets::DataSet &validationSet,
                              data_sets::DataSet &testSet, int maxEpochs, int maxEpochsNoBest, int validateEvery, int testEvery,
                              real_t learningRate, real_t beta1, real_t beta2, real_t epsilon, bool hybridOnlineBatch)

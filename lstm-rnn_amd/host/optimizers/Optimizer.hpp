@@ -26,6 +26,11 @@ public:
     // pass = (epoch << 32) | index of the fraction in the epoch -- derived, not stored, so --continue resumes the same masks;
     // validation and test passes do not drop
     void setDropoutSeed(uint64_t seed) { m_dropoutSeed = seed; }
+    // --max_grad_norm (include/currennt_hip.h, section Gradient clipping): the bound is set once, 0 = off; the device keeps the
+    // statistics, takeClipStats reads and resets them (one synchronising call, once per epoch)
+    void setMaxGradNorm(real_t maxNorm);
+    struct ClipStats { float maxNormSeen; long long updates, clipped, skipped; };
+    ClipStats takeClipStats();
     // autosave / --continue (Optimizer.cu:326-358)
     virtual void exportState(json::Value *jsonDoc) const;
     virtual void importState(const json::Value &jsonDoc);

@@ -473,6 +473,20 @@ class NeuralNetwork:
         64-bit (seed, pass) of their masks.  The library keeps no clock: a training loop hands a new pass per fraction."""
         B.check(self.lib.cn_ctx_set_dropout_pass(self.ctx, 1 if enable else 0, int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1)), self.ctx)
 
+    def set_grad_clip(self, max_norm):
+        """cn_ctx_set_grad_clip: clip every update's gradient to this global L2 norm (include/currennt_hip.h, section Gradient
+        clipping); 0 turns it off, a bound nothing reaches (FLT_MAX) only monitors the norm."""
+        B.check(self.lib.cn_ctx_set_grad_clip(self.ctx, float(max_norm)), self.ctx)
+
+    def grad_clip_stats(self, reset=False):
+        """cn_ctx_grad_clip_stats: dict(last_norm, last_scale, updates, clipped, skipped, max_norm_seen); zeros with clipping off."""
+        f = [C.c_float() for _ in range(3)]
+        n = [C.c_int64() for _ in range(3)]
+        B.check(self.lib.cn_ctx_grad_clip_stats(self.ctx, C.byref(f[0]), C.byref(f[1]), C.byref(n[0]), C.byref(n[1]), C.byref(n[2]),
+                                                C.byref(f[2]), 1 if reset else 0), self.ctx)
+        return dict(last_norm=np.float32(f[0].value), last_scale=np.float32(f[1].value), updates=n[0].value, clipped=n[1].value,
+                    skipped=n[2].value, max_norm_seen=np.float32(f[2].value))
+
     def accumulate_updates(self, first):
         """Batch learning (Optimizer.cu:72-85): add this fraction's weightUpdates of all layers to the epoch sum on the device
         (`first`: copy instead of add)."""
