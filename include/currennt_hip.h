@@ -284,7 +284,9 @@ int  cn_sgd_update_all(cn_ctx *ctx, float learning_rate, float momentum);
  * weights are last read by its own backward pass, so the layers below never see the difference; only a cn_layer_read of
  * CN_BUF_WEIGHTS between the two calls would.  The following cn_sgd_update_all(ctx, same values) -- or cn_sgd_update per
  * layer -- completes the step (waits, handles layers no backward call reached) and disarms; it is an error to start another
- * backward pass before it.  Not for batch learning (the epoch sum is formed first) nor with weight noise.        [async] */
+ * backward pass before it.  Not for batch learning (the epoch sum is formed first).  Weight noise generated on the device
+ * (cn_ctx_set_weight_noise) goes with it; the reference's host protocol, which uploads noisy weights and restores them behind
+ * the backward pass, does not.                                                                                    [async] */
 int  cn_ctx_arm_update(cn_ctx *ctx, float learning_rate, float momentum);
 
 /* Batch learning (`--stochastic false`): Optimizer.cu:72-85 sums the fractions' weightUpdates of an epoch on the DEVICE
@@ -466,6 +468,38 @@ int  cn_ctx_set_grad_clip(cn_ctx *ctx, float max_norm);
  * reports zeros.                                                                                                      [sync] */
 int  cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, int64_t *updates, int64_t *clipped, int64_t *skipped,
                             float *max_norm_seen, int reset);
+
+/* ---- Weight noise (--weight_noise_sigma, Optimizer.cu:58-84: the reference's only regulariser) ----------------------------------
+ * Gaussian noise on the weights, seen by the backward pass alone: every backward product with a weight in it reads w' = w + n, while
+ * the forward pass, the error and the update see the clean weights.  The reference draws the noise on the host; here it is
+ * generated on the device, straight into a second set of the operand copies a backward pass reads (an LSTM layer's transposed
+ * input weights, transposed recurrent weights and peephole weights; a dense layer's transposed weights).  The bias weights are
+ * read by no backward pass.  CN_BUF_WEIGHTS, the parameter arena and the copies a forward pass reads never hold noise: nothing
+ * needs restoring, and a forward pass behind a noisy backward pass without an update is bit-equal to one with noise off.
+ *
+ * The noise.  For a trainable layer with creation ordinal `ordinal` (as for dropout) and flat weight index k in the reference
+ * layout, 0 <= k < cn_layer_weight_count:
+ *      (w0,w1,w2,w3) = Philox4x32-10( counter = (k >> 2, 0, pass_lo, pass_hi),
+ *                                     key     = ((seed_lo + ordinal) mod 2^32, seed_hi XOR 0x6E6F6973) )
+ *      pair p = (k & 3) >> 1 uses words (w[2p], w[2p+1]) = (a, b)
+ *      u1 = (float)(2*(a >> 9) + 1) * 2^-24        in (0,1), exact in fp32
+ *      t  = (float)(2*(b >> 9) + 1) * 2^-23        in (0,2), exact in fp32   (= 2*u2)
+ *      r  = sqrt_rn( mul_rn(-2, logf(u1)) )
+ *      z  = mul_rn(r, (k & 1) ? sinpif(t) : cospif(t))        Box-Muller, both outputs of a pair used
+ *      n  = mul_rn(sigma, z)
+ *      w' = add_rn(w, n)                                      then rounded ONCE to the operand type (CN_PREC_BF16: to nearest even)
+ * Every *_rn is a single fp32 operation rounded to nearest, no contraction; the square root is correctly rounded; logf, sinpif and
+ * cospif are the device library's.  The key's XOR constant ("nois") keeps the stream apart from the dropout masks of the same
+ * seed.  The noise is a function of (seed, pass, ordinal, k, sigma) alone: not of any padding, the precision mode, the kernels
+ * chosen or the rank.  Padding entries of the noisy copies are exactly zero.
+ *
+ * Works with both update rules, armed updates (the fused per-layer update runs behind a noisy backward pass: it rebuilds the
+ * clean copies only), clipping, dropout, the deterministic mode, batch learning and a bound communicator, in all three precisions.
+ * With noise off the library launches exactly what it launches without this call and allocates nothing for it. */
+/* sigma == 0: off, and a fresh context is off.  Negative, NaN or infinite: CN_ERR_BAD_ARG.  `seed` and `pass` are the caller's (the
+ * library keeps no clock).  Each layer's cn_layer_backward uses the triple in force when it is called.  The first non-zero sigma
+ * that reaches a backward pass allocates the noisy copies.                                                        [async] */
+int  cn_ctx_set_weight_noise(cn_ctx *ctx, float sigma, uint64_t seed, uint64_t pass);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,12 @@ int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int 
  * when that pass did not drop.  [sync] */
 int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count);
 
+/* The weights a layer's last backward pass read (include/currennt_hip.h, section Weight noise): gathered back from the noisy
+ * operand copies into the flat reference layout and widened to float; count = cn_layer_weight_count.  Bias entries, which no
+ * backward pass reads, are the clean weights.  CN_ERR_STATE when that pass had no noise, and when any pad entry of a noisy copy is
+ * not exactly 0.  [sync] */
+int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count);
+
 #ifdef __cplusplus
 }
 #endif

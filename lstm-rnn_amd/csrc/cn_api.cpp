@@ -7,6 +7,7 @@
 //   softmax forward SoftmaxLayer.cu:250-315 backward :317-353
 //   post output     MulticlassClassificationLayer.cu:159-240, SsePostOutputLayer.cu:114-155
 #include "cn_internal.h"
+#include "cn_noise_unpack.h"
 #include "../../include/currennt_hip_debug.h"
 
 #include <dlfcn.h>
@@ -189,6 +190,14 @@ struct cn_ctx {
     uint64_t drop_seed = 0, drop_pass = 0;
     int next_ordinal = 0;                 // layers created so far (cn_layer::ordinal)
 
+    // cn_ctx_set_weight_noise (include/currennt_hip.h, section Weight noise): the triple the backward passes that follow go by
+    float noise_sigma = 0.f;              // 0: off
+    uint64_t noise_seed = 0, noise_pass = 0;
+    // option noise_ahead: the sets were generated on the side stream beside the forward pass; ev_noise completes with them and
+    // the first backward pass that reads a set makes the main stream wait for it (noise_wait)
+    hipEvent_t ev_noise_fork = nullptr, ev_noise = nullptr;
+    bool noise_wait = false;
+
     // parameter arena [weights | weightUpdates | weightDeltas]
     bool finalized = false;
     float *arena = nullptr;
@@ -261,7 +270,13 @@ struct cn_layer {
     // packed copies
     void *Win = nullptr, *WinT = nullptr, *Wrec = nullptr, *WrecT = nullptr;
     float *bias_p = nullptr, *peep_p = nullptr;
-    float *grad_block = nullptr;          // dWin | dWrec | dbias | dpeep  (or dW | colsum), zeroed per backward
+    // weight noise: the noisy set of the copies a backward pass reads (WinT, and WrecT / peep_p of an LSTM layer), allocated by the
+    // first backward pass with a non-zero sigma.  noisy_ready: the set holds the noise of the triple in force and of the weights as
+    // they are, and this layer's backward pass has not consumed it yet; noise_used: the last backward pass read the set.
+    void *nWinT = nullptr, *nWrecT = nullptr;
+    float *npeep = nullptr;
+    bool noisy_ready = false, noise_used = false;
+    float *grad_block = nullptr;         // dWin | dWrec | dbias | dpeep  (or dW | colsum), zeroed per backward
     size_t grad_block_floats = 0;
     float *dWin = nullptr, *dWrec = nullptr, *dbias = nullptr, *dpeep = nullptr;
 
@@ -877,7 +892,7 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule
     it.wu_rw = l->wu; it.g_in = l->dWin; it.g_rec = l->dWrec; it.g_bias = l->dbias; it.g_peep = l->dpeep;
     if (folds) { it.update = 3; it.f_in = folds[0]; it.f_rec[0] = folds[1]; it.f_rec[1] = folds[2]; it.f_bias = folds[3]; }
     launch_pack_group(st, c->f32, grp, done, r.adam ? &ad : nullptr);
-    l->dirty = false; l->pack_pending = false; l->updated = true;
+    l->dirty = false; l->pack_pending = false; l->updated = true; l->noisy_ready = false;
 }
 // armed update without a communicator: unpack + update + operand copies ride on ONE launch behind the gradient GEMMs
 bool armed_fused(const cn_layer *l) { return l->ctx->armed && !l->ctx->has_comm(); }
@@ -910,6 +925,78 @@ void mask_handed_back_error(cn_layer *l)
     if (!l->dropped) return;
     Timed tm(l->ctx, KC_OTHER);
     launch_dropout_bwd(l->ctx->stream, l->drop, l->prev->err);
+}
+
+// ---- weight noise (include/currennt_hip.h, section Weight noise) ----
+// The noisy set of every trainable layer whose set is stale, in ONE launch on `st`, from the triple in force and the flat weights
+// as they are (the first use allocates the sets).
+void generate_noisy(cn_ctx *c, hipStream_t st)
+{
+    {
+        Timed tm(c, KC_OTHER, st);
+        PackGroup grp{};
+        PackNoise nz{};
+        nz.k1 = (uint32_t)(c->noise_seed >> 32) ^ 0x6E6F6973u;
+        nz.pass_lo = (uint32_t)c->noise_pass; nz.pass_hi = (uint32_t)(c->noise_pass >> 32);
+        nz.sigma = c->noise_sigma;
+        for (cn_layer *o : c->layers) {
+            if (!o->trainable || o->noisy_ready) continue;
+            if (!o->nWinT) {
+                const size_t e = c->esz();
+                if (o->lstm) {
+                    const size_t R = (size_t)o->dirs * 4 * o->Hp;
+                    o->nWinT = dalloc(o, R * o->Pp * e); o->nWrecT = dalloc(o, R * o->Hp * e);
+                    o->npeep = (float *)dalloc(o, (size_t)o->dirs * 3 * o->Hp * sizeof(float));
+                } else o->nWinT = dalloc(o, (size_t)o->Lp * o->Pp * e);
+            }
+            PackItem &it = add_pack_item(grp, o);
+            it.Win = nullptr; it.Wrec = nullptr; it.bias_p = nullptr;
+            it.WinT = o->nWinT; it.WrecT = o->nWrecT; it.peep_p = o->npeep;
+            nz.k0[grp.n - 1] = (uint32_t)c->noise_seed + (uint32_t)o->ordinal;
+            o->noisy_ready = true;
+            if (grp.n == PACK_GROUP_MAX) { launch_pack_group_noise(st, c->f32, grp, nz); grp.n = 0; }
+        }
+        if (grp.n) launch_pack_group_noise(st, c->f32, grp, nz);
+    }
+}
+// In front of a layer's backward kernels, on the main stream: does this pass read the noisy set of the layer's copies?  A stale
+// set is generated here, with every other stale one: the first backward call of a pass pays for all layers.  (The noise is a
+// function of the key and the flat weights, which no backward pass of the layers above changes for the layers below: an armed
+// update rewrites its own layer only, and marks that layer's set stale.)
+bool backward_noise(cn_layer *l)
+{
+    cn_ctx *c = l->ctx;
+    l->noise_used = c->noise_sigma != 0.f;
+    if (!l->noise_used) return false;
+    if (c->noise_wait) { HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_noise, 0)); c->noise_wait = false; }
+    if (!l->noisy_ready) generate_noisy(c, c->stream);
+    l->noisy_ready = false;               // consumed: the next pass of this layer has a set of its own generated
+    return true;
+}
+// Option noise_ahead, in front of the first trainable layer's forward pass: the key of the coming backward pass is known already
+// (cn_ctx_set_weight_noise precedes the pass), so the stale sets are generated on the side stream beside the forward pass.  The
+// side stream forks from the main stream here: behind the last update of the weights and the last backward kernels that read
+// the sets.  A triple or weights that change before the backward pass make the sets stale again, and backward_noise generates
+// them in place.
+void noise_ahead(cn_ctx *c)
+{
+    if (c->noise_sigma == 0.f || !c->overlap || !c->side || c->timing) return;
+    bool any = false;
+    for (cn_layer *o : c->layers) {
+        if (!o->trainable || o->noisy_ready) continue;
+        if (!o->nWinT) return;            // (the first generation allocates, on the main stream)
+        any = true;
+    }
+    if (!any) return;
+    if (!c->ev_noise) {
+        HIP_CHECK(hipEventCreateWithFlags(&c->ev_noise_fork, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&c->ev_noise, hipEventDisableTiming));
+    }
+    HIP_CHECK(hipEventRecord(c->ev_noise_fork, c->stream));
+    HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_noise_fork, 0));
+    generate_noisy(c, c->side);
+    HIP_CHECK(hipEventRecord(c->ev_noise, c->side));
+    c->noise_wait = true;
 }
 
 void lstm_forward(cn_layer *l)
@@ -950,6 +1037,7 @@ void lstm_backward(cn_layer *l)
     const int R = l->dirs * 4 * l->Hp, Hp = l->Hp, PS = c->PSp, N = c->N;
     const size_t e = c->esz();
     repack(l);
+    const bool noisy = backward_noise(l);   // every backward product with a weight in it then reads the noisy set: WrecT, peep, WinT
     bool fork_attached = false;
     // (the packed gradient accumulators are zero here: allocation clears them, the unpack kernel re-clears them)
     int det_grid = 0;
@@ -957,6 +1045,7 @@ void lstm_backward(cn_layer *l)
     {   // K5+K6+K7 and the bias / peephole sums of K9
         Timed tm(c, KC_REC_BWD);
         LstmRec r; lstm_rec_args(l, r); r.kname = l->kname[1];
+        if (noisy) { r.WrecT = l->nWrecT; r.peep = l->npeep; }
         if (c->det) { r.gpart = l->gpart; r.gpart_slots = l->gpart_slots; r.det_grid = &det_grid; }
         if (!launch_lstm_cluster(c->stream, c->prec, true, r, &c->xch_epoch)) {
             check_rec_lds(l, true);
@@ -971,7 +1060,7 @@ void lstm_backward(cn_layer *l)
     if (l->prev->trainable) {   // K8 (LstmLayer.cu:990-1009): one K = R product instead of 4*dirs
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
-        g.A = l->delta_op; g.lda = R; g.B = l->WinT; g.ldb = R;
+        g.A = l->delta_op; g.lda = R; g.B = noisy ? l->nWinT : l->WinT; g.ldb = R;
         g.C = l->prev->err; g.ldc = l->prev->Lp; g.bias = nullptr; g.act = ACT_IDENTITY;
         g.M = N; g.N = l->Pp; g.K = R;
         use_rowmap(c, g);
@@ -1075,6 +1164,7 @@ void ff_backward(cn_layer *l)
     cn_ctx *c = l->ctx;
     const int N = c->N;
     repack(l);
+    const bool noisy = backward_noise(l);
     if (c->det) ensure_det(l);
     FoldItem colfold{}; colfold.nparts = 0;       // deterministic mode: the column sums' fold rides on the gradient product's
     bool dummy_deltas_zero = false;               // (the row map's condition: every operand row of a dummy frame is zero)
@@ -1105,7 +1195,7 @@ void ff_backward(cn_layer *l)
     if (l->prev->trainable) {   // FeedForwardLayer.cu:188-198
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
-        g.A = l->delta_op; g.lda = l->Lp; g.B = l->WinT; g.ldb = l->Lp;
+        g.A = l->delta_op; g.lda = l->Lp; g.B = noisy ? l->nWinT : l->WinT; g.ldb = l->Lp;
         g.C = l->prev->err; g.ldc = l->prev->Lp; g.bias = nullptr; g.act = ACT_IDENTITY;
         g.M = N; g.N = l->Pp; g.K = l->Lp;
         if (dummy_deltas_zero) use_rowmap(c, g);
@@ -1236,6 +1326,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         if (ctx->side_slow) hipStreamSynchronize(ctx->side_slow);     // shared per device, never destroyed: masked_stream()
         if (ctx->ev_sgd) hipEventDestroy(ctx->ev_sgd);
         if (ctx->ev_ext) hipEventDestroy(ctx->ev_ext);
+        if (ctx->ev_noise) { hipEventDestroy(ctx->ev_noise); hipEventDestroy(ctx->ev_noise_fork); }
         if (ctx->copy) { hipStreamSynchronize(ctx->copy); hipStreamDestroy(ctx->copy); }
         if (ctx->comm_stream) hipStreamSynchronize(ctx->comm_stream);
         if (ctx->comm) { (void)rccl().CommDestroy(ctx->comm); ctx->comm = nullptr; }
@@ -1979,6 +2070,7 @@ int cn_layer_forward(cn_layer *layer)
         require_loaded(layer->ctx);
         finalize(layer->ctx);
         join_side(layer->ctx);
+        if (layer->trainable && !layer->prev->trainable && opt().noise_ahead) noise_ahead(layer->ctx);
         if (layer->lstm) lstm_forward(layer);
         else if (layer->trainable) ff_forward(layer);
         /* input and post output layers: no-op (InputLayer.cpp:62-65, SsePostOutputLayer.cu:134-137) */
@@ -2179,7 +2271,7 @@ int cn_layer_set_weights(cn_layer *layer, const float *host, int count)
         if (!c->finalized) { layer->pending_w.assign(host, host + count); return; }
         HIP_CHECK(hipMemcpyAsync(layer->w, host, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
-        layer->dirty = true;
+        layer->dirty = true; layer->noisy_ready = false;
     });
 }
 
@@ -2326,7 +2418,7 @@ int cn_ctx_param_arena(cn_ctx *ctx, void **weights, void **weight_updates, void 
 int cn_ctx_weights_touched(cn_ctx *ctx)
 {
     if (!ctx) { g_last_error = "cn_ctx_weights_touched: ctx is NULL"; return CN_ERR_BAD_ARG; }
-    for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
+    for (cn_layer *l : ctx->layers) if (l->trainable) { l->dirty = true; l->noisy_ready = false; }
     return CN_OK;
 }
 
@@ -2436,7 +2528,7 @@ static void update_layer(cn_layer *layer, const UpdateRule &r, const char *fn)
     }
     Timed tm(c, KC_OTHER);
     launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr, clip_record(c));
-    layer->dirty = true;
+    layer->dirty = true; layer->noisy_ready = false;
 }
 
 int cn_sgd_update(cn_layer *layer, float learning_rate, float momentum)
@@ -2576,6 +2668,66 @@ int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count)
     });
 }
 
+// ---- weight noise (include/currennt_hip.h, section Weight noise) ----
+int cn_ctx_set_weight_noise(cn_ctx *ctx, float sigma, uint64_t seed, uint64_t pass)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_weight_noise: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!(sigma >= 0.f) || std::isinf(sigma)) throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_set_weight_noise: sigma must be finite and >= 0 (0 = off)");
+        if (sigma != ctx->noise_sigma || seed != ctx->noise_seed || pass != ctx->noise_pass)
+            for (cn_layer *l : ctx->layers) l->noisy_ready = false;      // (sets generated ahead belong to the old triple)
+        ctx->noise_sigma = sigma; ctx->noise_seed = seed; ctx->noise_pass = pass;
+    });
+}
+
+int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_dbg_noisy_weights: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        if (!layer->trainable || !layer->noise_used) throw cn_error(CN_ERR_STATE, "cn_dbg_noisy_weights: the layer's last backward pass had no weight noise");
+        if (layer->noisy_ready) throw cn_error(CN_ERR_STATE, "cn_dbg_noisy_weights: the noisy copies have been generated again for a pass this layer has not run yet");
+        if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_dbg_noisy_weights: count != weight count");
+        join_side(c);
+        // the copies as floats on the host (bf16 mode: widened there), then the gather in plain C++ (cn_noise_unpack.h)
+        auto fetch = [&](const void *dev, size_t n) {
+            std::vector<float> out(n);
+            if (!n) return out;
+            if (c->f32) HIP_CHECK(hipMemcpyAsync(out.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            else {
+                std::vector<uint16_t> raw(n);
+                HIP_CHECK(hipMemcpyAsync(raw.data(), dev, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+                HIP_CHECK(hipStreamSynchronize(c->stream));
+                for (size_t i = 0; i < n; ++i) { const uint32_t b = (uint32_t)raw[i] << 16; memcpy(&out[i], &b, 4); }
+            }
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            return out;
+        };
+        NoiseUnpackGeom g{};
+        g.lstm = layer->lstm ? 1 : 0; g.P = layer->P; g.Pp = layer->Pp; g.L = layer->size; g.Lp = layer->Lp;
+        g.dirs = layer->dirs; g.H = layer->H; g.Hp = layer->Hp;
+        g.prevH = layer->prev->lstm ? layer->prev->H : 0; g.prevHp = layer->prev->lstm ? layer->prev->Hp : 0;
+        g.prevDirs = layer->prev->lstm ? layer->prev->dirs : 0;
+        const size_t R = (size_t)layer->dirs * 4 * layer->Hp;
+        const std::vector<float> WinT = fetch(layer->nWinT, layer->lstm ? R * layer->Pp : (size_t)layer->Lp * layer->Pp);
+        std::vector<float> WrecT, peep;
+        if (layer->lstm) {
+            WrecT = fetch(layer->nWrecT, R * layer->Hp);
+            std::vector<float> p((size_t)layer->dirs * 3 * layer->Hp);     // (fp32 in every mode)
+            HIP_CHECK(hipMemcpyAsync(p.data(), layer->npeep, p.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            peep.swap(p);
+        }
+        std::vector<float> flat(count);
+        HIP_CHECK(hipMemcpyAsync(flat.data(), layer->w, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));   // the bias entries
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        const size_t bad = noise_unpack(g, WinT, WrecT, peep, flat);
+        if (bad) throw cn_error(CN_ERR_STATE, "cn_dbg_noisy_weights: " + std::to_string(bad) + " pad entries of the noisy copies are not exactly 0");
+        std::copy(flat.begin(), flat.end(), host);
+    });
+}
+
 // cn_sgd_update_all / cn_adam_update_all: one sequence for both rules (r.lr: the call's learning rate)
 // (in an unnamed namespace inside extern "C", as it has been: hipcc gives such a function an unmangled GLOBAL symbol, so the
 // library's dynamic symbol table lists "update_all" -- nobody declares it; dropping it is a change of the export list of its own)
@@ -2626,7 +2778,7 @@ void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
             for (cn_layer *l : ctx->layers)
                 if (l->trainable) launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), clip, (attach && l == last) ? ctx->ev_sgd : nullptr);
     }
-    for (cn_layer *l : ctx->layers) if (l->trainable) l->dirty = true;
+    for (cn_layer *l : ctx->layers) if (l->trainable) { l->dirty = true; l->noisy_ready = false; }
     if (grouped) {
         PackGroup grp{};
         PackAdam ad{};

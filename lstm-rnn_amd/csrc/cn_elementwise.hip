@@ -11,6 +11,7 @@
 //   optimizers/SteepestDescentOptimizer.cu:39-59 UpdateWeightFn  -> sgd_kernel
 //   (no counterpart in the reference) the Adam step of include/currennt_hip.h -> adam_kernel, pack_group_adam_kernel
 //   (no counterpart in the reference) dropout on a layer's input, include/currennt_hip.h -> dropout_fwd_kernel, dropout_bwd_kernel
+//   optimizers/Optimizer.cu:58-84 weight noise, drawn on the device (include/currennt_hip.h, section Weight noise) -> pack_group_noise_kernel
 #include "cn_internal.h"
 
 #include <float.h>
@@ -99,11 +100,27 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
 // Clipping on (UPD = 4, include/currennt_hip.h, section Gradient clipping): an update rule with the record of grad_norm_kernel in
 // front of it.  Types and an UPD of their own: the forms without it are instantiated as before.
 template <class B> struct PackClip : B { float scale; int state; };
+// Weight noise (UPD = 5, include/currennt_hip.h, section Weight noise): the fetch returns w + n(fi), and the bodies write the
+// copies a backward pass reads only.  A type and an UPD of their own again.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1);
+struct PackNoiseKey { uint32_t k0, k1, pass_lo, pass_hi; float sigma; };
+__device__ __forceinline__ float weight_noise(const PackNoiseKey &u, long k)
+{
+    const uint4 w = philox4x32_10(make_uint4((uint32_t)(k >> 2), 0u, u.pass_lo, u.pass_hi), u.k0, u.k1);
+    const bool second = (k & 2) != 0;                                          // the pair of this index: words (0, 1) or (2, 3)
+    const uint32_t a = second ? w.z : w.x, b = second ? w.w : w.y;
+    const float u1 = (float)(2u * (a >> 9) + 1u) * 0x1p-24f;                   // odd multiples of 2^-24 / 2^-23 below 2^24: exact
+    const float t = (float)(2u * (b >> 9) + 1u) * 0x1p-23f;
+    const float r = sqrtf(__fmul_rn(-2.0f, logf(u1)));                         // (sqrtf: the correctly rounded one, see adam_step)
+    const float z = __fmul_rn(r, (k & 1) ? sinpif(t) : cospif(t));
+    return __fmul_rn(u.sigma, z);
+}
 template <int UPD, class U>
 __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
                                             const PackFold *fold = nullptr, long foff = 0)
 {
-    if constexpr (UPD == 4) {              // the gradient from the flat weightUpdates (as UPD = 1), scaled or the step skipped
+    if constexpr (UPD == 5) return __fadd_rn(w[fi], weight_noise(u, fi));
+    else if constexpr (UPD == 4) {         // the gradient from the flat weightUpdates (as UPD = 1), scaled or the step skipped
         if (u.state == CLIP_SKIP) return u.w_rw[fi];          // (the operand copies are still written, from the unchanged weight)
         float g = u.wu[fi];
         if (u.state == CLIP_SCALE) g = __fmul_rn(u.scale, g);
@@ -146,7 +163,7 @@ __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, co
             float v = 0.f;
             if (j < H && i >= 0) v = pack_fetch<UPD>(w, upd, (long)gg * L * P + (long)d * H * P + (long)j * P + i, pg.g_in + (long)r * Pp + pc, 1.0f,
                                                      &pg.f_in, (long)r * Pp + pc);   // dWin[r][pc]
-            st_op<F32>(Win, (long)r * Pp + pc, v);
+            if constexpr (UPD != 5) st_op<F32>(Win, (long)r * Pp + pc, v);
             st_op<F32>(WinT, (long)pc * R + r, v);
         } else if (idx < nIn + nRec) {
             const long k = idx - nIn;
@@ -157,9 +174,10 @@ __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, co
                 v = pack_fetch<UPD>(w, upd, 4L * L * (P + 1) + (long)gg * L * H + (long)d * H * H + (long)j * H + i,
                                     pg.g_rec + ((long)d * 4 * Hp + 4 * j + gg) * Hp + i, 1.0f,
                                     &pg.f_rec[d & 1], (long)(4 * j + gg) * Hp + i);                                          // dWrec[d][4j + g][i]
-            st_op<F32>(Wrec, ((long)d * 4 * Hp + gg * Hp + j) * Hp + i, v);
+            if constexpr (UPD != 5) st_op<F32>(Wrec, ((long)d * 4 * Hp + gg * Hp + j) * Hp + i, v);
             st_op<F32>(WrecT, ((long)d * Hp + i) * 4 * Hp + 4 * j + gg, v);
         } else if (idx < nIn + nRec + nB) {
+            if constexpr (UPD == 5) continue;                 // (no backward pass reads the bias weights)
             const int k = idx - nIn - nRec;
             const int d = k / (4 * Hp), j = (k / 4) % Hp, gg = k % 4;
             bias_p[k] = (j < H) ? bias * pack_fetch<UPD>(w, upd, 4L * L * P + gg * L + d * H + j, pg.g_bias + k, 1.0f, &pg.f_bias, k) : 0.f;   // LstmLayer.cu:97-100
@@ -242,9 +260,10 @@ __device__ __forceinline__ void ff_pack_body(const FfGeom &g, float bias, const 
             const int j = idx / g.Pp, pc = idx % g.Pp;
             const int i = unpad_col(pc, g.P, g.prevH, g.prevHp, g.prevDirs);
             float v = (j < g.L && i >= 0) ? pack_fetch<UPD>(w, upd, (long)j * g.P + i, pg.g_in + (long)j * g.Pp + pc, 1.0f, &pg.f_in, (long)j * g.Pp + pc) : 0.f;
-            st_op<F32>(W, (long)j * g.Pp + pc, v);
+            if constexpr (UPD != 5) st_op<F32>(W, (long)j * g.Pp + pc, v);
             st_op<F32>(WT, (long)pc * g.Lp + j, v);
         } else {
+            if constexpr (UPD == 5) continue;
             const int j = idx - nW;
             bias_p[j] = (j < g.L) ? bias * pack_fetch<UPD>(w, upd, (long)g.L * g.P + j, pg.g_bias + j, bias, &pg.f_bias, j) : 0.f;            // FeedForwardLayer.cu:59
         }
@@ -338,7 +357,8 @@ __global__ void pack_group_clip_kernel(PackGroup grp, PackAdam ad, const ClipRec
         else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
     }
 }
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip)
+// the grid of a grouped launch: item i's workgroups are [grp.first[i], grp.first[i + 1]), one thread per packed entry up to 1024 groups
+static int pack_group_blocks(PackGroup &grp)
 {
     int blocks = 0;
     for (int i = 0; i < grp.n; ++i) {
@@ -348,6 +368,11 @@ void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done,
         int b = (int)((total + 255) / 256); if (b > 1024) b = 1024;
         grp.first[i] = blocks; blocks += b;
     }
+    return blocks;
+}
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip)
+{
+    const int blocks = pack_group_blocks(grp);
     if (blocks == 0) return;
     if (clip) {
         const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
@@ -368,6 +393,28 @@ void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done,
     }
     if (f32) hipExtLaunchKernelGGL(pack_group_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
     else     hipExtLaunchKernelGGL(pack_group_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
+}
+// Weight noise: the NOISY set of the copies a backward pass reads (items' WinT / WrecT / peep_p point there; Win, Wrec and bias_p
+// are not written), every layer of the group in one launch, each with its own key word 0 (seed + ordinal).
+template <bool F32>
+__global__ void pack_group_noise_kernel(PackGroup grp, PackNoise nz)
+{
+    int i = 0;
+    uint32_t k0 = nz.k0[0];
+#pragma unroll
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) { i = k; k0 = nz.k0[k]; }
+    const PackItem it = grp.item[i];
+    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
+    const PackNoiseKey key{k0, nz.k1, nz.pass_lo, nz.pass_hi, nz.sigma};
+    if (it.lstm) lstm_pack_body<F32, 5>(it.lg, it.bias, it.w, nullptr, it.WinT, nullptr, it.WrecT, nullptr, it.peep_p, grp.first[i], count, key);
+    else         ff_pack_body<F32, 5>(it.fg, it.bias, it.w, nullptr, it.WinT, nullptr, grp.first[i], count, key);
+}
+void launch_pack_group_noise(hipStream_t s, bool f32, PackGroup &grp, const PackNoise &nz)
+{
+    const int blocks = pack_group_blocks(grp);
+    if (blocks == 0) return;
+    if (f32) hipLaunchKernelGGL(pack_group_noise_kernel<true>, dim3(blocks), dim3(256), 0, s, grp, nz);
+    else     hipLaunchKernelGGL(pack_group_noise_kernel<false>, dim3(blocks), dim3(256), 0, s, grp, nz);
 }
 void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const float *w, void *W, void *WT, float *bias_p)
 {

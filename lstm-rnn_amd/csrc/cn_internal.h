@@ -48,7 +48,10 @@ enum Prec { P_BF16 = 0, P_F32 = 1, P_X3 = 2 };
     FLAG(no_loss_defer) FLAG(no_pack_group) FLAG(no_sgd_fuse) NUM(comm_cu_margin, 32)                                           \
     /* CTC: label cap per sequence of a CTC layer created afterwards (0: min(max_seq_length, 512)); A/B: the beta sweep as a     \
        launch of its own behind the alpha sweep instead of beside it */                                                          \
-    NUM(ctc_max_labels, 0) FLAG(ctc_serial_sweeps)
+    NUM(ctc_max_labels, 0) FLAG(ctc_serial_sweeps)                                                                                \
+    /* weight noise: generate the noisy operand copies on the side stream beside the forward pass (the key is known before it) \
+       instead of on the main stream in front of the first backward kernel */                                                    \
+    FLAG(noise_ahead)
 struct Options {
 #define CN_OPT_FIELD(name) int name = 0;
 #define CN_OPT_FIELD_NUM(name, dflt) long name = dflt;
@@ -257,6 +260,11 @@ struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
 // the instantiations without it keep their code
 struct ClipRecord;
 void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr, const ClipRecord *clip = nullptr);
+// Weight noise (include/currennt_hip.h, section Weight noise): the group's items name the NOISY copies in WinT / WrecT / peep_p
+// (the launch writes nothing else) and the clean flat weights in w; item i's key word 0 is k0[i] = seed_lo + ordinal, the other
+// key word (seed_hi ^ "nois"), counter words 2 and 3 and sigma are the group's.  Kernels of their own (pack_group_noise_kernel).
+struct PackNoise { uint32_t k0[PACK_GROUP_MAX]; uint32_t k1, pass_lo, pass_hi; float sigma; };
+void launch_pack_group_noise(hipStream_t s, bool f32, PackGroup &grp, const PackNoise &nz);
 void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const float *w,
                     void *W, void *WT, float *bias_p);
 void launch_ff_unpack_grads(hipStream_t s, const FfGeom &g, float bias, float *dW, float *colsum, float *wu, hipEvent_t done = nullptr);

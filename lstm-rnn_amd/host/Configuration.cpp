@@ -49,6 +49,9 @@ const char *Configuration::usage()
            "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
            "            --max_grad_norm X (clip every update's gradient to this global L2 norm; a step with a non-finite gradient is\n"
            "                      skipped; default 0 = off)\n"
+           "            --weight_noise_sigma X (Gaussian noise on the weights the backward pass reads; default 0 = off)\n"
+           "            --weight_noise_on_device B (generate that noise on the device from --random_seed, the epoch and the fraction\n"
+           "                      index: no host copies, the update stays overlapped, --continue resumes the same noise; default false)\n"
            "            --momentum X --save_network F --train_file F[,F] --val_file F --test_file F --truncate_seq N\n"
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
@@ -126,6 +129,7 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "dump_epochs") m_dumpEpochs = std::max(1, atoi(v.c_str()));
     else if (key == "input_noise_sigma") m_inputNoiseSigma = (real_t)atof(v.c_str());
     else if (key == "weight_noise_sigma") m_weightNoiseSigma = (real_t)atof(v.c_str());
+    else if (key == "weight_noise_on_device") m_weightNoiseOnDevice = toBool(key, v);
     else if (key == "input_left_context") m_inputLeftContext = atoi(v.c_str());
     else if (key == "input_right_context") m_inputRightContext = atoi(v.c_str());
     else if (key == "output_time_lag") m_outputTimeLag = atoi(v.c_str());

@@ -75,6 +75,9 @@ public:
     // data/noise options of Configuration.cpp:139-146,171-176
     real_t inputNoiseSigma() const { return m_inputNoiseSigma; }
     real_t weightNoiseSigma() const { return m_weightNoiseSigma; }
+    // --weight_noise_on_device: the noise of --weight_noise_sigma is generated on the device (include/currennt_hip.h, section
+    // Weight noise) instead of drawn on the host and uploaded; default false
+    bool weightNoiseOnDevice() const { return m_weightNoiseOnDevice; }
     int inputLeftContext() const { return m_inputLeftContext; }
     int inputRightContext() const { return m_inputRightContext; }
     int outputTimeLag() const { return m_outputTimeLag; }
@@ -91,6 +94,7 @@ private:
     int m_dumpEpochs = 1;
     bool m_dumpFractions = false, m_dumpLabels = false, m_autosave = false, m_autosaveBest = false;
     real_t m_inputNoiseSigma = 0, m_weightNoiseSigma = 0;
+    bool m_weightNoiseOnDevice = false;
     int m_inputLeftContext = 0, m_inputRightContext = 0, m_outputTimeLag = 0;
     std::string m_autosavePrefix, m_continueFile, m_serializedOptions;
     bool m_help = false, m_trainingMode = false, m_hybridOnlineBatch = false, m_shuffleFractions = false,

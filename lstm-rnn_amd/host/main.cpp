@@ -351,8 +351,11 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 printf("Momentum:                  %g\n\n", (double)config.momentum());
             }
             if (config.maxGradNorm() > 0) printf("Max. gradient norm:        %g\n\n", (double)config.maxGradNorm());
+            if (config.weightNoiseOnDevice()) printf("Weight noise:              sigma %g, generated on the device\n\n", (double)config.weightNoiseSigma());
             optimizer.setMaxGradNorm(config.maxGradNorm());
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
+            // --weight_noise_on_device: seed = --random_seed on every rank (no rank offset: the replicas stay identical)
+            optimizer.setWeightNoiseOnDevice(config.weightNoiseOnDevice(), (uint64_t)config.randomSeed());
             // every rank its own masks: seed = --random_seed + rank * 0x9E3779B97F4A7C15 (mod 2^64)
             optimizer.setDropoutSeed((uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull);
 

@@ -100,6 +100,12 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         if (anyDropout && calcWeightUpdates)
             hipCheck(cn_ctx_set_dropout_pass(m_neuralNetwork.context(), 1, m_dropoutSeed, ((uint64_t)m_curEpoch << 32) | (fractionIndex & 0xFFFFFFFFull)),
                      m_neuralNetwork.context());
+        // weight noise generated on the device: the key of this fraction's backward pass (validation and test passes run none)
+        const bool deviceNoise = calcWeightUpdates && m_weightNoiseOnDevice && m_weightNoiseSigma > 0;
+        if (deviceNoise)
+            hipCheck(cn_ctx_set_weight_noise(m_neuralNetwork.context(), m_weightNoiseSigma, m_weightNoiseSeed,
+                                             ((uint64_t)m_curEpoch << 32) | (fractionIndex & 0xFFFFFFFFull)), m_neuralNetwork.context());
+        const bool hostNoise = m_weightNoiseSigma > 0 && !m_weightNoiseOnDevice;
         ++fractionIndex;
         m_neuralNetwork.loadSequences(frac);
         m_neuralNetwork.computeForwardPass();
@@ -122,9 +128,11 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         if (calcWeightUpdates) {
             // weight noise: the forward pass above used the clean weights, the backward pass runs on noisy ones
             // and the clean weights come back before the update (Optimizer.cu:58-68, :82-84).  The noise is
-            // drawn on the host like the reference's (TrainableLayer.cu:188-209), std::mt19937 instead of boost's.
+            // drawn on the host like the reference's (TrainableLayer.cu:188-209), std::mt19937 instead of boost's -- unless
+            // --weight_noise_on_device: then the library generates it into the copies the backward pass reads (set above),
+            // nothing is uploaded or restored and the update may be armed.
             std::vector<Hip::real_vector> origWeights(ls.size());
-            if (m_weightNoiseSigma > 0) {
+            if (hostNoise) {
                 std::normal_distribution<real_t> dist(0.0f, m_weightNoiseSigma);
                 for (size_t i = 1; i + 1 < ls.size(); ++i) {
                     layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
@@ -135,9 +143,9 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
                     layer->setWeights(noisy);
                 }
             }
-            if (m_hybridOnlineBatch && !(m_weightNoiseSigma > 0)) _armUpdate();
+            if (m_hybridOnlineBatch && !hostNoise) _armUpdate();
             m_neuralNetwork.computeBackwardPass();
-            if (m_weightNoiseSigma > 0) {
+            if (hostNoise) {
                 hipCheck(cn_ctx_join(m_neuralNetwork.context()), m_neuralNetwork.context());   // gradient GEMMs still read the noisy operands
                 for (size_t i = 1; i + 1 < ls.size(); ++i) {
                     layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());

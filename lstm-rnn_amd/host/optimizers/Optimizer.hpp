@@ -22,6 +22,11 @@ public:
 
     // Gaussian weight noise during the backward pass (Optimizer.cu:58-68,82-84; --weight_noise_sigma)
     void setWeightNoise(real_t sigma, unsigned randomSeed) { m_weightNoiseSigma = sigma; m_noiseGen.seed(randomSeed); }
+    // --weight_noise_on_device (include/currennt_hip.h, section Weight noise): the same sigma, generated on the device with this
+    // seed -- the same on every rank, so the replicas perturb the same weights the same way -- and pass = (epoch << 32) | index of
+    // the fraction in the epoch: derived, not stored, so --continue resumes the same noise.  No host copies, no join, and the
+    // update of hybrid online/batch learning stays armed.
+    void setWeightNoiseOnDevice(bool onDevice, uint64_t seed) { m_weightNoiseOnDevice = onDevice; m_weightNoiseSeed = seed; }
     // Dropout (layers with a JSON "dropout"; include/currennt_hip.h, section Dropout): training passes drop with this seed and
     // pass = (epoch << 32) | index of the fraction in the epoch -- derived, not stored, so --continue resumes the same masks;
     // validation and test passes do not drop
@@ -50,7 +55,7 @@ public:
 
 protected:
     virtual void _updateWeights() = 0;
-    // hybrid online/batch learning without weight noise: the update of the coming backward pass may be applied layer by layer
+    // hybrid online/batch learning without weight noise drawn on the host: the update of the coming backward pass may be applied layer by layer
     // behind each layer's gradient (cn_ctx_arm_update); _updateWeights() then only completes it
     virtual void _armUpdate() {}
     real_t _processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates, real_t *classError);   // Optimizer.cu:37-104
@@ -76,6 +81,8 @@ private:
     std::vector<Hip::real_vector> m_bestWeights;
     real_t m_weightNoiseSigma = 0;
     std::mt19937 m_noiseGen;
+    bool m_weightNoiseOnDevice = false;
+    uint64_t m_weightNoiseSeed = 0;
     uint64_t m_dropoutSeed = 0;
 protected:
     static void _exportWeights(json::Value *jsonDoc, const char *arrayName, const std::vector<Hip::real_vector> &weights);   // :106-123

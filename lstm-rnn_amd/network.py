@@ -105,6 +105,13 @@ class Layer:
         B.check(self.net.lib.cn_dbg_dropout_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
         return out.reshape(self.net.T, self.net.PS, self.prev.size)
 
+    def noisy_weights(self):
+        """The weights this layer's last backward pass read, flat reference layout (cn_dbg_noisy_weights): w + noise as the noisy
+        operand copies hold it, the bias entries clean; CN_ERR_STATE when that pass had no weight noise."""
+        out = np.empty(self.weight_count, np.float32)
+        B.check(self.net.lib.cn_dbg_noisy_weights(self.handle, out.ctypes.data_as(C.c_void_p), self.weight_count), self.net.ctx)
+        return out
+
     def weight_updates_tensor(self, torch):
         """The layer's weightUpdates in HBM as a torch tensor aliasing the library's memory (no copy)."""
         if getattr(self, "_wu_tensor", None) is None:
@@ -472,6 +479,12 @@ class NeuralNetwork:
         """cn_ctx_set_dropout_pass: whether the forward passes that follow drop (on the layers with a "dropout" rate), and the
         64-bit (seed, pass) of their masks.  The library keeps no clock: a training loop hands a new pass per fraction."""
         B.check(self.lib.cn_ctx_set_dropout_pass(self.ctx, 1 if enable else 0, int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1)), self.ctx)
+
+    def set_weight_noise(self, sigma, seed=0, pass_=0):
+        """cn_ctx_set_weight_noise: the backward passes that follow read w + N(0, sigma^2) noise generated on the device from the
+        64-bit (seed, pass) (include/currennt_hip.h, section Weight noise); the forward pass and the update keep the clean weights.
+        sigma 0 turns it off.  The library keeps no clock: a training loop hands a new pass per fraction."""
+        B.check(self.lib.cn_ctx_set_weight_noise(self.ctx, float(sigma), int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1)), self.ctx)
 
     def set_grad_clip(self, max_norm):
         """cn_ctx_set_grad_clip: clip every update's gradient to this global L2 norm (include/currennt_hip.h, section Gradient
