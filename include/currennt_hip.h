@@ -501,6 +501,65 @@ int  cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, in
  * that reaches a backward pass allocates the noisy copies.                                                        [async] */
 int  cn_ctx_set_weight_noise(cn_ctx *ctx, float sigma, uint64_t seed, uint64_t pass);
 
+/* ---- Input augmentation (--input_noise_sigma, DataSet.cpp:177-184: drawn there on the loader thread; SpecAugment's frequency and
+ *      time masks, Park et al. 2019: no counterpart in the reference) -------------------------------------------------------------
+ * Gaussian noise on the input patterns and masks over runs of features and of frames, applied on the device where a fraction is
+ * re-laid out: the augmented inputs ARE the input layer's outputs.  cn_layer_read(input, CN_BUF_OUTPUTS) returns them, the first
+ * layer's forward product and input-weight gradient read them, nothing keeps the clean ones.  Targets, classes, pattern types
+ * and the row map are untouched.
+ *
+ * Geometry.  P is the input layer's size, B = context_left + context_right + 1 the frames the caller spliced into one pattern,
+ * P0 = P / B the features of a frame; P % B != 0 makes the load fail with CN_ERR_SHAPE.  For slot s (0 <= s < PS), time t and
+ * column c of the pattern:
+ *      block b = c / P0        feature j = c % P0        source frame ts = clamp(t + b - context_left, 0, len_s - 1)
+ * len_s is the number of frames of slot s whose pattern type is not NONE (a sequence lies in its slot from t = 0 without holes).  A
+ * frame whose pattern type is NONE is copied unchanged, and so is everything in a slot with len_s = 0.  Noise and masks are
+ * functions of the SOURCE element (s, ts, j): every context copy of a frame carries the same noise and the same masks, which is
+ * what adding the noise before splicing gives (DataSet.cpp:177-190).
+ *
+ * The noise.  e = ts*P0 + j,
+ *      (w0,w1,w2,w3) = Philox4x32-10( counter = (e >> 2, s, pass_lo, pass_hi),
+ *                                     key     = (seed_lo, seed_hi XOR 0x696E7074) )
+ * and from there exactly the formulas of section Weight noise with e in the place of k: pair (e & 3) >> 1, u1, t, r,
+ * z = mul_rn(r, (e & 1) ? sinpif(t) : cospif(t)), n = mul_rn(sigma, z), x' = add_rn(x, n): every step a single fp32 operation.
+ * The constant ("inpt") keeps the stream apart from the weight noise and the dropout masks of the same seed.  With
+ * noise_sigma == 0 nothing is added (x' = x, bit for bit).
+ *
+ * The masks.  For each slot with len_s >= 1, mask m draws
+ *      (w0,w1,.,.) = Philox4x32-10( counter = (m, s, pass_lo, pass_hi), key = (seed_lo, seed_hi XOR 0x6D61736B) )       ("mask")
+ * Frequency mask i uses m = i, time mask i uses m = 16 + i: a mask does not depend on how many of the other kind there are.
+ *      frequency mask:  Fc = min(freq_width, P0)                                      w = w0 mod (Fc + 1)
+ *                       f0 = w1 mod (P0 - w + 1)                                      covers features     f0 <= j  < f0 + w
+ *      time mask:       Wc = min(time_width, len_s * time_max_permille / 1000)        w = w0 mod (Wc + 1)       (integer division)
+ *                       t0 = w1 mod (len_s - w + 1)                                   covers source frames t0 <= ts < t0 + w
+ * A covered element becomes exactly +0.0, noise or not: the mean of standardised features.  (The bias of the modulo, at most
+ * 2^-32 * range, is ignored.)
+ *
+ * The result is rounded ONCE to the operand type (CN_PREC_BF16: to nearest even; fp32 otherwise) and is a function of
+ * (settings, s, ts, j, x) alone: not of any padding, the precision mode, the load path or the kernels chosen.  Pad slots and pad
+ * columns stay exactly zero.
+ *
+ * When.  Every cn_fraction_load and cn_fraction_load_resident re-lays the fraction out with the settings in force when it is
+ * called, on every path (resident, staged host upload, the strided copies of option overlap = 0).  cn_fraction_prefetch* records
+ * the settings in force at the prefetch; the load that follows is a hit only if the settings in force at the load equal the
+ * recorded ones member by member -- otherwise the prefetch is discarded like any other miss and the load runs the ordinary way.
+ * What a load leaves behind is therefore always a function of the settings at the load.
+ *
+ * With a == NULL, or noise_sigma == 0 and both counts 0, the library launches exactly what it launches without the call. */
+typedef struct cn_input_augment {
+    float    noise_sigma;                  /* >= 0, finite; 0 = no noise                                   */
+    int      context_left, context_right;  /* how the caller spliced the patterns it loads (>= 0)          */
+    int      freq_masks, freq_width;       /* number of frequency masks (0..8), largest width F (>= 0)     */
+    int      time_masks, time_width;       /* number of time masks (0..8), largest width W (>= 0)          */
+    int      time_max_permille;            /* 0..1000: a time mask is at most len * this / 1000 frames     */
+    uint64_t seed, pass;                   /* the caller's: the library keeps no clock                     */
+} cn_input_augment;
+/* NULL = off, and a fresh context is off.  CN_ERR_BAD_ARG: a negative, NaN or infinite noise_sigma; a negative context, width or
+ * count; a count above 8; time_max_permille outside 0..1000.  (P % B != 0 is found at the load: CN_ERR_SHAPE.)  The first enabling
+ * call allocates the per-slot mask table (a few hundred bytes per slot; a second one with the first prefetch); turning the
+ * augmentation off again leaves them unused until the context is destroyed.                                      [async] */
+int  cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,8 @@ EXPORTS = [
     "cn_ctx_set_grad_clip", "cn_ctx_grad_clip_stats",
     # include/currennt_hip.h, section Weight noise, and its hook in include/currennt_hip_debug.h
     "cn_ctx_set_weight_noise", "cn_dbg_noisy_weights",
+    # include/currennt_hip.h, section Input augmentation
+    "cn_ctx_set_input_augment",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -66,6 +68,13 @@ class Fraction(C.Structure):
                 ("input_pattern_size", C.c_int), ("output_pattern_size", C.c_int),
                 ("pat_types", C.c_void_p), ("inputs", C.c_void_p),
                 ("target_classes", C.c_void_p), ("targets", C.c_void_p)]
+
+
+class InputAugment(C.Structure):
+    """cn_input_augment (include/currennt_hip.h, section Input augmentation)"""
+    _fields_ = [("noise_sigma", C.c_float), ("context_left", C.c_int), ("context_right", C.c_int),
+                ("freq_masks", C.c_int), ("freq_width", C.c_int), ("time_masks", C.c_int), ("time_width", C.c_int),
+                ("time_max_permille", C.c_int), ("seed", C.c_uint64), ("pass_", C.c_uint64)]
 
 
 # include/currennt_hip_debug.h: cn_dbg_tn_item, cn_dbg_fold_item (every pointer a c_void_p: an int would be cut to 32 bits)
@@ -192,6 +201,7 @@ def load_library():
     L.cn_ctx_grad_clip_stats.argtypes = [vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(cf), ci]
     L.cn_ctx_set_weight_noise.argtypes = [vp, cf, C.c_uint64, C.c_uint64]
     L.cn_dbg_noisy_weights.argtypes = [vp, vp, C.c_size_t]
+    L.cn_ctx_set_input_augment.argtypes = [vp, C.POINTER(InputAugment)]
     _LIB = L
     return L
 

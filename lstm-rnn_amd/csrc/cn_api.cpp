@@ -153,7 +153,15 @@ struct cn_ctx {
         bool host = false; cn_fraction f_host{}; int slot = 0;     // cn_fraction_prefetch: f points into staging area `slot`, f_host is what the caller announced
         char *pat = nullptr, *pat_raw = nullptr; int *tcls = nullptr; void *in_op = nullptr; float *targets = nullptr;   // alternates
         bool allocated = false;
+        cn_input_augment aug{};                                  // the augmentation in force at the prefetch (all zero: off)
+        int *aug_tab = nullptr;                                  // its slot table: this re-layout runs on the side stream
     } pf;
+
+    // cn_ctx_set_input_augment (include/currennt_hip.h, section Input augmentation): the settings the loads that follow go by --
+    // all zero when off, so that two settings compare member by member -- and the slot table of the loads on this stream
+    // ([PS][AUG_TAB_STRIDE] ints, allocated by the first enabling call that knows PS)
+    cn_input_augment aug{};
+    int *aug_tab = nullptr;
 
     // data-parallel training: RCCL communicator of this rank, its stream and the newest reduction's event
     ncclComm_t comm = nullptr;
@@ -534,21 +542,63 @@ bool is_class_post(const cn_layer *post)
 struct FractionBuffers { char *pat, *pat_raw; int *tcls; void *in_op; float *targets; };
 // `f` with DEVICE pointers (the caller's resident arrays or a staging area): [T][PS] -> [T][PSp] operands, pattern types with their
 // row map, classes or targets; a binary classification layer's classes become its targets
-void relayout(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b)
+// ... augmented on the way when `aug` is on (section Input augmentation): the slot table `aug_tab` first, on the same stream
+bool aug_enabled(const cn_input_augment &a) { return a.noise_sigma > 0.f || a.freq_masks > 0 || a.time_masks > 0; }
+bool same_augment(const cn_input_augment &a, const cn_input_augment &b)
+{
+    return a.noise_sigma == b.noise_sigma && a.context_left == b.context_left && a.context_right == b.context_right &&
+           a.freq_masks == b.freq_masks && a.freq_width == b.freq_width && a.time_masks == b.time_masks && a.time_width == b.time_width &&
+           a.time_max_permille == b.time_max_permille && a.seed == b.seed && a.pass == b.pass;
+}
+void check_augment_shape(const cn_input_augment &a, const cn_layer *input)
+{
+    if (!aug_enabled(a)) return;
+    const long B = (long)a.context_left + a.context_right + 1;
+    if (input->size % B != 0)
+        throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: input layer size of " + std::to_string(input->size) + " is no multiple of the " +
+                       std::to_string(B) + " frames of the input augmentation's context");
+}
+AugArgs aug_args(const cn_input_augment &a, const cn_layer *input)
+{
+    AugArgs g{};
+    g.P0 = input->size / (a.context_left + a.context_right + 1); g.ctx_left = a.context_left;
+    g.nfreq = a.freq_masks; g.fwidth = a.freq_width; g.ntime = a.time_masks; g.twidth = a.time_width; g.permille = a.time_max_permille;
+    g.k0 = (uint32_t)a.seed; g.k1_noise = (uint32_t)(a.seed >> 32) ^ 0x696E7074u; g.k1_mask = (uint32_t)(a.seed >> 32) ^ 0x6D61736Bu;
+    g.pass_lo = (uint32_t)a.pass; g.pass_hi = (uint32_t)(a.pass >> 32);
+    g.sigma = a.noise_sigma;
+    return g;
+}
+void ensure_aug_table(cn_ctx *c, int *&tab)
+{
+    if (!tab && c->PS > 0) HIP_CHECK(hipMalloc((void **)&tab, (size_t)c->PS * AUG_TAB_STRIDE * sizeof(int)));
+}
+void relayout(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b,
+              const cn_input_augment &aug, int *&aug_tab)
 {
     const bool cls = is_class_post(post);
-    launch_fraction_load(st, c->f32, f.max_seq_length, c->PS, c->PSp, f.pat_types, b.pat,
-                         cls ? f.target_classes : nullptr, b.tcls,
-                         (post && !cls) ? f.targets : nullptr, post ? b.targets : nullptr,
-                         post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN, f.min_seq_length);
+    if (aug_enabled(aug)) {
+        ensure_aug_table(c, aug_tab);
+        const AugArgs g = aug_args(aug, input);
+        launch_augment_table(st, g, f.pat_types, c->PS, f.max_seq_length, c->PS, aug_tab);
+        launch_fraction_load_augment(st, c->f32, g, aug_tab, f.max_seq_length, c->PS, c->PSp, f.pat_types, b.pat,
+                                     cls ? f.target_classes : nullptr, b.tcls,
+                                     (post && !cls) ? f.targets : nullptr, post ? b.targets : nullptr,
+                                     post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN, f.min_seq_length);
+    } else {
+        launch_fraction_load(st, c->f32, f.max_seq_length, c->PS, c->PSp, f.pat_types, b.pat,
+                             cls ? f.target_classes : nullptr, b.tcls,
+                             (post && !cls) ? f.targets : nullptr, post ? b.targets : nullptr,
+                             post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN, f.min_seq_length);
+    }
     if (post && post->kind == CN_LAYER_BINARY_CLASSIFICATION)
         launch_classes_to_targets(st, b.tcls, b.targets, f.max_seq_length * c->PSp);
 }
 // ... out of staging area `slot`: behind its upload (copy stream); the area is free again when the re-layout has read it
-void relayout_staged(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b, int slot)
+void relayout_staged(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b, int slot,
+                     const cn_input_augment &aug, int *&aug_tab)
 {
     HIP_CHECK(hipStreamWaitEvent(st, c->ev_up[slot], 0));
-    relayout(st, c, input, post, f, b);
+    relayout(st, c, input, post, f, b, aug, aug_tab);
     HIP_CHECK(hipEventRecord(c->ev_free[slot], st));
     c->stage_used[slot] = true;
 }
@@ -557,8 +607,8 @@ void launch_prefetch(cn_ctx *c, hipStream_t st)
 {
     cn_ctx::Prefetch &p = c->pf;
     const FractionBuffers alt{p.pat, p.pat_raw, p.tcls, p.in_op, p.targets};
-    if (p.host) relayout_staged(st, c, p.input, p.post, p.f, alt, p.slot);     // (f points into the staging area)
-    else relayout(st, c, p.input, p.post, p.f, alt);
+    if (p.host) relayout_staged(st, c, p.input, p.post, p.f, alt, p.slot, p.aug, p.aug_tab);     // (f points into the staging area)
+    else relayout(st, c, p.input, p.post, p.f, alt, p.aug, p.aug_tab);
     p.launched = true;
 }
 void ensure_fork_events(cn_layer *l)
@@ -1347,7 +1397,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         }
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
-        hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart);
+        hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart); hipFree(ctx->aug_tab); hipFree(ctx->pf.aug_tab);
         hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
@@ -1906,25 +1956,26 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
         flush_loss(ctx);                     // (a deferred loss sum counts the rows of the fraction that is being replaced)
         Timed tm(ctx, KC_OTHER);
         require_targets("cn_fraction_load", post_output, f);
+        check_augment_shape(ctx->aug, input);
         cn_ctx::Prefetch &pf = ctx->pf;
         // a prefetch of the same kind (resident / host buffers) announced exactly this fraction and the side stream has re-laid it
         // out (join_side above ordered this stream behind it): nothing is copied or launched here
         const bool hit = pf.valid && pf.launched && pf.host == !resident && pf.input == input && pf.post == post_output &&
-                         same_fraction(pf.host ? pf.f_host : pf.f, *f);
+                         same_fraction(pf.host ? pf.f_host : pf.f, *f) && same_augment(pf.aug, ctx->aug);
         pf.valid = false;          // a prefetch serves the very next load or nothing
         const FractionBuffers cur{ctx->d_pat, ctx->d_pat_raw, ctx->d_tcls, input->out_op, post_output ? post_output->targets : nullptr};
         if (hit) {
             ++pf.hits;
             swap_in_prefetched(ctx, input, post_output);
         } else if (resident) {      // everything is in HBM already: one kernel re-lays it out
-            relayout(ctx->stream, ctx, input, post_output, *f, cur);
+            relayout(ctx->stream, ctx, input, post_output, *f, cur, ctx->aug, ctx->aug_tab);
         } else if (ctx->overlap) {
             // Host buffers: pack [patTypes | classes or targets | inputs] into pinned memory, ONE contiguous upload
             // on the copy stream (it runs while the previous fraction still computes: the staging areas alternate),
             // then the same re-layout kernel as the resident path.  (Strided 2-D copies from pageable memory cost
             // one transfer per time step: 3.5 ms per fraction of 2.3 MB, twice the whole training step.)
             const Staged sg = stage_upload(ctx, input, post_output, f);
-            relayout_staged(ctx->stream, ctx, input, post_output, sg.f, cur, sg.slot);
+            relayout_staged(ctx->stream, ctx, input, post_output, sg.f, cur, sg.slot, ctx->aug, ctx->aug_tab);
         } else {
             // CN_NO_OVERLAP: strided copies [T][PS] -> [T][PSp]: pad slots keep their permanent NONE / -1 / 0 contents
             const size_t PS = ctx->PS, PSp = ctx->PSp;
@@ -1942,7 +1993,15 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
                 const size_t trow = (size_t)post_output->size * sizeof(float);
                 HIP_CHECK(hipMemcpy2DAsync(post_output->targets, PSp * trow, f->targets, PS * trow, PS * trow, T, kind, ctx->stream));
             }
-            launch_pad_convert(ctx->stream, ctx->f32, input->stage_in, N, input->size, input->out_op, input->Lp);
+            if (aug_enabled(ctx->aug)) {       // the same arithmetic at the pad_convert stage, from the pattern types just copied
+                ensure_aug_table(ctx, ctx->aug_tab);
+                const AugArgs g = aug_args(ctx->aug, input);
+                launch_augment_table(ctx->stream, g, ctx->d_pat, (int)PSp, T, (int)PS, ctx->aug_tab);
+                launch_pad_convert_augment(ctx->stream, ctx->f32, g, ctx->aug_tab, input->stage_in, ctx->d_pat, T, (int)PS, (int)PSp,
+                                           input->size, input->out_op, input->Lp);
+            } else {
+                launch_pad_convert(ctx->stream, ctx->f32, input->stage_in, N, input->size, input->out_op, input->Lp);
+            }
             HIP_CHECK(hipStreamSynchronize(ctx->stream));     // the caller may reuse its host buffers on return
         }
         set_current(ctx, f);
@@ -1990,7 +2049,10 @@ static int fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output
             pf.allocated = true;
         }
         if (post_output && post_output->targets && !pf.targets) pf.targets = (float *)dalloc(post_output, input->maxN() * post_output->size * sizeof(float));
+        check_augment_shape(ctx->aug, input);
         pf.f = *f; pf.input = input; pf.post = post_output; pf.launched = false; pf.host = host;
+        pf.aug = ctx->aug;                  // the load that follows is a hit only under these settings
+        if (aug_enabled(pf.aug)) ensure_aug_table(ctx, pf.aug_tab);
         if (host) {
             // pack and upload NOW (copy stream, beside whatever the device is doing); the re-layout follows on the side stream of the
             // next gradient work, reading the staging area
@@ -2677,6 +2739,26 @@ int cn_ctx_set_weight_noise(cn_ctx *ctx, float sigma, uint64_t seed, uint64_t pa
         if (sigma != ctx->noise_sigma || seed != ctx->noise_seed || pass != ctx->noise_pass)
             for (cn_layer *l : ctx->layers) l->noisy_ready = false;      // (sets generated ahead belong to the old triple)
         ctx->noise_sigma = sigma; ctx->noise_seed = seed; ctx->noise_pass = pass;
+    });
+}
+
+// ---- input augmentation (include/currennt_hip.h, section Input augmentation) ----
+int cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_input_augment: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!a) { ctx->aug = cn_input_augment{}; return; }
+        const char *w = "cn_ctx_set_input_augment: ";
+        if (!(a->noise_sigma >= 0.f) || std::isinf(a->noise_sigma)) throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "noise_sigma must be finite and >= 0 (0 = no noise)");
+        if (a->context_left < 0 || a->context_right < 0) throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "context_left / context_right must be >= 0");
+        if (a->freq_masks < 0 || a->freq_masks > AUG_MAX_MASKS || a->time_masks < 0 || a->time_masks > AUG_MAX_MASKS)
+            throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "freq_masks / time_masks must be in 0.." + std::to_string(AUG_MAX_MASKS));
+        if (a->freq_width < 0 || a->time_width < 0) throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "freq_width / time_width must be >= 0");
+        if (a->time_max_permille < 0 || a->time_max_permille > 1000) throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "time_max_permille must be in 0..1000");
+        if (!aug_enabled(*a)) { ctx->aug = cn_input_augment{}; return; }      // no noise, no masks: off, whatever the other members say
+        enter(ctx);
+        ctx->aug = *a;
+        ensure_aug_table(ctx, ctx->aug_tab);
     });
 }
 

@@ -13,6 +13,7 @@
 //   (no counterpart in the reference) dropout on a layer's input, include/currennt_hip.h -> dropout_fwd_kernel, dropout_bwd_kernel
 //   optimizers/Optimizer.cu:58-84 weight noise, drawn on the device (include/currennt_hip.h, section Weight noise) -> pack_group_noise_kernel
 #include "cn_internal.h"
+#include "cn_philox_device.h"
 
 #include <float.h>
 
@@ -102,18 +103,12 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
 template <class B> struct PackClip : B { float scale; int state; };
 // Weight noise (UPD = 5, include/currennt_hip.h, section Weight noise): the fetch returns w + n(fi), and the bodies write the
 // copies a backward pass reads only.  A type and an UPD of their own again.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1);
+// (philox4x32_10 and the Box-Muller step gauss_noise: cn_philox_device.h)
 struct PackNoiseKey { uint32_t k0, k1, pass_lo, pass_hi; float sigma; };
 __device__ __forceinline__ float weight_noise(const PackNoiseKey &u, long k)
 {
     const uint4 w = philox4x32_10(make_uint4((uint32_t)(k >> 2), 0u, u.pass_lo, u.pass_hi), u.k0, u.k1);
-    const bool second = (k & 2) != 0;                                          // the pair of this index: words (0, 1) or (2, 3)
-    const uint32_t a = second ? w.z : w.x, b = second ? w.w : w.y;
-    const float u1 = (float)(2u * (a >> 9) + 1u) * 0x1p-24f;                   // odd multiples of 2^-24 / 2^-23 below 2^24: exact
-    const float t = (float)(2u * (b >> 9) + 1u) * 0x1p-23f;
-    const float r = sqrtf(__fmul_rn(-2.0f, logf(u1)));                         // (sqrtf: the correctly rounded one, see adam_step)
-    const float z = __fmul_rn(r, (k & 1) ? sinpif(t) : cospif(t));
-    return __fmul_rn(u.sigma, z);
+    return gauss_noise(w, k, u.sigma);
 }
 template <int UPD, class U>
 __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
@@ -587,17 +582,6 @@ void launch_pad_f32(hipStream_t s, const float *src, int N, int L, float *dst, l
 // neighbouring padded columns of one row (Pp and every direction's pitch are multiples of 4, so the four lie in one direction)
 // and moves them with one 8-byte (bf16) or 16-byte (fp32) load and store.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 // Bit k of the result: padded element (row, pc + k) is a kept unit of a real slot.  Four reference units share one Philox call
 // (counter word 0 = unit >> 2).  The four columns are the units base .. base + 3 of the reference layout; they straddle two
 // calls only where a backward direction starts at a unit that is no multiple of 4 (H % 4 != 0).

@@ -276,6 +276,25 @@ void launch_rowmap(hipStream_t s, const char *dpat, int N, int *rm, int maxN, in
 void launch_fraction_load(hipStream_t s, bool f32, int T, int PS, int PSp, const char *pat, char *dpat, const int *tcls, int *dtcls,
                           const float *tgt, float *dtgt, int W, const float *in, int P, void *dst, int Pp, int *rm = nullptr, int maxN = 0, int Tmin = 0);
 void launch_pad_convert(hipStream_t s, bool f32, const float *src, int N, int P, void *dst, int Pp);
+// ---- input augmentation (include/currennt_hip.h, section Input augmentation; cn_augment.hip) ----
+// The settings of one re-layout as the kernels take them: P0 = P / (ctx_left + ctx_right + 1) features per frame, the two Philox
+// keys ((seed_lo, seed_hi ^ "inpt") for the noise, (seed_lo, seed_hi ^ "mask") for the masks) and counter words 2 and 3.
+struct AugArgs {
+    int P0, ctx_left, nfreq, fwidth, ntime, twidth, permille;
+    uint32_t k0, k1_noise, k1_mask, pass_lo, pass_hi;
+    float sigma;
+};
+#define AUG_MAX_MASKS 8                          // per kind
+#define AUG_TAB_STRIDE (1 + 4 * AUG_MAX_MASKS)   // ints per slot: len, (start, width) of the frequency masks, then of the time masks
+// tab[PS][AUG_TAB_STRIDE] from the pattern types pat[t * pstride + s] (0 <= t < T, 0 <= s < PS): one small workgroup
+void launch_augment_table(hipStream_t s, const AugArgs &a, const char *pat, int pstride, int T, int PS, int *tab);
+// launch_fraction_load with the augmentation of `a` / `tab` applied to the inputs on the way
+void launch_fraction_load_augment(hipStream_t s, bool f32, const AugArgs &a, const int *tab, int T, int PS, int PSp, const char *pat, char *dpat,
+                                  const int *tcls, int *dtcls, const float *tgt, float *dtgt, int W, const float *in, int P, void *dst, int Pp,
+                                  int *rm = nullptr, int maxN = 0, int Tmin = 0);
+// launch_pad_convert of inputs already in the device's row layout (src[T * PSp][P], dpat[T * PSp]), with the same augmentation
+void launch_pad_convert_augment(hipStream_t s, bool f32, const AugArgs &a, const int *tab, const float *src, const char *dpat, int T, int PS, int PSp,
+                                int P, void *dst, int Pp);
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
 // The key of one forward pass of one layer, and the geometry that maps a padded element to the reference (frame, unit) the mask
 // is stated in: row r = t * PSp + ps <-> frame n = t * PS + ps (pad slots ps >= PS: zeros); column -> unit as unpad_col does

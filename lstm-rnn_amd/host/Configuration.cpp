@@ -52,6 +52,12 @@ const char *Configuration::usage()
            "            --weight_noise_sigma X (Gaussian noise on the weights the backward pass reads; default 0 = off)\n"
            "            --weight_noise_on_device B (generate that noise on the device from --random_seed, the epoch and the fraction\n"
            "                      index: no host copies, the update stays overlapped, --continue resumes the same noise; default false)\n"
+           "            --input_noise_sigma X (Gaussian noise on the input patterns of the training set and of --ff_input_file; default 0)\n"
+           "            --input_noise_on_device B (generate that noise on the device from --random_seed, the epoch and the fraction\n"
+           "                      index instead of on the loader thread; --continue resumes the same noise; default false)\n"
+           "            --spec_augment_freq_masks N --spec_augment_freq_width F --spec_augment_time_masks N --spec_augment_time_width W\n"
+           "            --spec_augment_time_ratio X (SpecAugment on the training fractions, on the device: N masks (0..8) of up to F\n"
+           "                      features / W frames each set to 0; a time mask is at most X (0..1, default 1) of its sequence)\n"
            "            --momentum X --save_network F --train_file F[,F] --val_file F --test_file F --truncate_seq N\n"
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
@@ -130,6 +136,22 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "input_noise_sigma") m_inputNoiseSigma = (real_t)atof(v.c_str());
     else if (key == "weight_noise_sigma") m_weightNoiseSigma = (real_t)atof(v.c_str());
     else if (key == "weight_noise_on_device") m_weightNoiseOnDevice = toBool(key, v);
+    else if (key == "input_noise_on_device") m_inputNoiseOnDevice = toBool(key, v);
+    else if (key == "spec_augment_freq_masks" || key == "spec_augment_time_masks") {
+        const int n = atoi(v.c_str());
+        if (n < 0 || n > 8) throw std::runtime_error("Error while parsing the command line and/or options file: --" + key + " must be in 0..8");
+        (key == "spec_augment_freq_masks" ? m_specFreqMasks : m_specTimeMasks) = n;
+    }
+    else if (key == "spec_augment_freq_width" || key == "spec_augment_time_width") {
+        const int w = atoi(v.c_str());
+        if (w < 0) throw std::runtime_error("Error while parsing the command line and/or options file: --" + key + " must be >= 0");
+        (key == "spec_augment_freq_width" ? m_specFreqWidth : m_specTimeWidth) = w;
+    }
+    else if (key == "spec_augment_time_ratio") {
+        m_specTimeRatio = (real_t)atof(v.c_str());
+        if (!(m_specTimeRatio >= 0 && m_specTimeRatio <= 1))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --spec_augment_time_ratio must be in 0..1");
+    }
     else if (key == "input_left_context") m_inputLeftContext = atoi(v.c_str());
     else if (key == "input_right_context") m_inputRightContext = atoi(v.c_str());
     else if (key == "output_time_lag") m_outputTimeLag = atoi(v.c_str());

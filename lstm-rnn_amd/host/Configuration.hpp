@@ -78,6 +78,16 @@ public:
     // --weight_noise_on_device: the noise of --weight_noise_sigma is generated on the device (include/currennt_hip.h, section
     // Weight noise) instead of drawn on the host and uploaded; default false
     bool weightNoiseOnDevice() const { return m_weightNoiseOnDevice; }
+    // --input_noise_on_device: the noise of --input_noise_sigma is generated on the device where a fraction is re-laid out
+    // (include/currennt_hip.h, section Input augmentation) instead of drawn by the data set's loader thread; default false
+    bool inputNoiseOnDevice() const { return m_inputNoiseOnDevice; }
+    // --spec_augment_*: SpecAugment's masks on the training fractions (same section); the ratio is handed over in permille
+    int specAugmentFreqMasks() const { return m_specFreqMasks; }
+    int specAugmentFreqWidth() const { return m_specFreqWidth; }
+    int specAugmentTimeMasks() const { return m_specTimeMasks; }
+    int specAugmentTimeWidth() const { return m_specTimeWidth; }
+    real_t specAugmentTimeRatio() const { return m_specTimeRatio; }
+    bool specAugment() const { return m_specFreqMasks > 0 || m_specTimeMasks > 0; }
     int inputLeftContext() const { return m_inputLeftContext; }
     int inputRightContext() const { return m_inputRightContext; }
     int outputTimeLag() const { return m_outputTimeLag; }
@@ -94,7 +104,9 @@ private:
     int m_dumpEpochs = 1;
     bool m_dumpFractions = false, m_dumpLabels = false, m_autosave = false, m_autosaveBest = false;
     real_t m_inputNoiseSigma = 0, m_weightNoiseSigma = 0;
-    bool m_weightNoiseOnDevice = false;
+    bool m_weightNoiseOnDevice = false, m_inputNoiseOnDevice = false;
+    int m_specFreqMasks = 0, m_specFreqWidth = 0, m_specTimeMasks = 0, m_specTimeWidth = 0;
+    real_t m_specTimeRatio = 1;
     int m_inputLeftContext = 0, m_inputRightContext = 0, m_outputTimeLag = 0;
     std::string m_autosavePrefix, m_continueFile, m_serializedOptions;
     bool m_help = false, m_trainingMode = false, m_hybridOnlineBatch = false, m_shuffleFractions = false,

@@ -1,6 +1,7 @@
 #include "DataSet.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <limits>
 #include <stdexcept>
 
@@ -208,7 +209,10 @@ bool DataSet::produceNext(DataSetFraction *frac)
         if (m_fractionShuffling) shuffleFractions();
     }
     if (m_curFirstSeqIdx < (int)m_sequences.size()) {
+        const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         makeFraction(m_curFirstSeqIdx, frac);
+        m_loaderSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        ++m_loaderFractions;
         m_curFirstSeqIdx += m_parallelSequences * m_world;
         return true;
     }

@@ -81,8 +81,14 @@ public:
     int numLabels() const { return m_numLabels; }                                     // classification data: the numLabels dimension
     const Hip::real_vector &outputMeans() const { return m_outputMeans; }
     const Hip::real_vector &outputStdevs() const { return m_outputStdevs; }
+    // what the loader thread has spent packing fractions so far (noise and splicing included) and how many it packed: read
+    // between epochs by the driver's CN_LOADER_TIME hook (tools/augment_cost.py)
+    double loaderSeconds() const { return m_loaderSeconds; }
+    long loaderFractions() const { return m_loaderFractions; }
 
 private:
+    double m_loaderSeconds = 0;
+    long m_loaderFractions = 0;
     bool m_fractionShuffling = false, m_sequenceShuffling = false, m_isClassificationData = false;
     int m_parallelSequences = 0, m_totalSequences = 0, m_totalTimesteps = 0, m_minSeqLength = 0, m_maxSeqLength = 0,
         m_inputPatternSize = 0, m_outputPatternSize = 0, m_numLabels = 0, m_curFirstSeqIdx = -1, m_rank = 0, m_world = 1;

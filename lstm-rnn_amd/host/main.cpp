@@ -55,6 +55,10 @@ std::shared_ptr<data_sets::DataSet> loadDataSet(const Configuration &config, dat
     case DATA_SET_TEST: type = "test set"; filenames = config.testFiles(); fraction = config.testFraction(); break;
     default: type = "feed forward input set"; filenames = config.feedForwardInputFiles(); augment.noiseDeviation = config.inputNoiseSigma(); break;
     }
+    // --input_noise_on_device: the data set draws none; the fractions of the same two sets get it where they are re-laid out
+    const bool deviceNoise = config.inputNoiseOnDevice() && augment.noiseDeviation > 0;
+    const real_t deviceSigma = deviceNoise ? augment.noiseDeviation : 0;
+    if (deviceNoise) augment.noiseDeviation = 0;
     printf("Loading %s ", type.c_str());
     for (size_t i = 0; i < filenames.size(); ++i) printf("'%s' ", filenames[i].c_str());
     printf("...");
@@ -68,7 +72,13 @@ std::shared_ptr<data_sets::DataSet> loadDataSet(const Configuration &config, dat
     printf("Loaded fraction:  %d%%\n", (int)(fraction * 100));
     printf("Sequences:        %d\n", ds->totalSequences());
     printf("Sequence lengths: %d..%d\n", ds->minSeqLength(), ds->maxSeqLength());
-    printf("Total timesteps:  %d\n\n", ds->totalTimesteps());
+    printf("Total timesteps:  %d\n", ds->totalTimesteps());
+    if (deviceNoise) printf("Input noise:      sigma %g, generated on the device\n", (double)deviceSigma);
+    if (dsType == DATA_SET_TRAINING && config.specAugment())
+        printf("SpecAugment:      %d frequency masks of up to %d features, %d time masks of up to %d frames (at most %g of a sequence), on the device\n",
+               config.specAugmentFreqMasks(), config.specAugmentFreqWidth(), config.specAugmentTimeMasks(), config.specAugmentTimeWidth(),
+               (double)config.specAugmentTimeRatio());
+    printf("\n");
     return ds;
 }
 
@@ -136,6 +146,22 @@ void makeDirs(const std::string &path)
 void swap32(void *p) { unsigned char *b = (unsigned char *)p; std::swap(b[0], b[3]); std::swap(b[1], b[2]); }
 void swap16(void *p) { unsigned char *b = (unsigned char *)p; std::swap(b[0], b[1]); }
 
+// The device's input augmentation as the options state it (include/currennt_hip.h, section Input augmentation): the noise of
+// --input_noise_sigma with --input_noise_on_device, the masks of --spec_augment_* where `masks` (training fractions only)
+cn_input_augment inputAugment(const Configuration &config, uint64_t seed, bool masks, uint64_t pass)
+{
+    cn_input_augment a{};
+    a.noise_sigma = config.inputNoiseOnDevice() ? (float)config.inputNoiseSigma() : 0.f;
+    a.context_left = config.inputLeftContext(); a.context_right = config.inputRightContext();
+    if (masks) {
+        a.freq_masks = config.specAugmentFreqMasks(); a.freq_width = config.specAugmentFreqWidth();
+        a.time_masks = config.specAugmentTimeMasks(); a.time_width = config.specAugmentTimeWidth();
+    }
+    a.time_max_permille = (int)lround(1000.0 * (double)config.specAugmentTimeRatio());
+    a.seed = seed; a.pass = pass;
+    return a;
+}
+
 void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::DataSet &set)      // main.cpp:307-490
 {
     const Hip::real_vector means = set.outputMeans(), stdevs = set.outputStdevs();
@@ -148,6 +174,10 @@ void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::Data
     while (set.getNextFraction(&frac)) {
         printf("Computing outputs for data fraction %d...", ++fracIdx);
         fflush(stdout);
+        if (config.inputNoiseOnDevice() && config.inputNoiseSigma() > 0) {       // pass = the fraction's index: one pass over the set
+            const cn_input_augment a = inputAugment(config, (uint64_t)config.randomSeed(), false, (uint64_t)(fracIdx - 1));
+            hipCheck(cn_ctx_set_input_augment(nn.context(), &a), nn.context());
+        }
         nn.loadSequences(frac);
         nn.computeForwardPass();
         std::vector<std::vector<std::vector<real_t> > > outputs = nn.getOutputs();
@@ -358,6 +388,9 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             optimizer.setWeightNoiseOnDevice(config.weightNoiseOnDevice(), (uint64_t)config.randomSeed());
             // every rank its own masks: seed = --random_seed + rank * 0x9E3779B97F4A7C15 (mod 2^64)
             optimizer.setDropoutSeed((uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull);
+            // --input_noise_on_device, --spec_augment_*: every rank its own stream, like the dropout masks (a rank holds other sequences)
+            if ((config.inputNoiseOnDevice() && config.inputNoiseSigma() > 0) || config.specAugment())
+                optimizer.setInputAugment(inputAugment(config, (uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull, true, 0));
 
             std::string infoRows;
             if (!config.continueFile().empty()) {                                               // main.cpp:198-204
@@ -420,6 +453,9 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             else printf("Maximum number of training epochs reached. Training stopped.\n");
             if (!validationSet->empty()) printf("Lowest validation error: %lf\n", optimizer.lowestValidationError());
             else printf("Final training set error: %lf\n", optimizer.curTrainingError());
+            // measurement hook (tools/augment_cost.py): what the training set's loader thread spent per fraction it packed
+            if (testHook("CN_LOADER_TIME") && trainingSet->loaderFractions() > 0)
+                printf("Loader: %.3f ms per fraction (%ld fractions)\n", trainingSet->loaderSeconds() * 1e3 / trainingSet->loaderFractions(), trainingSet->loaderFractions());
             printf("\n");
             printf("Storing the trained network in '%s'... ", config.trainedNetworkFile().c_str());
             if (root) saveNetwork(neuralNetwork, config.trainedNetworkFile());

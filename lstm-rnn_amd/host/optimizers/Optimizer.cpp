@@ -92,6 +92,13 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         anyDropout = anyDropout || (layer && layer->dropout() > 0);
     }
     if (anyDropout && !calcWeightUpdates) hipCheck(cn_ctx_set_dropout_pass(m_neuralNetwork.context(), 0, 0, 0), m_neuralNetwork.context());
+    // input augmentation on the device: only training fractions; `index` is the fraction's index in the epoch
+    auto setInputAugment = [&](uint64_t index) {
+        cn_input_augment a = m_inputAugment;
+        a.pass = ((uint64_t)m_curEpoch << 32) | (index & 0xFFFFFFFFull);
+        hipCheck(cn_ctx_set_input_augment(m_neuralNetwork.context(), &a), m_neuralNetwork.context());
+    };
+    if (m_inputAugmentOn && !calcWeightUpdates) hipCheck(cn_ctx_set_input_augment(m_neuralNetwork.context(), nullptr), m_neuralNetwork.context());
     uint64_t fractionIndex = 0;
     data_sets::DataSetFraction frac, next;
     bool firstFraction = true;
@@ -106,6 +113,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
             hipCheck(cn_ctx_set_weight_noise(m_neuralNetwork.context(), m_weightNoiseSigma, m_weightNoiseSeed,
                                              ((uint64_t)m_curEpoch << 32) | (fractionIndex & 0xFFFFFFFFull)), m_neuralNetwork.context());
         const bool hostNoise = m_weightNoiseSigma > 0 && !m_weightNoiseOnDevice;
+        if (m_inputAugmentOn && calcWeightUpdates) setInputAugment(fractionIndex);      // (what its prefetch was announced under)
         ++fractionIndex;
         m_neuralNetwork.loadSequences(frac);
         m_neuralNetwork.computeForwardPass();
@@ -123,7 +131,10 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         // the top of the next iteration only exchanges buffers.  (`next` keeps its vectors' storage when it becomes `frac`:
         // the hint is matched by address.)
         const bool haveNext = ds.getNextFraction(&next);
-        if (haveNext && calcWeightUpdates) m_neuralNetwork.prefetchSequences(next);
+        if (haveNext && calcWeightUpdates) {
+            if (m_inputAugmentOn) setInputAugment(fractionIndex);      // the next fraction's settings, in front of its announcement
+            m_neuralNetwork.prefetchSequences(next);
+        }
 
         if (calcWeightUpdates) {
             // weight noise: the forward pass above used the clean weights, the backward pass runs on noisy ones

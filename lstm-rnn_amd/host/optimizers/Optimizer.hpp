@@ -27,6 +27,11 @@ public:
     // the fraction in the epoch: derived, not stored, so --continue resumes the same noise.  No host copies, no join, and the
     // update of hybrid online/batch learning stays armed.
     void setWeightNoiseOnDevice(bool onDevice, uint64_t seed) { m_weightNoiseOnDevice = onDevice; m_weightNoiseSeed = seed; }
+    // --input_noise_on_device / --spec_augment_* (include/currennt_hip.h, section Input augmentation): the training fractions are
+    // re-laid out with these settings -- seed as for dropout (each rank holds other sequences), pass = (epoch << 32) | index of the
+    // fraction in the epoch, derived like dropout's -- set in front of each fraction's prefetch announcement and again in front
+    // of its load, so the load stays a hit; validation and test passes load without augmentation
+    void setInputAugment(const cn_input_augment &settings) { m_inputAugment = settings; m_inputAugmentOn = true; }
     // Dropout (layers with a JSON "dropout"; include/currennt_hip.h, section Dropout): training passes drop with this seed and
     // pass = (epoch << 32) | index of the fraction in the epoch -- derived, not stored, so --continue resumes the same masks;
     // validation and test passes do not drop
@@ -84,6 +89,8 @@ private:
     bool m_weightNoiseOnDevice = false;
     uint64_t m_weightNoiseSeed = 0;
     uint64_t m_dropoutSeed = 0;
+    cn_input_augment m_inputAugment{};
+    bool m_inputAugmentOn = false;
 protected:
     static void _exportWeights(json::Value *jsonDoc, const char *arrayName, const std::vector<Hip::real_vector> &weights);   // :106-123
     static void _importWeights(const json::Value &jsonDoc, const char *arrayName, std::vector<Hip::real_vector> *weights);   // :125-149

@@ -486,6 +486,19 @@ class NeuralNetwork:
         sigma 0 turns it off.  The library keeps no clock: a training loop hands a new pass per fraction."""
         B.check(self.lib.cn_ctx_set_weight_noise(self.ctx, float(sigma), int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1)), self.ctx)
 
+    def set_input_augment(self, noise_sigma=0.0, context=(0, 0), freq_masks=0, freq_width=0, time_masks=0, time_width=0,
+                          time_max_permille=1000, seed=0, pass_=0):
+        """cn_ctx_set_input_augment: the loads (and prefetches) that follow re-lay their fraction out with Gaussian input noise and
+        SpecAugment masks generated on the device from the 64-bit (seed, pass) (include/currennt_hip.h, section Input
+        augmentation); `context` = (left, right) is how the caller spliced the patterns.  set_input_augment(None), or no noise and
+        no masks, turns it off.  The library keeps no clock: a training loop hands a new pass per fraction."""
+        if noise_sigma is None:
+            B.check(self.lib.cn_ctx_set_input_augment(self.ctx, None), self.ctx)
+            return
+        a = B.InputAugment(float(noise_sigma), int(context[0]), int(context[1]), int(freq_masks), int(freq_width), int(time_masks),
+                           int(time_width), int(time_max_permille), int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1))
+        B.check(self.lib.cn_ctx_set_input_augment(self.ctx, C.byref(a)), self.ctx)
+
     def set_grad_clip(self, max_norm):
         """cn_ctx_set_grad_clip: clip every update's gradient to this global L2 norm (include/currennt_hip.h, section Gradient
         clipping); 0 turns it off, a bound nothing reaches (FLT_MAX) only monitors the norm."""
