@@ -560,6 +560,32 @@ typedef struct cn_input_augment {
  * augmentation off again leaves them unused until the context is destroyed.                                      [async] */
 int  cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a);
 
+/* ---- Residual connections (no counterpart in the reference; He et al. 2016, and Kim et al. 2017 for stacked LSTMs) ----------------
+ * A hidden layer l of kind lstm, blstm or feedforward_{tanh,logistic,identity} whose preceding layer has the same `size` may be
+ * marked residual; the preceding layer may be of any kind, the input layer included.  Write b for what l computes without the
+ * mark, its "branch": l's operand copy, which its own recurrence and its recurrent-weight gradient keep reading.  What l's
+ * followers and cn_layer_read(.., CN_BUF_OUTPUTS, ..) see for a real frame n and unit u is
+ *      out[n][u] = round_op( float(b_op[n][u]) + float(x_op[n][u]) )
+ * b_op: l's operand copy; x_op: what the preceding layer's followers read -- its own sum if it is residual too, never a dropped
+ * copy; round_op: ONE rounding to the operand type (CN_PREC_F32 / CN_PREC_BF16X3: none, the fp32 sum; CN_PREC_BF16: to nearest
+ * even).  Units are matched in the reference layout, unit u of both layers (blstm: the forward units, then the backward ones),
+ * whatever padding either layer's rows have.  On rows that are not real frames (dummy frames, pad slots) out is the branch: 0
+ * for an LSTM layer.  Pad columns of out are zeros.
+ *
+ * Backward.  l's outputErrors e, as its follower wrote them, are dL/d out.  The branch's backward pass uses e as it does without
+ * the mark (a feed-forward layer's act' is taken at the branch output).  When the preceding layer is trainable its outputErrors
+ * become (what l's backward pass hands back today, after the dropout mask if l drops) + e on real frames, unit by unit, one fp32
+ * addition; dummy rows get nothing added.  Dropout on l's input acts on the weighted path only: the skip path is never dropped and
+ * never rescaled.  Weight noise does not touch it.  This is part of the model, not a regulariser: every forward pass sums.
+ *
+ * With no layer marked the library launches exactly what it launches without this call and allocates nothing for it. */
+/* The JSON "residual" of a layer.  CN_ERR_BAD_ARG: a layer of another kind; a size that differs from the preceding layer's; a
+ * post output layer directly behind the layer (cn_layer_create of a post output layer behind a residual layer is refused as
+ * well: the post output kernels read the fp32 outputs, and that case is left out).  May be called between fractions; takes effect
+ * with the layer's next forward pass, and each layer's backward pass goes by what its forward pass did.  The first enabling call
+ * allocates the layer's sum buffer (the size of its operand copy; a feed-forward layer: also an fp32 copy of its outputErrors). */
+int  cn_layer_set_residual(cn_layer *layer, int enable);
+
 #ifdef __cplusplus
 }
 #endif

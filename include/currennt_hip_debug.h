@@ -84,6 +84,11 @@ int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count);
  * not exactly 0.  [sync] */
 int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count);
 
+/* The branch output of a residual layer (include/currennt_hip.h, section Residual connections), as its last forward pass left it:
+ * the layer's own operand copy in the reference layout [T * PS][size], widened to float; count = T * PS * size.  CN_ERR_STATE when
+ * that pass did not sum.  [sync] */
+int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -259,6 +259,13 @@ struct cn_layer {
     bool dropped = false;                 // the last forward pass dropped ...
     DropArgs drop{};                      // ... with this key: what its backward pass masks the handed-back error with
 
+    // residual connection around this layer (include/currennt_hip.h, section Residual connections)
+    bool residual = false;                // cn_layer_set_residual
+    void *res_sum = nullptr;              // [maxN][Lp] (op) out_op + what the preceding layer's followers read; allocated when first enabled
+    float *res_e = nullptr;               // dense layers: [maxN][Lp] the outputErrors as handed in (launch_ff_delta overwrites err in place)
+    bool summed = false;                  // the last forward pass summed ...
+    ResArgs res{};                        // ... with this geometry: what its followers read and what its backward pass adds go by the record
+
     // lstm internals
     float *acts = nullptr, *cell = nullptr, *th = nullptr;
     void *pre16 = nullptr;                // bf16 mode: the input projection's pre-activations as bf16 (LstmRec::pre16), where the forward kernel takes them
@@ -947,6 +954,37 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule
 // armed update without a communicator: unpack + update + operand copies ride on ONE launch behind the gradient GEMMs
 bool armed_fused(const cn_layer *l) { return l->ctx->armed && !l->ctx->has_comm(); }
 
+// ---- residual connections (include/currennt_hip.h, section Residual connections) ----
+// The operand a follower of `p` reads: p's operand copy, or -- when p's last forward pass summed -- its sum buffer.  (Looked up at
+// every use: a prefetch swaps the input layer's out_op.)
+const void *follower_operand(const cn_layer *p) { return p->summed ? p->res_sum : p->out_op; }
+// behind a marked layer's own forward kernels: the sum its followers read.  The layer records that it summed and with which
+// geometry; its backward pass goes by the record.
+void residual_sum(cn_layer *l)
+{
+    cn_ctx *c = l->ctx;
+    l->summed = false;                    // (follower_operand(l->prev) below is about the PRECEDING layer; this layer's record is set last)
+    if (!l->residual) return;
+    const cn_layer *p = l->prev;
+    ResArgs &a = l->res;
+    a.N = c->N; a.L = l->size; a.Lp = l->Lp;
+    a.H = l->lstm ? l->H : 0; a.Hp = l->lstm ? l->Hp : 0; a.dirs = l->lstm ? l->dirs : 0;
+    a.xLp = p->Lp; a.xH = p->lstm ? p->H : 0; a.xHp = p->lstm ? p->Hp : 0; a.xdirs = p->lstm ? p->dirs : 0;
+    const bool two = l->lstm && l->dirs == 2, xtwo = p->lstm && p->dirs == 2;     // (one direction: unit u at column u, like a dense layer)
+    a.same_map = two == xtwo && (!two || l->Hp == p->Hp);
+    Timed tm(c, KC_OTHER);
+    launch_residual_fwd(c->stream, c->f32, a, c->d_pat, l->out_op, follower_operand(p), l->res_sum);
+    l->summed = true;
+}
+// behind K8 and mask_handed_back_error on the main stream: the skip path's term of the preceding layer's outputErrors.  `e`: this
+// layer's outputErrors as its follower handed them in.
+void residual_add_error(cn_layer *l, const float *e)
+{
+    if (!l->summed || !l->prev->trainable) return;
+    Timed tm(l->ctx, KC_OTHER);
+    launch_residual_bwd(l->ctx->stream, l->res, l->ctx->d_pat, e, l->prev->err);
+}
+
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
 // The operand a layer's input products read in this forward pass: the preceding layer's operand copy, or -- when the pass drops --
 // the masked copy, written here in front of K1.  The layer records whether it dropped and with which key: its backward pass
@@ -955,7 +993,7 @@ const void *forward_input(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     l->dropped = c->drop_enable && l->drop_rate > 0.f;
-    if (!l->dropped) return l->prev->out_op;
+    if (!l->dropped) return follower_operand(l->prev);
     DropArgs &a = l->drop;
     a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.P = l->P; a.Pp = l->Pp;
     a.prevH = l->prev->lstm ? l->prev->H : 0; a.prevHp = l->prev->lstm ? l->prev->Hp : 0; a.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
@@ -964,11 +1002,11 @@ const void *forward_input(cn_layer *l)
     a.thr = (uint32_t)std::floor((double)l->drop_rate * 4294967296.0);
     a.scale = (float)(1.0 / (1.0 - (double)l->drop_rate));
     Timed tm(c, KC_OTHER);
-    launch_dropout_fwd(c->stream, c->f32, a, l->prev->out_op, l->in_drop);
+    launch_dropout_fwd(c->stream, c->f32, a, follower_operand(l->prev), l->in_drop);
     return l->in_drop;
 }
 // the same operand for the input-weight gradient of the backward pass
-const void *backward_input(const cn_layer *l) { return l->dropped ? l->in_drop : l->prev->out_op; }
+const void *backward_input(const cn_layer *l) { return l->dropped ? l->in_drop : follower_operand(l->prev); }
 // behind K8 on the main stream: the error handed to the preceding layer passes the forward pass's mask
 void mask_handed_back_error(cn_layer *l)
 {
@@ -1079,6 +1117,7 @@ void lstm_forward(cn_layer *l)
         if (!launch_lstm_cluster(c->stream, c->prec, false, r, &c->xch_epoch)) { check_rec_lds(l, false); launch_lstm_forward(c->stream, c->prec, r); }
         HIP_CHECK(hipGetLastError());
     }
+    residual_sum(l);
 }
 
 void lstm_backward(cn_layer *l)
@@ -1119,6 +1158,7 @@ void lstm_backward(cn_layer *l)
         fork_attached = fork != nullptr;
     }
     if (l->prev->trainable) mask_handed_back_error(l);    // (K8 carries the fork: K9 does not read prev->err and starts beside this)
+    residual_add_error(l, l->err);        // (the recurrent kernels only read l->err: LstmRec::err is const, the hand-written loops only load from it)
     // K9 runs on the side stream: it only feeds weightUpdates, forked AFTER K8 so the critical-path GEMM has the chip to itself, and running beside the
     // preceding layer's recurrent kernel (which occupies ~10 % of the CUs)
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
@@ -1207,6 +1247,7 @@ void ff_forward(cn_layer *l)
         c->rowstat_of = stat ? l : nullptr;
         if (!c->f32 && l->has_follower) launch_pad_convert(c->stream, false, l->out_f32, c->N, l->Lp, l->out_op, l->Lp);
     }
+    residual_sum(l);
 }
 
 void ff_backward(cn_layer *l)
@@ -1233,7 +1274,10 @@ void ff_backward(cn_layer *l)
         } else {
             l->err_in_delta = false;
             if (l->kind == CN_LAYER_SOFTMAX) l->sm_lazy_next = false;   // no fused consumer: lazy rows would be normalised on demand every pass
-            const float *y = posteriors(l);
+            const float *y = posteriors(l);                 // (the branch: act' of a marked layer is taken at its own output, not at the sum)
+            // a marked layer hands its outputErrors on as they came in: launch_ff_delta below overwrites them in place
+            if (l->summed && l->prev->trainable)
+                HIP_CHECK(hipMemcpyAsync(l->res_e, l->err, (size_t)N * l->Lp * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             if (l->mcc_pending) launch_mcc_backward(c->stream, y, c->d_tcls, N, l->size, l->Lp, l->err);
             if (l->kind == CN_LAYER_SOFTMAX) launch_softmax_bwd(c->stream, y, l->err, c->d_pat, N, l->size, l->Lp);
             launch_ff_delta(c->stream, c->f32, ff_act(l->kind), y, l->err, l->delta_op, N, l->size, l->Lp);
@@ -1254,6 +1298,7 @@ void ff_backward(cn_layer *l)
         fork_attached = fork != nullptr;
     }
     if (l->prev->trainable) mask_handed_back_error(l);
+    residual_add_error(l, l->res_e);
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
         const bool fused = armed_fused(l);
         const bool defer = c->det && fused;
@@ -1765,6 +1810,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
         case CN_LAYER_MULTICLASS_CLASSIFICATION: {
             if (!preceding->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: a post output layer needs a trainable preceding layer");
             if (preceding->lstm) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: post output layers directly after an LSTM layer are not supported");
+            if (preceding->residual) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: a post output layer directly after a residual layer is not supported");
             const bool paired = kind == CN_LAYER_WEIGHTEDSSE || kind == CN_LAYER_SSE_MASK;
             // PostOutputLayer.cpp:58-59; the weighted layers take (target, weight) pairs: WeightedSsePostOutputLayer.cu:103, SseMaskPostOutputLayer.cu:103
             if (paired ? size != 2 * preceding->size : size != preceding->size)
@@ -2416,8 +2462,9 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
         case CN_BUF_OUTPUTS:
             if (layer->kind == CN_LAYER_INPUT)        // the operand copy of the inputs (bf16 mode: rounded to bf16)
                 launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            else if (layer->lstm)
-                for (int d = 0; d < layer->dirs; ++d) launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, d * Hp, 1, N, H, tmp, layer->size, d * H, c->PS, c->PSp);
+            else if (layer->lstm)     // (a marked layer: the sum its followers read)
+                for (int d = 0; d < layer->dirs; ++d) launch_unpad(c->stream, opbf, follower_operand(layer), layer->Lp, d * Hp, 1, N, H, tmp, layer->size, d * H, c->PS, c->PSp);
+            else if (layer->summed) launch_unpad(c->stream, opbf, layer->res_sum, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
             else if (layer->trainable) launch_unpad(c->stream, false, posteriors(layer), layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
             else throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no outputs");
             break;
@@ -2683,6 +2730,50 @@ int cn_layer_set_learning_rate(cn_layer *layer, float learning_rate)
     if (!layer->trainable) { g_last_error = "cn_layer_set_learning_rate: layer has no weights"; return CN_ERR_BAD_ARG; }
     layer->own_lr = learning_rate;
     return CN_OK;
+}
+
+// ---- residual connections (include/currennt_hip.h, section Residual connections) ----
+int cn_layer_set_residual(cn_layer *layer, int enable)
+{
+    if (!layer) { g_last_error = "cn_layer_set_residual: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        const bool kind_ok = layer->lstm || layer->kind == CN_LAYER_FF_TANH || layer->kind == CN_LAYER_FF_LOGISTIC || layer->kind == CN_LAYER_FF_IDENTITY;
+        if (!kind_ok) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_residual: only lstm, blstm and feedforward_* layers can be residual");
+        if (layer->size != layer->prev->size)
+            throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_residual: a residual layer must have the size of its preceding layer (" +
+                                           std::to_string(layer->size) + " vs. " + std::to_string(layer->prev->size) + ")");
+        for (const cn_layer *o : layer->ctx->layers)
+            if (o->prev == layer && o->post)
+                throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_residual: a residual layer directly in front of a post output layer is not supported");
+        if (enable && !layer->res_sum) {          // like out_op: same size, cleared once
+            enter(layer->ctx);
+            layer->res_sum = dalloc(layer, layer->maxN() * layer->Lp * layer->ctx->esz());
+            if (!layer->lstm) layer->res_e = (float *)dalloc(layer, layer->maxN() * layer->Lp * sizeof(float));
+        }
+        layer->residual = enable != 0;
+    });
+}
+
+int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_dbg_residual_branch: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        require_loaded(c);
+        if (!layer->summed) throw cn_error(CN_ERR_STATE, "cn_dbg_residual_branch: the layer's last forward pass did not sum");
+        const int N = c->Next;
+        if (count != (size_t)N * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_dbg_residual_branch: count != T*PS*size");
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
+        const bool opbf = !c->f32;
+        if (layer->lstm)
+            for (int d = 0; d < layer->dirs; ++d)
+                launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, d * layer->Hp, 1, N, layer->H, tmp, layer->size, d * layer->H, c->PS, c->PSp);
+        else launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
+        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
 }
 
 // ---- dropout (include/currennt_hip.h, section Dropout) ----

@@ -308,6 +308,19 @@ struct DropArgs {
 void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *src, void *dst);
 // err[N][Pp] (fp32) masked and rescaled in place with the same key
 void launch_dropout_bwd(hipStream_t s, const DropArgs &a, float *err);
+// ---- residual connections (include/currennt_hip.h, section Residual connections; cn_residual.hip) ----
+// The geometry of one forward pass of one marked layer: N = T * PSp rows, L units in both layers; the marked layer's rows are Lp
+// wide with its units at the columns of (H, Hp, dirs), the preceding layer's xLp wide with (xH, xHp, xdirs) -- H = 0: a dense
+// layer or the input layer, unit u at column u; else direction d's units at columns [d * Hp, d * Hp + H).  same_map: unit u has
+// the same column in both (the 16-byte path).  Every row width and Hp is a multiple of 32.
+struct ResArgs {
+    int N, L, Lp, H, Hp, dirs, xLp, xH, xHp, xdirs, same_map;
+};
+// sum[N][Lp] (op) = branch[N][Lp] (op) + x[N][xLp] (op), one rounding to the operand type, on the rows with pat[row] != 0;
+// the branch on the other rows (dummy frames, pad slots); pad columns are written as zeros
+void launch_residual_fwd(hipStream_t s, bool f32, const ResArgs &a, const char *pat, const void *branch, const void *x, void *sum);
+// prev_err[N][xLp] (fp32) += e[N][Lp] (fp32) on the rows with pat[row] != 0, unit by unit
+void launch_residual_bwd(hipStream_t s, const ResArgs &a, const char *pat, const float *e, float *prev_err);
 // delta = act'(y) * err (in place on err, all N slots: FeedForwardLayer.cu:72-79), op copy for the GEMMs
 void launch_ff_delta(hipStream_t s, bool f32, int act, const float *y, float *err, void *delta_op, int N, int L, int Lp);
 // column sums of delta over the N slots (FeedForwardLayer.cu:82-102): colsum[j] += sum_n err[n][j]

@@ -16,7 +16,7 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
     , m_name(layerChild.hasMember("name") ? layerChild["name"].getString() : "")
     , m_size(layerChild.hasMember("size") ? layerChild["size"].getInt() : 0)
     , m_parallelSequences(parallelSequences), m_maxSeqLength(maxSeqLength)
-    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0)
+    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0), m_residual(false)
 {
     if (!layerChild.hasMember("name")) throw std::runtime_error("Missing value 'name' in layer description");       // Layer.cpp:52-53
     if (m_name.empty()) throw std::runtime_error("Empty layer name in layer description");                           // :54-55
@@ -27,8 +27,24 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
                                kind == CN_LAYER_FF_IDENTITY || kind == CN_LAYER_SOFTMAX;
     if (layerChild.hasMember("dropout") && !trainableKind)
         throw std::runtime_error("Invalid value 'dropout' in layer '" + m_name + "': only lstm, blstm, feedforward_* and softmax layers take dropout");
+    // "residual": true marks a hidden layer whose followers read its output plus its input (include/currennt_hip.h, section
+    // Residual connections; the reference has none).  The three refusals are the library's, said here with the layer's name.
+    if (layerChild.hasMember("residual")) {
+        const bool residualKind = trainableKind && kind != CN_LAYER_SOFTMAX;
+        if (layerChild["residual"].type() != json::Value::Bool)
+            throw std::runtime_error("Invalid value 'residual' in layer '" + m_name + "': true or false expected");
+        if (!residualKind)
+            throw std::runtime_error("Invalid value 'residual' in layer '" + m_name + "': only lstm, blstm and feedforward_* layers can be residual");
+        m_residual = layerChild["residual"].getBool();
+        if (m_residual && m_size != precedingLayer->size())
+            throw std::runtime_error("Invalid value 'residual' in layer '" + m_name + "': the layer's size " + std::to_string(m_size) +
+                                     " differs from the preceding layer's size " + std::to_string(precedingLayer->size()));
+    }
+    if (precedingLayer && precedingLayer->residual() && !trainableKind)
+        throw std::runtime_error("Invalid value 'residual' in layer '" + precedingLayer->name() + "': a post output layer cannot follow a residual layer directly");
     hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
                              precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
+    if (m_residual) hipCheck(cn_layer_set_residual(m_handle, 1), ctx);
 }
 
 Layer::~Layer() {}     // device memory belongs to the context (cn_ctx_destroy)
@@ -135,6 +151,7 @@ void TrainableLayer::exportLayer(json::Value *layersArray) const
     Layer::exportLayer(layersArray);
     (*layersArray)[layersArray->size() - 1].addMember("bias", (double)m_bias);
     if (m_dropout > 0) (*layersArray)[layersArray->size() - 1].addMember("dropout", (double)m_dropout);
+    if (residual()) (*layersArray)[layersArray->size() - 1].addMember("residual", true);
 }
 
 // ---- FeedForward / Softmax / Lstm -----------------------------------------------------------

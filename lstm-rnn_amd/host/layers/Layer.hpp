@@ -32,6 +32,7 @@ public:
     virtual const std::string &type() const = 0;
     virtual bool isTrainable() const { return false; }
     virtual bool isPostOutput() const { return false; }
+    bool residual() const { return m_residual; }          // JSON "residual": followers read this layer's output plus its input
 
     Hip::real_vector outputs() const;                     // Layer.hpp:132
     Hip::real_vector outputErrors() const;                // Layer.hpp:153
@@ -53,6 +54,7 @@ protected:
     int m_size;
     int m_parallelSequences, m_maxSeqLength, m_curMaxSeqLength, m_curMinSeqLength, m_curNumSeqs;
     Hip::pattype_vector m_patTypes;
+    bool m_residual;
 };
 
 class InputLayer : public Layer {                         // layers/InputLayer.{hpp,cpp}

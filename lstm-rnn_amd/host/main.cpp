@@ -90,6 +90,7 @@ void printLayers(const NeuralNetwork &nn)                                       
         printf("[size: %d", nn.layers()[i]->size());
         const layers::TrainableLayer *tl = dynamic_cast<const layers::TrainableLayer *>(nn.layers()[i].get());
         if (tl) { printf(", bias: %.1lf, weights: %d", (double)tl->bias(), tl->weightCount()); weights += tl->weightCount(); }
+        if (nn.layers()[i]->residual()) printf(", residual");
         printf("]\n");
     }
     printf("Total weights: %d\n", weights);

@@ -14,6 +14,7 @@ from . import binding as B
 
 _TRAINABLE = ("lstm", "blstm", "softmax", "feedforward_tanh", "feedforward_logistic",
               "feedforward_identity")
+_RESIDUAL = ("lstm", "blstm", "feedforward_tanh", "feedforward_logistic", "feedforward_identity")
 _POST = ("sse", "multiclass_classification", "weightedsse", "wf", "ce", "rmse", "binary_classification", "ctc")
 
 
@@ -35,6 +36,8 @@ class Layer:
             raise RuntimeError("Missing value 'bias' in layer '%s'" % self.name)       # TrainableLayer.cu:61-62
         self.bias = float(desc.get("bias", 0.0))
         self.learning_rate = float(desc.get("learningRate", -1.0))                     # TrainableLayer.cu:58
+        if prev is not None and self.post and getattr(prev, "residual", False):       # (as the C++ driver; the library refuses the layer too)
+            raise RuntimeError("Invalid value 'residual' in layer '%s': a post output layer cannot follow a residual layer directly" % prev.name)
         h = C.c_void_p()
         L = net.lib
         B.check(L.cn_layer_create(net.ctx, B.LAYER_KINDS[self.type], prev.handle if prev else None,
@@ -54,6 +57,19 @@ class Layer:
             if not 0.0 <= self.dropout < 1.0:
                 raise RuntimeError("Invalid value 'dropout' in layer '%s': the rate must lie in [0, 1)" % self.name)
             self.set_dropout(self.dropout)
+        # "residual": followers read this layer's output plus its input (include/currennt_hip.h, section Residual connections)
+        self.residual = False
+        if "residual" in desc:
+            # (the same refusals, with the same texts, as the C++ driver's Layer constructor)
+            if not isinstance(desc["residual"], bool):
+                raise RuntimeError("Invalid value 'residual' in layer '%s': true or false expected" % self.name)
+            if self.type not in _RESIDUAL:
+                raise RuntimeError("Invalid value 'residual' in layer '%s': only lstm, blstm and feedforward_* layers can be residual" % self.name)
+            if desc["residual"]:
+                if self.size != prev.size:
+                    raise RuntimeError("Invalid value 'residual' in layer '%s': the layer's size %d differs from the preceding layer's size %d"
+                                       % (self.name, self.size, prev.size))
+                self.set_residual(True)
         if self.type in ("lstm", "blstm"):
             self.dirs = 2 if self.type == "blstm" else 1
             self.H = self.size // self.dirs
@@ -104,6 +120,20 @@ class Layer:
         out = np.empty(n, np.float32)
         B.check(self.net.lib.cn_dbg_dropout_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
         return out.reshape(self.net.T, self.net.PS, self.prev.size)
+
+    def set_residual(self, enable=True):
+        """cn_layer_set_residual: from this layer's next forward pass on, its followers and outputs() see its own output plus
+        what its preceding layer's followers see."""
+        B.check(self.net.lib.cn_layer_set_residual(self.handle, 1 if enable else 0), self.net.ctx)
+        self.residual = bool(enable)
+
+    def residual_branch(self):
+        """This layer's own output in its last forward pass, [T][PS][size] (cn_dbg_residual_branch): outputs() minus the skip
+        path; CN_ERR_STATE when that pass did not sum."""
+        n = self.net.N * self.size
+        out = np.empty(n, np.float32)
+        B.check(self.net.lib.cn_dbg_residual_branch(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
+        return out.reshape(self.net.T, self.net.PS, self.size)
 
     def noisy_weights(self):
         """The weights this layer's last backward pass read, flat reference layout (cn_dbg_noisy_weights): w + noise as the noisy
