@@ -586,6 +586,45 @@ int  cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a);
  * allocates the layer's sum buffer (the size of its operand copy; a feed-forward layer: also an fp32 copy of its outputErrors). */
 int  cn_layer_set_residual(cn_layer *layer, int enable);
 
+/* ---- Layer normalization (no counterpart in the reference; Ba et al. 2016, "pre-LN": in front of the weighted path) ---------------
+ * A trainable layer l (lstm, blstm, feedforward_*, softmax) may be marked: its input products then read a normalised copy of what
+ * its preceding layer's followers read.  The preceding layer may be of any kind, the input layer included; its size P must be >= 2.
+ *
+ * The rule.  For a real frame n (pattern type not NONE, slot < PS), with x_i, i = 0..P-1, the operand values the preceding
+ * layer's followers read for that frame (its sum if it is residual, never a dropped copy), taken as floats:
+ *      mean = (1/P) sum_i x_i          var = (1/P) sum_i (x_i - mean)^2        two passes over the row, both sums formed in double
+ *      rstd = 1 / sqrt(var + eps)      in double; mean and rstd each rounded once to float: mean_f, rstd_f
+ *      xn_i = round_op( mul_rn( sub_rn(x_i, mean_f), rstd_f ) )
+ * Every *_rn is a single fp32 operation rounded to nearest, no contraction; round_op: ONE rounding to the operand type
+ * (CN_PREC_F32 / CN_PREC_BF16X3: none; CN_PREC_BF16: to nearest even); eps is the layer's, default 1e-5.  The order in which the
+ * double sums are formed is the kernel's own: the result is held to a bound, not to bits, and is the same bits from run to run.
+ * Units are the reference layout's: pad columns take no part in a statistic and are written as zeros.  Rows that are not real
+ * frames (dummy frames, pad slots) are written as zeros, which keeps the row map's condition that every operand row of a dummy
+ * frame is zero.
+ *
+ * There is no learned gain and no bias: xn is read only by l's own input products, and
+ *      W (gamma * xn + beta) + b = (W diag gamma) xn + (W beta + b),
+ * so a gain is absorbed by the columns of the input weights and a bias by the layer's bias weights (for an LSTM layer for all
+ * four gates at once).  Nothing is added to the weights, the optimizers, the clipping norm or the all-reduce, and nothing is
+ * summed over frames.
+ *
+ * Forward.  l's input products (and the input-weight gradient) read xn.  If l also drops, the dropout mask is applied to xn: the
+ * order is normalisation, then dropout.  The preceding layer's own outputs, CN_BUF_OUTPUTS and a residual skip path never see the
+ * normalisation: a residual l adds its un-normalised input.  This is part of the model, not a regulariser: every forward pass
+ * normalises.
+ *
+ * Backward.  When the preceding layer is trainable, what l's backward pass hands back (after the dropout mask if l drops), g =
+ * dL/d xn, is rewritten in place, in front of a residual l's skip term, as
+ *      dx_i = rstd_f * ( g_i - mean(g) - xn_i * mean(g * xn) )        on real frames;  0 on every other row
+ * with xn as the forward pass stored it (after round_op), rstd_f as the forward pass stored it, and both means formed in double over
+ * the P units and rounded once to float.  Each layer's backward pass goes by what its forward pass did.
+ *
+ * With no layer marked the library launches exactly what it launches without this call and allocates nothing for it. */
+/* The JSON "layer_norm" / "layer_norm_eps" of a layer.  CN_ERR_BAD_ARG: a layer that is not trainable; a preceding layer of size 1;
+ * eps not finite or <= 0.  May be called between fractions; takes effect with the layer's next forward pass.  The first enabling
+ * call allocates the normalised copy (the size of the preceding layer's operand copy) and one float per row. */
+int  cn_layer_set_layer_norm(cn_layer *layer, int enable, float eps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,12 @@ int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count);
  * that pass did not sum.  [sync] */
 int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count);
 
+/* The normalised copy of a layer's input (include/currennt_hip.h, section Layer normalization), as its last forward pass left it:
+ * reference layout [T * PS][P], P the preceding layer's size, widened to float; count = T * PS * P, anything else: CN_ERR_SHAPE.
+ * CN_ERR_STATE when that pass did not normalise.  A layer that also drops keeps both copies: cn_dbg_dropout_input returns what
+ * its input products read, the masked copy of this one.  [sync] */
+int cn_dbg_layer_norm_input(cn_layer *layer, float *host, size_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ EXPORTS = [
     "cn_ctx_set_input_augment",
     # include/currennt_hip.h, section Residual connections, and its hook in include/currennt_hip_debug.h
     "cn_layer_set_residual", "cn_dbg_residual_branch",
+    # include/currennt_hip.h, section Layer normalization, and its hook in include/currennt_hip_debug.h
+    "cn_layer_set_layer_norm", "cn_dbg_layer_norm_input",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -201,6 +203,8 @@ def load_library():
     L.cn_dbg_dropout_input.argtypes = [vp, vp, C.c_size_t]
     L.cn_layer_set_residual.argtypes = [vp, ci]
     L.cn_dbg_residual_branch.argtypes = [vp, vp, C.c_size_t]
+    L.cn_layer_set_layer_norm.argtypes = [vp, ci, cf]
+    L.cn_dbg_layer_norm_input.argtypes = [vp, vp, C.c_size_t]
     L.cn_ctx_set_grad_clip.argtypes = [vp, cf]
     L.cn_ctx_grad_clip_stats.argtypes = [vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(cf), ci]
     L.cn_ctx_set_weight_noise.argtypes = [vp, cf, C.c_uint64, C.c_uint64]

@@ -259,6 +259,14 @@ struct cn_layer {
     bool dropped = false;                 // the last forward pass dropped ...
     DropArgs drop{};                      // ... with this key: what its backward pass masks the handed-back error with
 
+    // layer normalization of this layer's input (include/currennt_hip.h, section Layer normalization)
+    bool layer_norm = false;              // cn_layer_set_layer_norm
+    float ln_eps = 1e-5f;
+    void *in_norm = nullptr;              // [maxN][Pp] (op) normalised copy of what the preceding layer's followers read; allocated when first enabled
+    float *ln_rstd = nullptr;             // [maxN] 1 / sqrt(var + eps) of every row of the last forward pass
+    bool normed = false;                  // the last forward pass normalised ...
+    LnArgs ln{};                          // ... with this eps and geometry: what its backward pass goes by
+
     // residual connection around this layer (include/currennt_hip.h, section Residual connections)
     bool residual = false;                // cn_layer_set_residual
     void *res_sum = nullptr;              // [maxN][Lp] (op) out_op + what the preceding layer's followers read; allocated when first enabled
@@ -985,15 +993,43 @@ void residual_add_error(cn_layer *l, const float *e)
     launch_residual_bwd(l->ctx->stream, l->res, l->ctx->d_pat, e, l->prev->err);
 }
 
+// ---- layer normalization of a layer's input (include/currennt_hip.h, section Layer normalization) ----
+// in front of K1 (and of the dropout copy): the normalised copy of what the preceding layer's followers read.  The layer records
+// that it normalised, with which eps and geometry; its backward pass goes by the record.
+const void *normalized_input(cn_layer *l, const void *x)
+{
+    cn_ctx *c = l->ctx;
+    l->normed = l->layer_norm;
+    if (!l->normed) return x;
+    const cn_layer *p = l->prev;
+    LnArgs &a = l->ln;
+    a.N = c->N; a.P = l->P; a.Pp = l->Pp; a.PS = c->PS; a.PSp = c->PSp; a.eps = l->ln_eps;
+    a.prevH = p->lstm ? p->H : 0; a.prevHp = p->lstm ? p->Hp : 0; a.prevDirs = p->lstm ? p->dirs : 0;
+    Timed tm(c, KC_OTHER);
+    launch_layernorm_fwd(c->stream, c->f32, a, c->d_pat, x, l->in_norm, l->ln_rstd);
+    return l->in_norm;
+}
+// behind K8 and mask_handed_back_error on the main stream, in front of residual_add_error: what K8 wrote is dL/d(normalised
+// copy); the preceding layer's outputErrors become dL/d(its output) along the weighted path.  (K9 reads in_norm on the side
+// stream meanwhile; nobody writes it.)
+void normalize_handed_back_error(cn_layer *l)
+{
+    if (!l->normed || !l->prev->trainable) return;
+    Timed tm(l->ctx, KC_OTHER);
+    launch_layernorm_bwd(l->ctx->stream, l->ctx->f32, l->ln, l->ctx->d_pat, l->in_norm, l->ln_rstd, l->prev->err);
+}
+
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
-// The operand a layer's input products read in this forward pass: the preceding layer's operand copy, or -- when the pass drops --
-// the masked copy, written here in front of K1.  The layer records whether it dropped and with which key: its backward pass
-// (the input-weight gradient's operand, the mask of the error it hands back) goes by the record, not by the context's state then.
+// The operand a layer's input products read in this forward pass: the preceding layer's operand copy (normalised first when the
+// layer is marked for it), or -- when the pass drops -- the masked copy of that, written here in front of K1.  The layer records
+// whether it dropped and with which key: its backward pass (the input-weight gradient's operand, the mask of the error it hands
+// back) goes by the record, not by the context's state then.
 const void *forward_input(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
+    const void *x = normalized_input(l, follower_operand(l->prev));
     l->dropped = c->drop_enable && l->drop_rate > 0.f;
-    if (!l->dropped) return follower_operand(l->prev);
+    if (!l->dropped) return x;
     DropArgs &a = l->drop;
     a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.P = l->P; a.Pp = l->Pp;
     a.prevH = l->prev->lstm ? l->prev->H : 0; a.prevHp = l->prev->lstm ? l->prev->Hp : 0; a.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
@@ -1002,11 +1038,11 @@ const void *forward_input(cn_layer *l)
     a.thr = (uint32_t)std::floor((double)l->drop_rate * 4294967296.0);
     a.scale = (float)(1.0 / (1.0 - (double)l->drop_rate));
     Timed tm(c, KC_OTHER);
-    launch_dropout_fwd(c->stream, c->f32, a, follower_operand(l->prev), l->in_drop);
+    launch_dropout_fwd(c->stream, c->f32, a, x, l->in_drop);
     return l->in_drop;
 }
 // the same operand for the input-weight gradient of the backward pass
-const void *backward_input(const cn_layer *l) { return l->dropped ? l->in_drop : follower_operand(l->prev); }
+const void *backward_input(const cn_layer *l) { return l->dropped ? l->in_drop : l->normed ? l->in_norm : follower_operand(l->prev); }
 // behind K8 on the main stream: the error handed to the preceding layer passes the forward pass's mask
 void mask_handed_back_error(cn_layer *l)
 {
@@ -1158,6 +1194,7 @@ void lstm_backward(cn_layer *l)
         fork_attached = fork != nullptr;
     }
     if (l->prev->trainable) mask_handed_back_error(l);    // (K8 carries the fork: K9 does not read prev->err and starts beside this)
+    normalize_handed_back_error(l);
     residual_add_error(l, l->err);        // (the recurrent kernels only read l->err: LstmRec::err is const, the hand-written loops only load from it)
     // K9 runs on the side stream: it only feeds weightUpdates, forked AFTER K8 so the critical-path GEMM has the chip to itself, and running beside the
     // preceding layer's recurrent kernel (which occupies ~10 % of the CUs)
@@ -1298,6 +1335,7 @@ void ff_backward(cn_layer *l)
         fork_attached = fork != nullptr;
     }
     if (l->prev->trainable) mask_handed_back_error(l);
+    normalize_handed_back_error(l);
     residual_add_error(l, l->res_e);
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
         const bool fused = armed_fused(l);
@@ -2771,6 +2809,47 @@ int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count)
             for (int d = 0; d < layer->dirs; ++d)
                 launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, d * layer->Hp, 1, N, layer->H, tmp, layer->size, d * layer->H, c->PS, c->PSp);
         else launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
+        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
+// ---- layer normalization (include/currennt_hip.h, section Layer normalization) ----
+int cn_layer_set_layer_norm(cn_layer *layer, int enable, float eps)
+{
+    if (!layer) { g_last_error = "cn_layer_set_layer_norm: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_layer_norm: only lstm, blstm, feedforward_* and softmax layers normalise their input");
+        if (layer->P < 2) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_layer_norm: the preceding layer must have at least 2 units");
+        if (!std::isfinite(eps) || !(eps > 0.f)) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_layer_norm: eps must be finite and > 0");
+        if (enable && !layer->in_norm) {          // like the preceding layer's out_op: same size, cleared once
+            enter(layer->ctx);
+            layer->in_norm = dalloc(layer, layer->maxN() * layer->Pp * layer->ctx->esz());
+            layer->ln_rstd = (float *)dalloc(layer, layer->maxN() * sizeof(float));
+        }
+        layer->layer_norm = enable != 0;
+        layer->ln_eps = eps;
+    });
+}
+
+int cn_dbg_layer_norm_input(cn_layer *layer, float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_dbg_layer_norm_input: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        require_loaded(c);
+        if (!layer->trainable || !layer->normed) throw cn_error(CN_ERR_STATE, "cn_dbg_layer_norm_input: the layer's last forward pass did not normalise");
+        // the geometry of the forward pass that wrote the copy (its record), not of whatever fraction is loaded now
+        const LnArgs &a = layer->ln;
+        const int frames = a.N / a.PSp * a.PS;
+        if (count != (size_t)frames * a.P) throw cn_error(CN_ERR_SHAPE, "cn_dbg_layer_norm_input: count != T*PS*size of the preceding layer (of that forward pass)");
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
+        const bool opbf = !c->f32;
+        if (a.prevH)
+            for (int d = 0; d < a.prevDirs; ++d) launch_unpad(c->stream, opbf, layer->in_norm, a.Pp, d * a.prevHp, 1, frames, a.prevH, tmp, a.P, d * a.prevH, a.PS, a.PSp);
+        else launch_unpad(c->stream, opbf, layer->in_norm, a.Pp, 0, 1, frames, a.P, tmp, a.P, 0, a.PS, a.PSp);
         HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
     });

@@ -308,6 +308,19 @@ struct DropArgs {
 void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *src, void *dst);
 // err[N][Pp] (fp32) masked and rescaled in place with the same key
 void launch_dropout_bwd(hipStream_t s, const DropArgs &a, float *err);
+// ---- layer normalization of a layer's input (include/currennt_hip.h, section Layer normalization; cn_layernorm.hip) ----
+// The geometry of one forward pass of one marked layer: N = T * PSp rows of Pp columns holding the preceding layer's P units
+// (prevH = 0: dense, units [0, P); else direction d's units at columns [d * prevHp, d * prevHp + prevH)); Pp and prevHp are
+// multiples of 32.  PS / PSp: slots per time step without and with pad slots (what the debug hook unpads with).
+struct LnArgs {
+    int N, P, Pp, prevH, prevHp, prevDirs, PS, PSp;
+    float eps;
+};
+// xn[N][Pp] (op) = the normalised x[N][Pp] (op) on the rows with pat[row] != 0, zeros on the other rows (dummy frames, pad slots)
+// and in pad columns; rstd[N]: 1 / sqrt(var + eps) of every real row as a float, 0 elsewhere
+void launch_layernorm_fwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *x, void *xn, float *rstd);
+// err[N][Pp] (fp32), dL/d xn, rewritten in place as dL/dx from the forward pass's xn and rstd; zeros on the rows with pat[row] == 0
+void launch_layernorm_bwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *xn, const float *rstd, float *err);
 // ---- residual connections (include/currennt_hip.h, section Residual connections; cn_residual.hip) ----
 // The geometry of one forward pass of one marked layer: N = T * PSp rows, L units in both layers; the marked layer's rows are Lp
 // wide with its units at the columns of (H, Hp, dirs), the preceding layer's xLp wide with (xH, xHp, xdirs) -- H = 0: a dense

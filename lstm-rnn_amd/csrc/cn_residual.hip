@@ -4,34 +4,13 @@
 //   residual_fwd_kernel   sum[N][Lp] (op)  = branch[N][Lp] (op) + x[N][xLp] (op) on real frames, the branch elsewhere; pad columns 0
 //   residual_bwd_kernel   prev_err[N][xLp] (fp32) += e[N][Lp] (fp32) on real frames
 // Both are streaming kernels: grid-stride loops, no LDS.  Units are matched in the reference layout (unit u of both layers); the
-// padded column of a unit depends on the layer's kind (res_col).  Where the two column maps coincide (ResArgs::same_map) a thread
+// padded column of a unit depends on the layer's kind (res_col, cn_unit_map_device.h).  Where the two column maps coincide (ResArgs::same_map) a thread
 // owns 16 bytes of one row (VEC); otherwise one element, whose partner it looks up (the mapped path).
 #include "cn_internal.h"
+#include "cn_unit_map_device.h"
 
 namespace cn {
 
-// column of unit u in a layer's padded rows: dense layers and a one-directional lstm keep u; a blstm puts direction d's unit j
-// at d * Hp + j (H = 0: dense)
-__device__ __forceinline__ int res_col(int u, int H, int Hp) { return H == 0 ? u : (u / H) * Hp + u % H; }
-// unit of padded column c, or -1 for a pad column
-__device__ __forceinline__ int res_unit(int c, int L, int H, int Hp, int dirs)
-{
-    if (H == 0) return c < L ? c : -1;
-    const int d = c / Hp, j = c % Hp;
-    return (d < dirs && j < H) ? d * H + j : -1;
-}
-// units among the G columns that start at c (a multiple of G; Hp and every row width are multiples of 32, so the G columns lie in
-// one direction and the units among them come first)
-__device__ __forceinline__ int res_units_in_group(int c, int G, int L, int H, int Hp, int dirs)
-{
-    int cnt;
-    if (H == 0) cnt = L - c;
-    else { const int d = c / Hp, j = c % Hp; cnt = d < dirs ? H - j : 0; }
-    return max(0, min(cnt, G));
-}
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned bf16_bits(float v) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)v); }     // (round to nearest even)
 // one 32-bit word of two bf16: element k0 (low half) and k0 + 1 of a group with cnt units; real: add x, else keep the branch
 __device__ __forceinline__ unsigned res_word(unsigned b, unsigned x, int k0, int cnt, bool real)
 {

@@ -1,5 +1,6 @@
 #include "Layer.hpp"
 
+#include <cmath>
 #include <stdexcept>
 
 namespace currennt_hip {
@@ -16,7 +17,7 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
     , m_name(layerChild.hasMember("name") ? layerChild["name"].getString() : "")
     , m_size(layerChild.hasMember("size") ? layerChild["size"].getInt() : 0)
     , m_parallelSequences(parallelSequences), m_maxSeqLength(maxSeqLength)
-    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0), m_residual(false)
+    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0), m_residual(false), m_layerNorm(false), m_layerNormEps(1e-5f)
 {
     if (!layerChild.hasMember("name")) throw std::runtime_error("Missing value 'name' in layer description");       // Layer.cpp:52-53
     if (m_name.empty()) throw std::runtime_error("Empty layer name in layer description");                           // :54-55
@@ -42,9 +43,30 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
     }
     if (precedingLayer && precedingLayer->residual() && !trainableKind)
         throw std::runtime_error("Invalid value 'residual' in layer '" + precedingLayer->name() + "': a post output layer cannot follow a residual layer directly");
+    // "layer_norm": true marks a trainable layer whose input products read a normalised copy of its input, "layer_norm_eps" is the
+    // eps under the square root (include/currennt_hip.h, section Layer normalization; the reference has none).  The refusals are
+    // the library's, said here with the layer's name.
+    if (layerChild.hasMember("layer_norm") || layerChild.hasMember("layer_norm_eps")) {
+        const std::string member = layerChild.hasMember("layer_norm") ? "layer_norm" : "layer_norm_eps";
+        if (!trainableKind)
+            throw std::runtime_error("Invalid value '" + member + "' in layer '" + m_name + "': only lstm, blstm, feedforward_* and softmax layers normalise their input");
+        if (layerChild.hasMember("layer_norm") && layerChild["layer_norm"].type() != json::Value::Bool)
+            throw std::runtime_error("Invalid value 'layer_norm' in layer '" + m_name + "': true or false expected");
+        if (layerChild.hasMember("layer_norm_eps")) {
+            const json::Value &eps = layerChild["layer_norm_eps"];
+            if (!eps.isNumber() || !(eps.getDouble() > 0) || !std::isfinite((float)eps.getDouble()))
+                throw std::runtime_error("Invalid value 'layer_norm_eps' in layer '" + m_name + "': a finite number above 0 expected");
+            m_layerNormEps = (float)eps.getDouble();
+        }
+        m_layerNorm = layerChild.hasMember("layer_norm") && layerChild["layer_norm"].getBool();
+        if (m_layerNorm && precedingLayer->size() < 2)
+            throw std::runtime_error("Invalid value 'layer_norm' in layer '" + m_name + "': the preceding layer's size " +
+                                     std::to_string(precedingLayer->size()) + " is below 2");
+    }
     hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
                              precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
     if (m_residual) hipCheck(cn_layer_set_residual(m_handle, 1), ctx);
+    if (m_layerNorm) hipCheck(cn_layer_set_layer_norm(m_handle, 1, m_layerNormEps), ctx);
 }
 
 Layer::~Layer() {}     // device memory belongs to the context (cn_ctx_destroy)
@@ -152,6 +174,10 @@ void TrainableLayer::exportLayer(json::Value *layersArray) const
     (*layersArray)[layersArray->size() - 1].addMember("bias", (double)m_bias);
     if (m_dropout > 0) (*layersArray)[layersArray->size() - 1].addMember("dropout", (double)m_dropout);
     if (residual()) (*layersArray)[layersArray->size() - 1].addMember("residual", true);
+    if (layerNorm()) {
+        (*layersArray)[layersArray->size() - 1].addMember("layer_norm", true);
+        (*layersArray)[layersArray->size() - 1].addMember("layer_norm_eps", (double)layerNormEps());
+    }
 }
 
 // ---- FeedForward / Softmax / Lstm -----------------------------------------------------------

@@ -34,6 +34,9 @@ public:
     virtual bool isPostOutput() const { return false; }
     bool residual() const { return m_residual; }          // JSON "residual": followers read this layer's output plus its input
 
+    bool layerNorm() const { return m_layerNorm; }        // JSON "layer_norm": this layer's input products read a normalised copy of its input
+    float layerNormEps() const { return m_layerNormEps; } // JSON "layer_norm_eps"
+
     Hip::real_vector outputs() const;                     // Layer.hpp:132
     Hip::real_vector outputErrors() const;                // Layer.hpp:153
 
@@ -55,6 +58,8 @@ protected:
     int m_parallelSequences, m_maxSeqLength, m_curMaxSeqLength, m_curMinSeqLength, m_curNumSeqs;
     Hip::pattype_vector m_patTypes;
     bool m_residual;
+    bool m_layerNorm;
+    float m_layerNormEps;
 };
 
 class InputLayer : public Layer {                         // layers/InputLayer.{hpp,cpp}

@@ -91,6 +91,7 @@ void printLayers(const NeuralNetwork &nn)                                       
         const layers::TrainableLayer *tl = dynamic_cast<const layers::TrainableLayer *>(nn.layers()[i].get());
         if (tl) { printf(", bias: %.1lf, weights: %d", (double)tl->bias(), tl->weightCount()); weights += tl->weightCount(); }
         if (nn.layers()[i]->residual()) printf(", residual");
+        if (nn.layers()[i]->layerNorm()) printf(", layer_norm");
         printf("]\n");
     }
     printf("Total weights: %d\n", weights);

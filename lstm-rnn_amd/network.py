@@ -70,6 +70,25 @@ class Layer:
                     raise RuntimeError("Invalid value 'residual' in layer '%s': the layer's size %d differs from the preceding layer's size %d"
                                        % (self.name, self.size, prev.size))
                 self.set_residual(True)
+        # "layer_norm": this layer's input products read a normalised copy of its input (include/currennt_hip.h, section Layer
+        # normalization); "layer_norm_eps": the eps under the square root, default 1e-5
+        self.layer_norm, self.layer_norm_eps = False, 1e-5
+        if "layer_norm" in desc or "layer_norm_eps" in desc:
+            # (the same refusals, with the same texts, as the C++ driver's Layer constructor)
+            member = "layer_norm" if "layer_norm" in desc else "layer_norm_eps"
+            if not self.trainable:
+                raise RuntimeError("Invalid value '%s' in layer '%s': only lstm, blstm, feedforward_* and softmax layers normalise their input"
+                                   % (member, self.name))
+            if not isinstance(desc.get("layer_norm", False), bool):
+                raise RuntimeError("Invalid value 'layer_norm' in layer '%s': true or false expected" % self.name)
+            eps = desc.get("layer_norm_eps", 1e-5)
+            if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0.0 < float(eps) < float("inf")):
+                raise RuntimeError("Invalid value 'layer_norm_eps' in layer '%s': a finite number above 0 expected" % self.name)
+            self.layer_norm_eps = float(eps)
+            if desc.get("layer_norm", False):
+                if prev.size < 2:
+                    raise RuntimeError("Invalid value 'layer_norm' in layer '%s': the preceding layer's size %d is below 2" % (self.name, prev.size))
+                self.set_layer_norm(True, self.layer_norm_eps)
         if self.type in ("lstm", "blstm"):
             self.dirs = 2 if self.type == "blstm" else 1
             self.H = self.size // self.dirs
@@ -134,6 +153,20 @@ class Layer:
         out = np.empty(n, np.float32)
         B.check(self.net.lib.cn_dbg_residual_branch(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
         return out.reshape(self.net.T, self.net.PS, self.size)
+
+    def set_layer_norm(self, enable=True, eps=1e-5):
+        """cn_layer_set_layer_norm: from this layer's next forward pass on, its input products read the normalised copy of what
+        its preceding layer's followers see (no gain, no bias: the input and bias weights absorb them)."""
+        B.check(self.net.lib.cn_layer_set_layer_norm(self.handle, 1 if enable else 0, float(eps)), self.net.ctx)
+        self.layer_norm, self.layer_norm_eps = bool(enable), float(eps)
+
+    def normalized_input(self):
+        """The normalised copy of this layer's input in its last forward pass, [T][PS][size of the preceding layer]
+        (cn_dbg_layer_norm_input); CN_ERR_STATE when that pass did not normalise."""
+        n = self.net.N * self.prev.size
+        out = np.empty(n, np.float32)
+        B.check(self.net.lib.cn_dbg_layer_norm_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
+        return out.reshape(self.net.T, self.net.PS, self.prev.size)
 
     def noisy_weights(self):
         """The weights this layer's last backward pass read, flat reference layout (cn_dbg_noisy_weights): w + noise as the noisy
