@@ -354,6 +354,50 @@ int  cn_ctx_timing_reset(cn_ctx *ctx);
  * "lstm_bwd_cluster_kernel<0,256,128,1>"; "" for other layers and before the first pass */
 const char *cn_layer_recurrent_kernel(cn_layer *layer, int backward);
 
+/* ---- Weight averaging (no counterpart in the reference; Polyak & Juditsky 1992, the exponential form of Tarvainen & Valpola
+ *      2017) ------------------------------------------------------------------------------------------------------------------
+ * An exponential moving average of the weights beside the weights themselves, and the exchange of the two: a validation pass, a
+ * stopping decision and an exported network may then use the smoothed model while training goes on with the raw one.
+ *
+ * State.  avg is ONE fp32 vector the length of the parameter arena (`count` of cn_ctx_param_arena, arena order, pad entries
+ * included), an allocation of its own made by the first call that needs it.  The library keeps no clock (as with Adam's `step`):
+ * the caller gives the decay of each step.
+ *
+ * The step, per arena entry, from the float argument `decay` in [0, 1):
+ *      omd = (float)(1.0 - (double)decay)                                    rounded once
+ *      avg = (omd == 1.0f) ? w : add_rn(avg, mul_rn(omd, sub_rn(w, avg)))
+ * Every *_rn is a single fp32 operation rounded to nearest, no contraction, denormals kept, as for Adam.  omd == 1 is an exact copy
+ * (avg + (w - avg) is not w in fp32: avg = 1, w = 1e-10).  The FIRST step of a context -- no average exists yet and none was
+ * uploaded -- copies, whatever the decay.  The step does not look at the clipping record: behind a skipped update it moves avg
+ * towards the unchanged w.  Data-parallel: every rank averages the same weights, so the replicas stay bit-identical without an
+ * exchange.
+ *
+ * The swap exchanges w and avg entry by entry over the arena and toggles the context's "swapped" flag; every trainable layer's
+ * operand copies become stale (what cn_ctx_weights_touched does), the noisy sets too.  The next forward pass reads the average; a
+ * second swap restores every bit.  While swapped, cn_layer_read(CN_BUF_WEIGHTS) returns the average and
+ * cn_layer_read_weight_average the raw weights; forward passes, loads, loss calls and reads stay allowed, and everything that
+ * would train on, update or overwrite the exchanged weights fails with CN_ERR_STATE: cn_layer_backward, cn_sgd_update*,
+ * cn_adam_update*, cn_ctx_arm_update, cn_ctx_arm_adam, cn_ctx_accumulate_updates, cn_ctx_take_accumulated, cn_allreduce_grads,
+ * cn_ctx_average_weights, cn_layer_set_weights, cn_layer_upload, cn_layer_upload_weight_average.
+ *
+ * Without any of these calls the library launches exactly what it launches without them and allocates nothing for them. */
+/* One averaging step over the whole arena with this decay, behind everything that wrote the weights.  A decay that is negative,
+ * >= 1 or NaN: CN_ERR_BAD_ARG.                                                                                        [async] */
+int  cn_ctx_average_weights(cn_ctx *ctx, float decay);
+/* Exchanges the weights and their average.  Without an average, or while an armed update is pending (cn_ctx_arm_update /
+ * cn_ctx_arm_adam not yet completed by the *_update* call): CN_ERR_STATE.                                              [async] */
+int  cn_ctx_swap_weight_average(cn_ctx *ctx);
+/* *exists: an average has been formed or uploaded; *swapped: the weights and the average are exchanged right now.  Either pointer
+ * may be NULL. */
+int  cn_ctx_weight_average_state(const cn_ctx *ctx, int *exists, int *swapped);
+/* The layer's part of the average, flat reference layout like CN_BUF_WEIGHTS; before an average exists: the weights (what the
+ * first step will copy).  A layer without weights: CN_ERR_BAD_ARG; count != cn_layer_weight_count: CN_ERR_SHAPE.       [sync] */
+int  cn_layer_read_weight_average(cn_layer *layer, float *host, size_t count);
+/* Overwrites the layer's part of the average from the host (autosave / --continue).  Creates the average if there is none: it
+ * starts as a copy of ALL weights, then this layer's part is overwritten; the averaging step that follows does not copy.  Errors
+ * as for the read. */
+int  cn_layer_upload_weight_average(cn_layer *layer, const float *host, size_t count);
+
 /* ---- Adam (no counterpart in the reference, whose option table names steepest_descent and rprop only,
  *      Configuration.cpp:152,265) ---------------------------------------------------------------------------------
  * A second update rule beside UpdateWeightFn, with the same three entry points and the same protocol as the cn_sgd_* trio.

@@ -54,6 +54,9 @@ EXPORTS = [
     "cn_layer_set_residual", "cn_dbg_residual_branch",
     # include/currennt_hip.h, section Layer normalization, and its hook in include/currennt_hip_debug.h
     "cn_layer_set_layer_norm", "cn_dbg_layer_norm_input",
+    # include/currennt_hip.h, section Weight averaging
+    "cn_ctx_average_weights", "cn_ctx_swap_weight_average", "cn_ctx_weight_average_state", "cn_layer_read_weight_average",
+    "cn_layer_upload_weight_average",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -210,6 +213,11 @@ def load_library():
     L.cn_ctx_set_weight_noise.argtypes = [vp, cf, C.c_uint64, C.c_uint64]
     L.cn_dbg_noisy_weights.argtypes = [vp, vp, C.c_size_t]
     L.cn_ctx_set_input_augment.argtypes = [vp, C.POINTER(InputAugment)]
+    L.cn_ctx_average_weights.argtypes = [vp, cf]
+    L.cn_ctx_swap_weight_average.argtypes = [vp]
+    L.cn_ctx_weight_average_state.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    L.cn_layer_read_weight_average.argtypes = [vp, vp, C.c_size_t]
+    L.cn_layer_upload_weight_average.argtypes = [vp, vp, C.c_size_t]
     _LIB = L
     return L
 

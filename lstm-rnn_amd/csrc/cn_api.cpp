@@ -183,6 +183,12 @@ struct cn_ctx {
     int family = FAMILY_NONE;
     float *adam_v = nullptr;              // Adam's second moments, [total] like a part of the arena, zeroed; allocated at the first Adam call
 
+    // Weight averaging (include/currennt_hip.h, section Weight averaging): the average, [total] like a part of the arena, allocated
+    // by the first averaging step (which copies the weights) or the first upload (a copy of the weights, then the layer's part);
+    // avg_swapped: the weights part of the arena holds the average and `avg` the raw weights right now
+    float *avg = nullptr;
+    bool avg_swapped = false;
+
     // cn_ctx_set_grad_clip (include/currennt_hip.h, section Gradient clipping): the bound (0: off), the device record -- allocated
     // by the first non-zero bound -- and whether the record still holds the norm of what weightUpdates holds now (cleared by
     // everything that changes the gradient; the first update call behind that forms the norm again)
@@ -848,6 +854,14 @@ void require_loaded(cn_ctx *c)
     if (!c->loaded) throw cn_error(CN_ERR_STATE, "no fraction loaded (call cn_fraction_load first)");
 }
 
+// Weight averaging: while the weights and their average are exchanged, nothing may train on, update or overwrite what the weights
+// part of the arena holds (fn: the ABI function, for the message)
+void refuse_swapped(const cn_ctx *c, const char *fn)
+{
+    if (c->avg_swapped)
+        throw cn_error(CN_ERR_STATE, std::string(fn) + ": the weights and their average are swapped (cn_ctx_swap_weight_average); swap them back first");
+}
+
 // a deferred cn_loss_accumulate that did not find a backward launch to ride on: the one-workgroup reduction now
 void flush_loss(cn_ctx *c)
 {
@@ -1481,7 +1495,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart); hipFree(ctx->aug_tab); hipFree(ctx->pf.aug_tab);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -1673,6 +1687,7 @@ int cn_allreduce_grads(cn_ctx *ctx, cn_layer *const *layers, int n)
 {
     if (!ctx || n < 0 || (n > 0 && !layers)) { g_last_error = "cn_allreduce_grads: bad argument"; return CN_ERR_BAD_ARG; }
     return guarded([&] {
+        refuse_swapped(ctx, "cn_allreduce_grads");
         require_comm(ctx, "cn_allreduce_grads");
         enter(ctx);
         finalize(ctx);
@@ -2229,6 +2244,7 @@ int cn_layer_backward(cn_layer *layer)
     return guarded([&] {
         cn_ctx *c = layer->ctx;
         enter(c);
+        refuse_swapped(c, "cn_layer_backward");
         require_loaded(c);
         finalize(c);
         if (layer->trainable && layer->updated)
@@ -2412,6 +2428,7 @@ int cn_layer_set_weights(cn_layer *layer, const float *host, int count)
         cn_ctx *c = layer->ctx;
         enter(c);
         if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_set_weights: layer has no weights");
+        refuse_swapped(c, "cn_layer_set_weights");
         if (count != layer->nw)
             throw cn_error(CN_ERR_SHAPE, "Invalid number of weights: " + std::to_string(count) + " given, " + std::to_string(layer->nw) + " expected");
         if (!c->finalized) { layer->pending_w.assign(host, host + count); return; }
@@ -2429,6 +2446,7 @@ int cn_layer_upload(cn_layer *layer, cn_buffer which, const float *host, size_t 
         cn_ctx *c = layer->ctx;
         enter(c);
         if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload: layer has no weights");
+        refuse_swapped(c, "cn_layer_upload");
         if (which != CN_BUF_WEIGHT_UPDATES && which != CN_BUF_WEIGHT_DELTAS && which != CN_BUF_ADAM_SECOND_MOMENTS) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload: not a parameter vector");
         if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_layer_upload: count != weight count");
         finalize(c);
@@ -2569,6 +2587,102 @@ int cn_ctx_weights_touched(cn_ctx *ctx)
     return CN_OK;
 }
 
+// ---- weight averaging (include/currennt_hip.h, section Weight averaging) ----
+// the average's allocation (the caller fills it: the first step copies, the first upload copies and overwrites a part)
+static float *alloc_avg(cn_ctx *c)
+{
+    float *p = nullptr;
+    HIP_CHECK(hipMalloc((void **)&p, (c->total ? c->total : 4) * sizeof(float)));
+    return p;
+}
+
+int cn_ctx_average_weights(cn_ctx *ctx, float decay)
+{
+    if (!ctx) { g_last_error = "cn_ctx_average_weights: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        if (!(decay >= 0.f && decay < 1.f)) throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_average_weights: decay must lie in [0, 1)");
+        refuse_swapped(ctx, "cn_ctx_average_weights");
+        finalize(ctx);
+        join_side(ctx);                      // (the step only reads the weights, but an armed step's updates ran on the side streams)
+        const float omd = (float)(1.0 - (double)decay);
+        const bool first = !ctx->avg;
+        if (first) ctx->avg = alloc_avg(ctx);
+        Timed tm(ctx, KC_OTHER);
+        launch_weight_average(ctx->stream, ctx->avg, ctx->arena, ctx->total, omd, first || omd == 1.0f);
+    });
+}
+
+int cn_ctx_swap_weight_average(cn_ctx *ctx)
+{
+    if (!ctx) { g_last_error = "cn_ctx_swap_weight_average: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        if (!ctx->avg) throw cn_error(CN_ERR_STATE, "cn_ctx_swap_weight_average: there is no average yet (cn_ctx_average_weights / cn_layer_upload_weight_average)");
+        bool pending = ctx->armed || ctx->arm_deferred;
+        for (cn_layer *l : ctx->layers) pending = pending || l->updated || l->deferred;
+        if (pending) throw cn_error(CN_ERR_STATE, "cn_ctx_swap_weight_average: an armed update is pending (complete it with the *_update* call first)");
+        join_side(ctx);
+        // the swap WRITES the flat weights: behind the launches that still read them elsewhere -- the operand copies an update left
+        // on the side stream (one wait, for the last of them: same stream, in order), noisy sets generated ahead
+        bool packs = false;
+        for (cn_layer *l : ctx->layers) { packs = packs || l->pack_pending; l->pack_pending = false; }
+        if (packs && ctx->ev_pack_last) HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_pack_last, 0));
+        if (ctx->noise_wait) { HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_noise, 0)); ctx->noise_wait = false; }
+        {
+            Timed tm(ctx, KC_OTHER);
+            launch_weight_swap(ctx->stream, ctx->arena, ctx->avg, ctx->total);
+        }
+        ctx->avg_swapped = !ctx->avg_swapped;
+        // every copy of the old weights is stale: the next forward pass rebuilds them all, a noisy backward pass its sets
+        for (cn_layer *l : ctx->layers) if (l->trainable) { l->dirty = true; l->noisy_ready = false; }
+    });
+}
+
+int cn_ctx_weight_average_state(const cn_ctx *ctx, int *exists, int *swapped)
+{
+    if (!ctx) { g_last_error = "cn_ctx_weight_average_state: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    if (exists) *exists = ctx->avg ? 1 : 0;
+    if (swapped) *swapped = ctx->avg_swapped ? 1 : 0;
+    return CN_OK;
+}
+
+int cn_layer_read_weight_average(cn_layer *layer, float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_layer_read_weight_average: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read_weight_average: layer has no weights");
+        if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_layer_read_weight_average: count != weight count");
+        finalize(c);
+        join_side(c);
+        const float *src = c->avg ? c->avg + layer->woff : layer->w;       // before an average exists: what the first step will copy
+        HIP_CHECK(hipMemcpyAsync(host, src, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int cn_layer_upload_weight_average(cn_layer *layer, const float *host, size_t count)
+{
+    if (!layer || !host) { g_last_error = "cn_layer_upload_weight_average: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_upload_weight_average: layer has no weights");
+        refuse_swapped(c, "cn_layer_upload_weight_average");
+        if (count != (size_t)layer->nw) throw cn_error(CN_ERR_SHAPE, "cn_layer_upload_weight_average: count != weight count");
+        finalize(c);
+        join_side(c);
+        if (!c->avg) {                       // the average starts as a copy of all weights
+            c->avg = alloc_avg(c);
+            HIP_CHECK(hipMemcpyAsync(c->avg, c->arena, c->total * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_CHECK(hipMemcpyAsync(c->avg + layer->woff, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
 // ---- the optimizer's calls: momentum SGD and Adam share every sequence, the rule says which -------------------------
 static UpdateRule sgd_rule(float lr, float mom) { UpdateRule r; r.lr = lr; r.mom = mom; return r; }
 static UpdateRule adam_rule(float lr, float b1, float b2, float eps, int64_t step)
@@ -2580,6 +2694,7 @@ static UpdateRule adam_rule(float lr, float b1, float b2, float eps, int64_t ste
 // gradient work
 static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
 {
+    refuse_swapped(c, fn);
     if (r.adam) check_adam_args(fn, r);
     bind_family(c, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
     comm_check_fast(c);
@@ -2620,6 +2735,7 @@ static const ClipRecord *clip_record(cn_ctx *c)
 static void arm(cn_ctx *ctx, const UpdateRule &r, const char *fn)
 {
     enter(ctx);
+    refuse_swapped(ctx, fn);
     if (r.adam) check_adam_args(fn, r);
     for (cn_layer *l : ctx->layers)
         if (l->updated) throw cn_error(CN_ERR_STATE, std::string(fn) + ": the previous armed update has not been completed (" +
@@ -2696,6 +2812,7 @@ int cn_ctx_accumulate_updates(cn_ctx *ctx, int first)
     return guarded([&] {
         enter(ctx);
         finalize(ctx);
+        refuse_swapped(ctx, "cn_ctx_accumulate_updates");
         if (ctx->armed || ctx->arm_deferred) throw cn_error(CN_ERR_STATE, "cn_ctx_accumulate_updates: an armed per-fraction update is pending (batch learning sums first, cn_ctx_arm_update is not for it)");
         if (!first && !ctx->acc_valid) throw cn_error(CN_ERR_STATE, "cn_ctx_accumulate_updates: nothing accumulated yet (the first fraction of an epoch passes first != 0)");
         join_side(ctx);                     // the gradient GEMMs / unpack launches of the side streams write weightUpdates
@@ -2712,6 +2829,7 @@ int cn_ctx_take_accumulated(cn_ctx *ctx)
     return guarded([&] {
         enter(ctx);
         finalize(ctx);
+        refuse_swapped(ctx, "cn_ctx_take_accumulated");
         if (!ctx->acc_valid) throw cn_error(CN_ERR_STATE, "cn_ctx_take_accumulated: nothing accumulated (cn_ctx_accumulate_updates)");
         join_side(ctx);
         HIP_CHECK(hipMemcpyAsync(ctx->arena + ctx->total, ctx->acc, ctx->total * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));

@@ -439,6 +439,13 @@ void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, C
 void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done = nullptr);
 void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done = nullptr);
 
+// ---- weight averaging (include/currennt_hip.h, section Weight averaging; cn_average.hip) ----
+// avg[0 .. n) = copy ? w : avg + omd * (w - avg), every operation an fp32 operation rounded on its own (n a multiple of 4, both
+// pointers 16-byte aligned: the weights part of the arena and the context's average)
+void launch_weight_average(hipStream_t s, float *avg, const float *w, size_t n, float omd, bool copy);
+// w[0 .. n) <-> avg[0 .. n)
+void launch_weight_swap(hipStream_t s, float *w, float *avg, size_t n);
+
 // ---- CTC post output layer (cn_ctc.hip; the arithmetic is stated in that file's header) -----------------------------------------
 struct CtcArgs {
     const float *y; const char *pat;      // posteriors [T * PSp][Lp], pattern types [T * PSp]

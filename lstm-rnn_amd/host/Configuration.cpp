@@ -49,6 +49,9 @@ const char *Configuration::usage()
            "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
            "            --max_grad_norm X (clip every update's gradient to this global L2 norm; a step with a non-finite gradient is\n"
            "                      skipped; default 0 = off)\n"
+           "            --weight_average_decay D (keep an exponential moving average of the weights, one step behind every update;\n"
+           "                      validation, early stopping, trained_network.jsn and .best.jsn use it; 0 < D < 1, default 0 = off)\n"
+           "            --weight_average_warmup B (step k >= 2 averages with min(D, k / (k + 9)); default true)\n"
            "            --weight_noise_sigma X (Gaussian noise on the weights the backward pass reads; default 0 = off)\n"
            "            --weight_noise_on_device B (generate that noise on the device from --random_seed, the epoch and the fraction\n"
            "                      index: no host copies, the update stays overlapped, --continue resumes the same noise; default false)\n"
@@ -104,6 +107,12 @@ void Configuration::apply(const std::string &key, const std::string &v)
         if (!(m_maxGradNorm >= 0) || std::isinf(m_maxGradNorm))
             throw std::runtime_error("Error while parsing the command line and/or options file: --max_grad_norm must be finite and >= 0 (0 = off)");
     }
+    else if (key == "weight_average_decay") {
+        m_weightAverageDecay = (real_t)atof(v.c_str());
+        if (!(m_weightAverageDecay >= 0 && m_weightAverageDecay < 1))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --weight_average_decay must be in [0, 1) (0 = off)");
+    }
+    else if (key == "weight_average_warmup") m_weightAverageWarmup = toBool(key, v);
     else if (key == "save_network") m_trainedNetwork = v;
     else if (key == "train_file") m_trainingFiles = splitList(v);
     else if (key == "val_file") m_validationFiles = splitList(v);

@@ -42,6 +42,11 @@ public:
     // --max_grad_norm: bound on the global L2 norm of an update's gradient (include/currennt_hip.h, section Gradient clipping;
     // no counterpart in the reference); 0 = off
     real_t maxGradNorm() const { return m_maxGradNorm; }
+    // --weight_average_decay: decay of the exponential moving average of the weights that validation, early stopping and the saved
+    // networks use (include/currennt_hip.h, section Weight averaging; no counterpart in the reference); 0 = off.
+    // --weight_average_warmup: step k >= 2 uses min(decay, k / (k + 9))
+    real_t weightAverageDecay() const { return m_weightAverageDecay; }
+    bool weightAverageWarmup() const { return m_weightAverageWarmup; }
     real_t featurePeriod() const { return m_featurePeriod; }
     real_t trainingFraction() const { return m_trainingFraction; }
     real_t validationFraction() const { return m_validationFraction; }
@@ -118,6 +123,8 @@ private:
            m_testFraction = 1, m_weightsUniformMin = -0.1f, m_weightsUniformMax = 0.1f, m_weightsNormalSigma = 0.1f, m_weightsNormalMean = 0;
     real_t m_adamBeta1 = 0.9f, m_adamBeta2 = 0.999f, m_adamEpsilon = 1e-8f;
     real_t m_maxGradNorm = 0;
+    real_t m_weightAverageDecay = 0;
+    bool m_weightAverageWarmup = true;
     std::string m_optimizer = "steepest_descent";
     feedforwardformat_type_t m_feedForwardFormat = FORMAT_SINGLE_CSV;
     std::string m_networkFile = "network.jsn", m_trainedNetwork = "trained_network.jsn", m_feedForwardOutputFile = "ff_output.csv";

@@ -384,7 +384,10 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             }
             if (config.maxGradNorm() > 0) printf("Max. gradient norm:        %g\n\n", (double)config.maxGradNorm());
             if (config.weightNoiseOnDevice()) printf("Weight noise:              sigma %g, generated on the device\n\n", (double)config.weightNoiseSigma());
+            if (config.weightAverageDecay() > 0)
+                printf("Weight averaging:          decay %g, warm-up %s\n\n", (double)config.weightAverageDecay(), config.weightAverageWarmup() ? "on" : "off");
             optimizer.setMaxGradNorm(config.maxGradNorm());
+            optimizer.setWeightAverage(config.weightAverageDecay(), config.weightAverageWarmup());
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
             // --weight_noise_on_device: seed = --random_seed on every rank (no rank offset: the replicas stay identical)
             optimizer.setWeightNoiseOnDevice(config.weightNoiseOnDevice(), (uint64_t)config.randomSeed());
@@ -400,6 +403,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 fflush(stdout);
                 restoreState(netDoc, &optimizer, &infoRows);
                 printf("done.\n\n");
+                if (optimizer.weightAverageStartsFresh())
+                    printf("Weight averaging: the autosave file holds no average; it starts with the next update.\n\n");
             }
 
             printf("Starting training...\n\n");
@@ -439,7 +444,12 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                             size_t pos = config.networkFile().find_last_of('.');
                             base = (pos != std::string::npos && pos > 0) ? config.networkFile().substr(0, pos) : config.networkFile();
                         }
-                        if (root) saveNetwork(neuralNetwork, base + ".best.jsn");
+                        if (root) {
+                            // --weight_average_decay: the epoch was scored on the average, so the average is what is saved
+                            const bool swapped = optimizer.swapWeightAverage();
+                            saveNetwork(neuralNetwork, base + ".best.jsn");
+                            if (swapped) optimizer.swapWeightAverage();
+                        }
                     }
                 } else infoRows += printfRow("        \n");
                 // --max_grad_norm: one line behind the epoch's row (not part of the table, nor of the rows an autosave keeps)

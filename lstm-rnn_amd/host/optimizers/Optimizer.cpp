@@ -1,5 +1,6 @@
 #include "Optimizer.hpp"
 
+#include <algorithm>
 #include <limits>
 #include <vector>
 
@@ -164,7 +165,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
                 }
             }
             if (m_hybridOnlineBatch) {
-                _updateWeights();                                           // Optimizer.cu:88-89
+                _completeUpdate();                                          // Optimizer.cu:88-89
             } else {
                 // batch learning: sum the fractions' weightUpdates, one update per epoch (:72-85, :95-97) -- on the device,
                 // one launch over all layers, like the reference's thrust::copy / thrust::transform(plus)
@@ -175,7 +176,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         have = haveNext;
         if (have) std::swap(frac, next);
     }
-    if (calcWeightUpdates && !m_hybridOnlineBatch) _updateWeights();
+    if (calcWeightUpdates && !m_hybridOnlineBatch) _completeUpdate();
     {
         float e = 0; int64_t correct = 0;
         // data-parallel: the sums of all ranks (every rank then computes the same epoch errors and takes the same
@@ -200,13 +201,39 @@ bool Optimizer::train()
     if (m_finished) return true;
     ++m_curEpoch;
     m_curTrainingError = _processDataSet(m_trainingSet, true, &m_curTrainingClassError);
+    // weight averaging: the evaluation passes and the best weights kept (_storeWeights, an empty validation set included) see the
+    // average; the raw weights are back before the stop decision, whose _restoreWeights() writes them
+    const bool swapped = swapWeightAverage();
     _scoreValidationSet();
     if (_dueThisEpoch(m_testSet, m_testEvery)) m_curTestError = _processDataSet(m_testSet, false, &m_curTestClassError);
+    if (swapped) swapWeightAverage();
     if (_shouldStop()) {
         _restoreWeights();          // training ends on the best weights seen, not on the last ones
         m_finished = true;
     }
     return m_finished;
+}
+
+// the update of the optimizer at hand, then the averaging step it completes (hybrid online/batch and batch learning, host or
+// device noise: every path to an update comes through here)
+void Optimizer::_completeUpdate()
+{
+    _updateWeights();
+    if (!(m_avgDecay > 0)) return;
+    const int64_t k = ++m_avgSteps;
+    double decay = (double)m_avgDecay;
+    if (m_avgWarmup && k >= 2) decay = std::min(decay, (double)k / ((double)k + 9.0));
+    hipCheck(cn_ctx_average_weights(m_neuralNetwork.context(), (float)decay), m_neuralNetwork.context());
+}
+
+bool Optimizer::swapWeightAverage()
+{
+    if (!(m_avgDecay > 0)) return false;
+    int exists = 0;
+    hipCheck(cn_ctx_weight_average_state(m_neuralNetwork.context(), &exists, nullptr), m_neuralNetwork.context());
+    if (!exists) return false;          // (no update yet: nothing to exchange)
+    hipCheck(cn_ctx_swap_weight_average(m_neuralNetwork.context()), m_neuralNetwork.context());
+    return true;
 }
 
 bool Optimizer::_dueThisEpoch(const data_sets::DataSet &set, int every) const
@@ -302,6 +329,19 @@ void Optimizer::exportState(json::Value *jsonDoc) const
     for (const IntField &f : StateTable::ints()) jsonDoc->addMember(f.key, json::Value(this->*f.member));
     for (const RealField &f : StateTable::reals()) jsonDoc->addMember(f.key, json::Value((double)(this->*f.member)));
     _exportWeights(jsonDoc, "optimizer_best_weights", m_bestWeights);
+    // weight averaging: the average (laid out like optimizer_best_weights) and the number of averaging steps taken
+    if (m_avgDecay > 0) {
+        const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
+        std::vector<Hip::real_vector> avg(ls.size());
+        for (size_t i = 1; i + 1 < ls.size(); ++i) {
+            layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+            if (!layer) continue;
+            avg[i].resize(layer->weightCount());
+            hipCheck(cn_layer_read_weight_average(layer->handle(), avg[i].data(), avg[i].size()), m_neuralNetwork.context());
+        }
+        _exportWeights(jsonDoc, "weight_average", avg);
+        jsonDoc->addMember("weight_average_steps", json::Value((double)m_avgSteps));
+    }
 }
 void Optimizer::importState(const json::Value &jsonDoc)
 {
@@ -309,6 +349,27 @@ void Optimizer::importState(const json::Value &jsonDoc)
     for (const IntField &f : StateTable::ints()) this->*f.member = jsonDoc[f.key].getInt();
     for (const RealField &f : StateTable::reals()) this->*f.member = (real_t)jsonDoc[f.key].getDouble();
     _importWeights(jsonDoc, "optimizer_best_weights", &m_bestWeights);
+    // weight averaging off: an average in the file is ignored.  On, and the file has none (it was written without averaging): the
+    // average starts fresh at the next update
+    if (!(m_avgDecay > 0)) return;
+    if (!jsonDoc.hasMember("weight_average")) {
+        m_avgStartsFresh = true;
+        m_avgSteps = 0;
+        return;
+    }
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
+    std::vector<Hip::real_vector> avg(ls.size());
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (layer) avg[i].resize(layer->weightCount());
+    }
+    _importWeights(jsonDoc, "weight_average", &avg);
+    m_avgSteps = jsonDoc.hasMember("weight_average_steps") ? (int64_t)jsonDoc["weight_average_steps"].getDouble() : 0;
+    if (m_avgSteps < 1) return;         // (written before the first update: the first step copies, as it would have)
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (layer) hipCheck(cn_layer_upload_weight_average(layer->handle(), avg[i].data(), avg[i].size()), m_neuralNetwork.context());
+    }
 }
 
 // the momentum state lives on the device (CN_BUF_WEIGHT_DELTAS); autosave moves it through the host

@@ -41,6 +41,17 @@ public:
     void setMaxGradNorm(real_t maxNorm);
     struct ClipStats { float maxNormSeen; long long updates, clipped, skipped; };
     ClipStats takeClipStats();
+    // --weight_average_decay / --weight_average_warmup (include/currennt_hip.h, section Weight averaging): one averaging step behind
+    // every completed update, whichever optimizer and learning mode; step k (from 1, kept here: the library keeps no clock, and it
+    // travels with the autosave) uses `decay`, with warm-up min(decay, k / (k + 9)) for k >= 2.  Between an epoch's training pass
+    // and its stop decision the weights and the average are exchanged: the validation and test errors, early stopping and the
+    // best weights kept -- and so trained_network.jsn -- are the average's.  decay 0 = off.
+    void setWeightAverage(real_t decay, bool warmup) { m_avgDecay = decay; m_avgWarmup = warmup; }
+    // Exchanges the weights and the average if averaging is on and an average exists (returns whether it did): the driver saves
+    // the .best.jsn network between two calls
+    bool swapWeightAverage();
+    // importState found no average in the autosave file although averaging is on (it was written without): it starts fresh
+    bool weightAverageStartsFresh() const { return m_avgStartsFresh; }
     // autosave / --continue (Optimizer.cu:326-358)
     virtual void exportState(json::Value *jsonDoc) const;
     virtual void importState(const json::Value &jsonDoc);
@@ -91,6 +102,10 @@ private:
     uint64_t m_dropoutSeed = 0;
     cn_input_augment m_inputAugment{};
     bool m_inputAugmentOn = false;
+    real_t m_avgDecay = 0;
+    bool m_avgWarmup = true, m_avgStartsFresh = false;
+    int64_t m_avgSteps = 0;             // averaging steps taken so far
+    void _completeUpdate();             // _updateWeights(), then the averaging step
 protected:
     static void _exportWeights(json::Value *jsonDoc, const char *arrayName, const std::vector<Hip::real_vector> &weights);   // :106-123
     static void _importWeights(const json::Value &jsonDoc, const char *arrayName, std::vector<Hip::real_vector> *weights);   // :125-149

@@ -127,6 +127,19 @@ class Layer:
         B.check(self.net.lib.cn_layer_upload(self.handle, B.BUF[which], flat.ctypes.data_as(C.c_void_p), flat.size),
                 self.net.ctx)
 
+    def weight_average(self):
+        """cn_layer_read_weight_average: this layer's part of the context's weight average (include/currennt_hip.h, section Weight
+        averaging); before an average exists: the weights.  While swapped it holds the raw weights."""
+        out = np.empty(self.weight_count, np.float32)
+        B.check(self.net.lib.cn_layer_read_weight_average(self.handle, out.ctypes.data_as(C.c_void_p), out.size), self.net.ctx)
+        return out
+
+    def upload_weight_average(self, array):
+        """cn_layer_upload_weight_average: overwrite this layer's part of the average from the host (autosave); creates the average
+        as a copy of all weights if there is none."""
+        flat = np.ascontiguousarray(array, np.float32).reshape(-1)
+        B.check(self.net.lib.cn_layer_upload_weight_average(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size), self.net.ctx)
+
     def set_dropout(self, rate):
         """cn_layer_set_dropout: the rate of the dropout on this layer's input (0: none)."""
         B.check(self.net.lib.cn_layer_set_dropout(self.handle, float(rate)), self.net.ctx)
@@ -537,6 +550,23 @@ class NeuralNetwork:
         """cn_ctx_arm_adam: the coming backward pass applies each layer's Adam step as soon as that layer's gradient is complete;
         follow the backward pass with update_weights_adam(same values), which completes the step."""
         B.check(self.lib.cn_ctx_arm_adam(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+
+    def average_weights(self, decay):
+        """cn_ctx_average_weights: one step avg += (1 - decay) * (w - avg) over all weights, behind the update that precedes it
+        (include/currennt_hip.h, section Weight averaging); the context's first step copies.  The library keeps no clock: a
+        training loop hands the decay of each step."""
+        B.check(self.lib.cn_ctx_average_weights(self.ctx, float(decay)), self.ctx)
+
+    def swap_weight_average(self):
+        """cn_ctx_swap_weight_average: exchange the weights and their average; the forward passes that follow read the average
+        until the next call swaps them back.  Nothing may train or update in between."""
+        B.check(self.lib.cn_ctx_swap_weight_average(self.ctx), self.ctx)
+
+    def weight_average_state(self):
+        """cn_ctx_weight_average_state: (exists, swapped)."""
+        e, s = C.c_int(), C.c_int()
+        B.check(self.lib.cn_ctx_weight_average_state(self.ctx, C.byref(e), C.byref(s)), self.ctx)
+        return bool(e.value), bool(s.value)
 
     def set_dropout_pass(self, enable, seed=0, pass_=0):
         """cn_ctx_set_dropout_pass: whether the forward passes that follow drop (on the layers with a "dropout" rate), and the
