@@ -604,6 +604,53 @@ typedef struct cn_input_augment {
  * augmentation off again leaves them unused until the context is destroyed.                                      [async] */
 int  cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a);
 
+/* ---- Input splicing and frame skipping (--input_left_context / --input_right_context, DataSet.cpp:346-366: spliced there on the
+ *      host; the frame skip, "low frame rate" input, has no counterpart in the reference) ------------------------------------------
+ * With the setting on, every cn_fraction_load, cn_fraction_load_resident, cn_fraction_prefetch and cn_fraction_prefetch_resident
+ * that follows takes its cn_fraction at SOURCE rate, unspliced, and the library derives the network-rate fraction on the device,
+ * where it re-lays the fraction out: the upload carries every frame once, and every layer runs on every K-th frame only.
+ *
+ * Let L, R, K be the three members, B = L + R + 1, P the input layer's size and P0 = P / B.  The source fraction:
+ *      max_seq_length = Tsrc, min_seq_length = Tmin_src; pat_types, target_classes and targets have Tsrc * PS rows; inputs is
+ *      [Tsrc * PS][P0]; input_pattern_size = P0.
+ * P % B != 0, input_pattern_size != P0 and ceil(Tsrc / K) above the layers' max_seq_length each fail the load with CN_ERR_SHAPE.
+ *
+ * The network-rate fraction, which is all that every later layer sees:
+ *      len_s = frames of slot s whose pattern type is not NONE (a sequence lies in its slot from t = 0 without holes)
+ *      n_s = ceil(len_s / K)        T' = ceil(Tsrc / K)        Tmin' = ceil(Tmin_src / K)
+ * Network frame (j, s) with j < n_s:
+ *      pattern type   FIRST for j = 0, LAST for j = n_s - 1 > 0, NORMAL otherwise: those of a sequence of n_s frames
+ *      input column c block b = c / P0, feature f = c % P0, source frame ts = clamp(K*j + b - L, 0, len_s - 1):
+ *                     inputs[(ts*PS + s)*P0 + f], rounded ONCE to the operand type
+ *      target class and target row: those of source row K*j, the frame the context is centred on.  (A lag of the targets is the
+ *                     caller's, applied at source rate before the load.)
+ * j >= n_s, pad slots and pad columns: NONE, zeros, class -1, zero targets, as without the setting.  The row map is built from
+ * the derived pattern types, with Tmin' time steps of unchecked rows.  The current fraction has T' and Tmin' steps: cn_layer_read
+ * of any layer returns T' * PS rows.  A CTC layer is unaffected: cn_layer_set_label_sequences brings the labels, and
+ * num_sequences is the caller's.  With K = 1 this is bit for bit what a load of the host-spliced fraction leaves.
+ *
+ * Together with cn_ctx_set_input_augment: the augmentation's context_left / context_right must equal L and R, otherwise the load
+ * fails with CN_ERR_SHAPE.  Noise and masks stay the functions of the source element (s, ts, f) stated there, with ts as above;
+ * len_s and the time masks count source frames.  With K = 1 the result is bit for bit that of a host-spliced load with the same
+ * augmentation; with K > 1 it is the augmentation of the source fraction, then the gather.
+ *
+ * cn_fraction_prefetch* records the setting in force at the prefetch; the load that follows is a hit only if the setting in force
+ * at the load equals it member by member.  With option overlap = 0 a host fraction is packed and uploaded like the staged route and
+ * re-laid out by the same kernel; the call then waits for it.  The staging areas are sized by what a fraction needs under the
+ * setting in force when they are allocated: a later setting whose fractions need more (a larger K, wider patterns) makes the next
+ * host load or prefetch reallocate them, which synchronises the device once.
+ *
+ * The augmentation's rule needs the source frames.  A caller that skips frames on the host (a network-rate fraction, setting off)
+ * and names a context to cn_ctx_set_input_augment gets the rule applied to the rows it loaded, as if they were consecutive frames:
+ * with a skip above 1 augment through this setting instead.
+ *
+ * {0, 0, 1} is ON: the identity gather, which leaves what the plain load leaves.  With s == NULL, or without the call, the library
+ * launches exactly what it launches today. */
+typedef struct cn_input_splice { int context_left, context_right, frame_skip; } cn_input_splice;
+/* NULL = off, and a fresh context is off.  CN_ERR_BAD_ARG: a negative context, a context above 32 per side, frame_skip outside
+ * 1..16.  The first spliced load allocates the per-slot length table if the augmentation has not.                  [async] */
+int  cn_ctx_set_input_splice(cn_ctx *ctx, const cn_input_splice *s);
+
 /* ---- Residual connections (no counterpart in the reference; He et al. 2016, and Kim et al. 2017 for stacked LSTMs) ----------------
  * A hidden layer l of kind lstm, blstm or feedforward_{tanh,logistic,identity} whose preceding layer has the same `size` may be
  * marked residual; the preceding layer may be of any kind, the input layer included.  Write b for what l computes without the

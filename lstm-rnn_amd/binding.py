@@ -50,6 +50,8 @@ EXPORTS = [
     "cn_ctx_set_weight_noise", "cn_dbg_noisy_weights",
     # include/currennt_hip.h, section Input augmentation
     "cn_ctx_set_input_augment",
+    # include/currennt_hip.h, section Input splicing and frame skipping
+    "cn_ctx_set_input_splice",
     # include/currennt_hip.h, section Residual connections, and its hook in include/currennt_hip_debug.h
     "cn_layer_set_residual", "cn_dbg_residual_branch",
     # include/currennt_hip.h, section Layer normalization, and its hook in include/currennt_hip_debug.h
@@ -82,6 +84,11 @@ class InputAugment(C.Structure):
     _fields_ = [("noise_sigma", C.c_float), ("context_left", C.c_int), ("context_right", C.c_int),
                 ("freq_masks", C.c_int), ("freq_width", C.c_int), ("time_masks", C.c_int), ("time_width", C.c_int),
                 ("time_max_permille", C.c_int), ("seed", C.c_uint64), ("pass_", C.c_uint64)]
+
+
+class InputSplice(C.Structure):
+    """cn_input_splice (include/currennt_hip.h, section Input splicing and frame skipping)"""
+    _fields_ = [("context_left", C.c_int), ("context_right", C.c_int), ("frame_skip", C.c_int)]
 
 
 # include/currennt_hip_debug.h: cn_dbg_tn_item, cn_dbg_fold_item (every pointer a c_void_p: an int would be cut to 32 bits)
@@ -213,6 +220,7 @@ def load_library():
     L.cn_ctx_set_weight_noise.argtypes = [vp, cf, C.c_uint64, C.c_uint64]
     L.cn_dbg_noisy_weights.argtypes = [vp, vp, C.c_size_t]
     L.cn_ctx_set_input_augment.argtypes = [vp, C.POINTER(InputAugment)]
+    L.cn_ctx_set_input_splice.argtypes = [vp, C.POINTER(InputSplice)]
     L.cn_ctx_average_weights.argtypes = [vp, cf]
     L.cn_ctx_swap_weight_average.argtypes = [vp]
     L.cn_ctx_weight_average_state.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]

@@ -154,6 +154,7 @@ struct cn_ctx {
         char *pat = nullptr, *pat_raw = nullptr; int *tcls = nullptr; void *in_op = nullptr; float *targets = nullptr;   // alternates
         bool allocated = false;
         cn_input_augment aug{};                                  // the augmentation in force at the prefetch (all zero: off)
+        cn_input_splice splice{};                                // ... and the splice settings (all zero: off)
         int *aug_tab = nullptr;                                  // its slot table: this re-layout runs on the side stream
     } pf;
 
@@ -162,6 +163,9 @@ struct cn_ctx {
     // ([PS][AUG_TAB_STRIDE] ints, allocated by the first enabling call that knows PS)
     cn_input_augment aug{};
     int *aug_tab = nullptr;
+    // cn_ctx_set_input_splice (section Input splicing and frame skipping): all zero when off (frame_skip >= 1: on), so that two
+    // settings compare member by member.  A spliced load forms its slot lengths in the same table (aug_tab).
+    cn_input_splice splice{};
 
     // data-parallel training: RCCL communicator of this rank, its stream and the newest reduction's event
     ncclComm_t comm = nullptr;
@@ -571,9 +575,26 @@ bool same_augment(const cn_input_augment &a, const cn_input_augment &b)
            a.freq_masks == b.freq_masks && a.freq_width == b.freq_width && a.time_masks == b.time_masks && a.time_width == b.time_width &&
            a.time_max_permille == b.time_max_permille && a.seed == b.seed && a.pass == b.pass;
 }
-void check_augment_shape(const cn_input_augment &a, const cn_layer *input)
+bool splice_enabled(const cn_input_splice &s) { return s.frame_skip >= 1; }
+bool same_splice(const cn_input_splice &a, const cn_input_splice &b)
+{
+    return a.context_left == b.context_left && a.context_right == b.context_right && a.frame_skip == b.frame_skip;
+}
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// the fraction every layer behind the re-layout sees: `f` itself, or with splicing on the network-rate lengths of the source-rate `f`
+cn_fraction network_rate(const cn_input_splice &s, const cn_fraction &f)
+{
+    cn_fraction n = f;
+    if (splice_enabled(s)) { n.max_seq_length = ceil_div(f.max_seq_length, s.frame_skip); n.min_seq_length = ceil_div(f.min_seq_length, s.frame_skip); }
+    return n;
+}
+void check_augment_shape(const cn_input_augment &a, const cn_input_splice &sp, const cn_layer *input)
 {
     if (!aug_enabled(a)) return;
+    if (splice_enabled(sp) && (a.context_left != sp.context_left || a.context_right != sp.context_right))
+        throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: the input augmentation's context of (" + std::to_string(a.context_left) + ", " +
+                       std::to_string(a.context_right) + ") differs from the input splicing's (" + std::to_string(sp.context_left) + ", " +
+                       std::to_string(sp.context_right) + ")");
     const long B = (long)a.context_left + a.context_right + 1;
     if (input->size % B != 0)
         throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: input layer size of " + std::to_string(input->size) + " is no multiple of the " +
@@ -587,17 +608,38 @@ AugArgs aug_args(const cn_input_augment &a, const cn_layer *input)
     g.k0 = (uint32_t)a.seed; g.k1_noise = (uint32_t)(a.seed >> 32) ^ 0x696E7074u; g.k1_mask = (uint32_t)(a.seed >> 32) ^ 0x6D61736Bu;
     g.pass_lo = (uint32_t)a.pass; g.pass_hi = (uint32_t)(a.pass >> 32);
     g.sigma = a.noise_sigma;
+    g.skip = 1;
+    return g;
+}
+// ... of a spliced load: the augmentation's settings when it is on (its context equals the splice's: check_augment_shape), the
+// geometry of the gather either way
+AugArgs splice_args(const cn_input_splice &sp, const cn_input_augment &a, const cn_layer *input)
+{
+    AugArgs g{};
+    if (aug_enabled(a)) g = aug_args(a, input);
+    g.P0 = input->size / (sp.context_left + sp.context_right + 1); g.ctx_left = sp.context_left; g.skip = sp.frame_skip;
     return g;
 }
 void ensure_aug_table(cn_ctx *c, int *&tab)
 {
     if (!tab && c->PS > 0) HIP_CHECK(hipMalloc((void **)&tab, (size_t)c->PS * AUG_TAB_STRIDE * sizeof(int)));
 }
+// ... gathered from a source-rate fraction when `sp` is on (section Input splicing and frame skipping): the same table first
 void relayout(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b,
-              const cn_input_augment &aug, int *&aug_tab)
+              const cn_input_augment &aug, const cn_input_splice &sp, int *&aug_tab)
 {
     const bool cls = is_class_post(post);
-    if (aug_enabled(aug)) {
+    const int Tnet = network_rate(sp, f).max_seq_length;
+    if (splice_enabled(sp)) {
+        ensure_aug_table(c, aug_tab);
+        const AugArgs g = splice_args(sp, aug, input);
+        launch_augment_table(st, g, f.pat_types, c->PS, f.max_seq_length, c->PS, aug_tab);
+        launch_fraction_load_splice(st, c->f32, g, aug_enabled(aug), aug_tab, Tnet, c->PS, c->PSp, b.pat,
+                                    cls ? f.target_classes : nullptr, b.tcls,
+                                    (post && !cls) ? f.targets : nullptr, post ? b.targets : nullptr,
+                                    post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN,
+                                    network_rate(sp, f).min_seq_length);
+    } else if (aug_enabled(aug)) {
         ensure_aug_table(c, aug_tab);
         const AugArgs g = aug_args(aug, input);
         launch_augment_table(st, g, f.pat_types, c->PS, f.max_seq_length, c->PS, aug_tab);
@@ -612,14 +654,14 @@ void relayout(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const 
                              post ? post->size : 0, f.inputs, input->size, b.in_op, input->Lp, c->rowmap_of(b.pat_raw), (int)c->pat_maxN, f.min_seq_length);
     }
     if (post && post->kind == CN_LAYER_BINARY_CLASSIFICATION)
-        launch_classes_to_targets(st, b.tcls, b.targets, f.max_seq_length * c->PSp);
+        launch_classes_to_targets(st, b.tcls, b.targets, Tnet * c->PSp);
 }
 // ... out of staging area `slot`: behind its upload (copy stream); the area is free again when the re-layout has read it
 void relayout_staged(hipStream_t st, cn_ctx *c, cn_layer *input, cn_layer *post, const cn_fraction &f, const FractionBuffers &b, int slot,
-                     const cn_input_augment &aug, int *&aug_tab)
+                     const cn_input_augment &aug, const cn_input_splice &sp, int *&aug_tab)
 {
     HIP_CHECK(hipStreamWaitEvent(st, c->ev_up[slot], 0));
-    relayout(st, c, input, post, f, b, aug, aug_tab);
+    relayout(st, c, input, post, f, b, aug, sp, aug_tab);
     HIP_CHECK(hipEventRecord(c->ev_free[slot], st));
     c->stage_used[slot] = true;
 }
@@ -628,8 +670,8 @@ void launch_prefetch(cn_ctx *c, hipStream_t st)
 {
     cn_ctx::Prefetch &p = c->pf;
     const FractionBuffers alt{p.pat, p.pat_raw, p.tcls, p.in_op, p.targets};
-    if (p.host) relayout_staged(st, c, p.input, p.post, p.f, alt, p.slot, p.aug, p.aug_tab);     // (f points into the staging area)
-    else relayout(st, c, p.input, p.post, p.f, alt, p.aug, p.aug_tab);
+    if (p.host) relayout_staged(st, c, p.input, p.post, p.f, alt, p.slot, p.aug, p.splice, p.aug_tab);     // (f points into the staging area)
+    else relayout(st, c, p.input, p.post, p.f, alt, p.aug, p.splice, p.aug_tab);
     p.launched = true;
 }
 void ensure_fork_events(cn_layer *l)
@@ -1944,7 +1986,16 @@ int cn_layer_weight_count(const cn_layer *layer) { return layer ? layer->nw : CN
 static void check_fraction(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, const cn_fraction *f)
 {
     if (input->kind != CN_LAYER_INPUT) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: `input` is not an input layer");
-    if (f->input_pattern_size != input->size)                                                     // InputLayer.cpp:52-55
+    const cn_input_splice &sp = ctx->splice;
+    if (splice_enabled(sp)) {      // a source-rate fraction of unspliced patterns (section Input splicing and frame skipping)
+        const int B = sp.context_left + sp.context_right + 1;
+        if (input->size % B != 0)
+            throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: input layer size of " + std::to_string(input->size) + " is no multiple of the " +
+                           std::to_string(B) + " frames of the input splicing's context");
+        if (f->input_pattern_size != input->size / B)
+            throw cn_error(CN_ERR_SHAPE, "Input layer size of " + std::to_string(input->size) + " / " + std::to_string(B) + " spliced frames = " +
+                           std::to_string(input->size / B) + " != data input pattern size of " + std::to_string(f->input_pattern_size));
+    } else if (f->input_pattern_size != input->size)                                              // InputLayer.cpp:52-55
         throw cn_error(CN_ERR_SHAPE, "Input layer size of " + std::to_string(input->size) +
                        " != data input pattern size of " + std::to_string(f->input_pattern_size));
     if (post_output) {
@@ -1954,7 +2005,10 @@ static void check_fraction(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
                            " != data target pattern size of " + std::to_string(f->output_pattern_size));
     }
     const int T = f->max_seq_length;
-    if (T <= 0 || T > ctx->maxT) throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: max_seq_length " + std::to_string(T) +
+    if (T > 0 && splice_enabled(sp) && ceil_div(T, sp.frame_skip) > ctx->maxT)
+        throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: max_seq_length " + std::to_string(T) + " at a frame skip of " + std::to_string(sp.frame_skip) +
+                       " gives " + std::to_string(ceil_div(T, sp.frame_skip)) + " steps, outside (0, " + std::to_string(ctx->maxT) + "]");
+    if (T <= 0 || (!splice_enabled(sp) && T > ctx->maxT)) throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: max_seq_length " + std::to_string(T) +
                                                 " outside (0, " + std::to_string(ctx->maxT) + "]");
     if (f->min_seq_length < 0 || f->min_seq_length > T) throw cn_error(CN_ERR_SHAPE, "cn_fraction_load: bad min_seq_length");
     if (!f->pat_types || !f->inputs) throw cn_error(CN_ERR_BAD_ARG, "cn_fraction_load: pat_types / inputs missing");
@@ -1979,7 +2033,7 @@ static Staged stage_upload(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
     const size_t b_pat = (rows + 15) & ~(size_t)15;
     const size_t b_tgt = !post_output ? 0 : (cls ? rows * sizeof(int) : rows * W * sizeof(float));
     const size_t b_tgt_al = (b_tgt + 15) & ~(size_t)15;
-    const size_t b_in = rows * (size_t)input->size * sizeof(float);
+    const size_t b_in = rows * (size_t)f->input_pattern_size * sizeof(float);      // (the input layer's size, or P0 of a spliced load: check_fraction)
     const size_t need = b_pat + b_tgt_al + b_in;
     if (need > ctx->stage_bytes || !ctx->h_stage[0]) {
         HIP_CHECK(hipDeviceSynchronize());
@@ -1988,8 +2042,10 @@ static Staged stage_upload(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, 
             if (ctx->d_stage[i]) HIP_CHECK(hipFree(ctx->d_stage[i]));
             ctx->stage_used[i] = false;
         }
-        const size_t maxrows = (size_t)ctx->maxT * PS;
-        size_t cap = ((maxrows + 15) & ~(size_t)15) + ((maxrows * std::max(W * sizeof(float), sizeof(int)) + 15) & ~(size_t)15) + maxrows * (size_t)input->size * sizeof(float);
+        // (the longest fraction the layers take: maxT steps, at source rate frame_skip times as many of the narrower patterns --
+        // under the splice setting in force now: a later setting that needs more comes back here, at the price of this synchronise)
+        const size_t maxrows = (size_t)ctx->maxT * PS * (splice_enabled(ctx->splice) ? (size_t)ctx->splice.frame_skip : 1);
+        size_t cap = ((maxrows + 15) & ~(size_t)15) + ((maxrows * std::max(W * sizeof(float), sizeof(int)) + 15) & ~(size_t)15) + maxrows * (size_t)f->input_pattern_size * sizeof(float);
         if (cap < need) cap = need;
         for (int i = 0; i < 2; ++i) {
             HIP_CHECK(hipHostMalloc((void **)&ctx->h_stage[i], cap, hipHostMallocDefault));
@@ -2055,26 +2111,30 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
         flush_loss(ctx);                     // (a deferred loss sum counts the rows of the fraction that is being replaced)
         Timed tm(ctx, KC_OTHER);
         require_targets("cn_fraction_load", post_output, f);
-        check_augment_shape(ctx->aug, input);
+        check_augment_shape(ctx->aug, ctx->splice, input);
+        const bool spliced = splice_enabled(ctx->splice);
         cn_ctx::Prefetch &pf = ctx->pf;
         // a prefetch of the same kind (resident / host buffers) announced exactly this fraction and the side stream has re-laid it
         // out (join_side above ordered this stream behind it): nothing is copied or launched here
         const bool hit = pf.valid && pf.launched && pf.host == !resident && pf.input == input && pf.post == post_output &&
-                         same_fraction(pf.host ? pf.f_host : pf.f, *f) && same_augment(pf.aug, ctx->aug);
+                         same_fraction(pf.host ? pf.f_host : pf.f, *f) && same_augment(pf.aug, ctx->aug) &&
+                         same_splice(pf.splice, ctx->splice);
         pf.valid = false;          // a prefetch serves the very next load or nothing
         const FractionBuffers cur{ctx->d_pat, ctx->d_pat_raw, ctx->d_tcls, input->out_op, post_output ? post_output->targets : nullptr};
         if (hit) {
             ++pf.hits;
             swap_in_prefetched(ctx, input, post_output);
         } else if (resident) {      // everything is in HBM already: one kernel re-lays it out
-            relayout(ctx->stream, ctx, input, post_output, *f, cur, ctx->aug, ctx->aug_tab);
-        } else if (ctx->overlap) {
+            relayout(ctx->stream, ctx, input, post_output, *f, cur, ctx->aug, ctx->splice, ctx->aug_tab);
+        } else if (ctx->overlap || spliced) {
             // Host buffers: pack [patTypes | classes or targets | inputs] into pinned memory, ONE contiguous upload
             // on the copy stream (it runs while the previous fraction still computes: the staging areas alternate),
             // then the same re-layout kernel as the resident path.  (Strided 2-D copies from pageable memory cost
             // one transfer per time step: 3.5 ms per fraction of 2.3 MB, twice the whole training step.)
             const Staged sg = stage_upload(ctx, input, post_output, f);
-            relayout_staged(ctx->stream, ctx, input, post_output, sg.f, cur, sg.slot, ctx->aug, ctx->aug_tab);
+            relayout_staged(ctx->stream, ctx, input, post_output, sg.f, cur, sg.slot, ctx->aug, ctx->splice, ctx->aug_tab);
+            // (option overlap = 0 with splicing on: the same route and the same kernel, then the wait its strided copies end with)
+            if (!ctx->overlap) HIP_CHECK(hipStreamSynchronize(ctx->stream));
         } else {
             // CN_NO_OVERLAP: strided copies [T][PS] -> [T][PSp]: pad slots keep their permanent NONE / -1 / 0 contents
             const size_t PS = ctx->PS, PSp = ctx->PSp;
@@ -2103,7 +2163,8 @@ static int fraction_load(cn_ctx *ctx, cn_layer *input, cn_layer *post_output, co
             }
             HIP_CHECK(hipStreamSynchronize(ctx->stream));     // the caller may reuse its host buffers on return
         }
-        set_current(ctx, f);
+        const cn_fraction fnet = network_rate(ctx->splice, *f);
+        set_current(ctx, &fnet);
         for (cn_layer *l : ctx->layers) l->ctc_labels_valid = l->ctc_swept = false;      // the labels belonged to the fraction that has been replaced
     });
 }
@@ -2148,10 +2209,11 @@ static int fraction_prefetch(cn_ctx *ctx, cn_layer *input, cn_layer *post_output
             pf.allocated = true;
         }
         if (post_output && post_output->targets && !pf.targets) pf.targets = (float *)dalloc(post_output, input->maxN() * post_output->size * sizeof(float));
-        check_augment_shape(ctx->aug, input);
+        check_augment_shape(ctx->aug, ctx->splice, input);
         pf.f = *f; pf.input = input; pf.post = post_output; pf.launched = false; pf.host = host;
         pf.aug = ctx->aug;                  // the load that follows is a hit only under these settings
-        if (aug_enabled(pf.aug)) ensure_aug_table(ctx, pf.aug_tab);
+        pf.splice = ctx->splice;
+        if (aug_enabled(pf.aug) || splice_enabled(pf.splice)) ensure_aug_table(ctx, pf.aug_tab);
         if (host) {
             // pack and upload NOW (copy stream, beside whatever the device is doing); the re-layout follows on the side stream of the
             // next gradient work, reading the staging area
@@ -3047,6 +3109,20 @@ int cn_ctx_set_input_augment(cn_ctx *ctx, const cn_input_augment *a)
         enter(ctx);
         ctx->aug = *a;
         ensure_aug_table(ctx, ctx->aug_tab);
+    });
+}
+
+// ---- input splicing and frame skipping (include/currennt_hip.h, section of that name) ----
+int cn_ctx_set_input_splice(cn_ctx *ctx, const cn_input_splice *s)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_input_splice: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!s) { ctx->splice = cn_input_splice{}; return; }
+        const char *w = "cn_ctx_set_input_splice: ";
+        if (s->context_left < 0 || s->context_right < 0 || s->context_left > 32 || s->context_right > 32)
+            throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "context_left / context_right must be in 0..32");
+        if (s->frame_skip < 1 || s->frame_skip > 16) throw cn_error(CN_ERR_BAD_ARG, std::string(w) + "frame_skip must be in 1..16");
+        ctx->splice = *s;
     });
 }
 

@@ -279,10 +279,13 @@ void launch_pad_convert(hipStream_t s, bool f32, const float *src, int N, int P,
 // ---- input augmentation (include/currennt_hip.h, section Input augmentation; cn_augment.hip) ----
 // The settings of one re-layout as the kernels take them: P0 = P / (ctx_left + ctx_right + 1) features per frame, the two Philox
 // keys ((seed_lo, seed_hi ^ "inpt") for the noise, (seed_lo, seed_hi ^ "mask") for the masks) and counter words 2 and 3.
+// skip: the frame skip of a spliced load (section Input splicing and frame skipping): time t is network frame t, centred on
+// source frame skip * t; 1 for every load that takes its fraction at network rate.
 struct AugArgs {
     int P0, ctx_left, nfreq, fwidth, ntime, twidth, permille;
     uint32_t k0, k1_noise, k1_mask, pass_lo, pass_hi;
     float sigma;
+    int skip;
 };
 #define AUG_MAX_MASKS 8                          // per kind
 #define AUG_TAB_STRIDE (1 + 4 * AUG_MAX_MASKS)   // ints per slot: len, (start, width) of the frequency masks, then of the time masks
@@ -295,6 +298,15 @@ void launch_fraction_load_augment(hipStream_t s, bool f32, const AugArgs &a, con
 // launch_pad_convert of inputs already in the device's row layout (src[T * PSp][P], dpat[T * PSp]), with the same augmentation
 void launch_pad_convert_augment(hipStream_t s, bool f32, const AugArgs &a, const int *tab, const float *src, const char *dpat, int T, int PS, int PSp,
                                 int P, void *dst, int Pp);
+// ---- input splicing and frame skipping (include/currennt_hip.h, section of that name; cn_splice.hip) ----
+// The re-layout of a SOURCE-rate fraction (Tsrc steps of unspliced P0-wide patterns, host layout [Tsrc][PS]) into the Tnet =
+// ceil(Tsrc / a.skip) network-rate steps of the padded device layout: derived pattern types, the classes / target rows of source
+// row skip * j, the gathered inputs (P = B * P0 columns; through augment_value when `augment`), then the row map.  `tab` is
+// launch_augment_table's for the source pattern types (row[0] = len_s is all an un-augmented load uses of it); a.P0, a.ctx_left
+// and a.skip are read whether `augment` or not.
+void launch_fraction_load_splice(hipStream_t s, bool f32, const AugArgs &a, bool augment, const int *tab, int Tnet, int PS, int PSp,
+                                 char *dpat, const int *tcls, int *dtcls, const float *tgt, float *dtgt, int W, const float *in, int P,
+                                 void *dst, int Pp, int *rm, int maxN, int Tmin_net);
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
 // The key of one forward pass of one layer, and the geometry that maps a padded element to the reference (frame, unit) the mask
 // is stated in: row r = t * PSp + ps <-> frame n = t * PS + ps (pad slots ps >= PS: zeros); column -> unit as unpad_col does

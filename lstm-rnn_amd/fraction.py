@@ -11,14 +11,20 @@ PATTYPE_NONE, PATTYPE_FIRST, PATTYPE_NORMAL, PATTYPE_LAST = 0, 1, 2, 3
 
 
 def make_fraction(inputs, targets, parallel_sequences, classification=True, output_size=None,
-                  context_left=0, context_right=0, output_lag=0, labels=None):
+                  context_left=0, context_right=0, output_lag=0, labels=None, frame_skip=1):
     """inputs: list of [len_i][P] float arrays; targets: list of [len_i] int arrays (classification)
     or [len_i][L] float arrays.  Returns the dict layout used by NeuralNetwork.load_sequences.
     context_left/right splice neighbouring frames into each input pattern (edge frames repeated) and
     output_lag delays the targets (class 0 / value 1.0 before the lag), DataSet.cpp:302-305,346-397.
     labels: list of int arrays, the label sequence of each sequence for a ctc net (no counterpart in the reference); `targets`
-    may then be None (the per-frame classes stay -1)."""
+    may then be None (the per-frame classes stay -1).
+    frame_skip k > 1: low-frame-rate input, the host path of include/currennt_hip.h, section Input splicing and frame skipping:
+    rows k * j of the spliced (and lagged) fraction with the pattern types of sequences of ceil(len_i / k) frames; T, Tmin and
+    seqLengths are then the network-rate ones."""
     PS = int(parallel_sequences)
+    skip = int(frame_skip)
+    if skip < 1:
+        raise ValueError("frame_skip must be >= 1")
     if not inputs or len(inputs) > PS:
         raise ValueError("need 1..parallel_sequences sequences")
     lengths = [int(x.shape[0]) for x in inputs]
@@ -56,6 +62,21 @@ def make_fraction(inputs, targets, parallel_sequences, classification=True, outp
         pat[0, i] = PATTYPE_FIRST
         if n > 1:
             pat[n - 1, i] = PATTYPE_LAST
+    if skip > 1:
+        x, pat = x[::skip], pat[::skip].copy()                       # rows skip * j; fresh pattern types for the ceil(n / skip) frames kept
+        if classification:
+            tc = tc[::skip]
+        else:
+            tg = tg[::skip]
+        for i, n in enumerate(lengths):
+            m = -(-n // skip)
+            pat[:m, i] = PATTYPE_NORMAL
+            pat[0, i] = PATTYPE_FIRST
+            if m > 1:
+                pat[m - 1, i] = PATTYPE_LAST
+        lengths = [-(-n // skip) for n in lengths]
+        T, Tmin = -(-T // skip), -(-Tmin // skip)
+        frac.update(T=T, Tmin=Tmin, seqLengths=lengths)
     frac["inputs"] = x.reshape(T * PS, P)
     frac["patTypes"] = pat.reshape(T * PS)
     if classification:

@@ -61,6 +61,11 @@ const char *Configuration::usage()
            "            --spec_augment_freq_masks N --spec_augment_freq_width F --spec_augment_time_masks N --spec_augment_time_width W\n"
            "            --spec_augment_time_ratio X (SpecAugment on the training fractions, on the device: N masks (0..8) of up to F\n"
            "                      features / W frames each set to 0; a time mask is at most X (0..1, default 1) of its sequence)\n"
+           "            --input_frame_skip K (low-frame-rate input, every set and --ff_input_file: the network runs on every K-th frame,\n"
+           "                      each with its --input_left_context / --input_right_context frames spliced around it; 1..16, default 1)\n"
+           "            --input_splice_on_device B (upload the frames unspliced at source rate and splice / skip where a fraction is\n"
+           "                      re-laid out on the device; contexts of at most 32 frames per side; default false.  With a skip above\n"
+           "                      1, --input_noise_on_device and --spec_augment_* need it: they belong to the source frames)\n"
            "            --momentum X --save_network F --train_file F[,F] --val_file F --test_file F --truncate_seq N\n"
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
@@ -164,6 +169,12 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "input_left_context") m_inputLeftContext = atoi(v.c_str());
     else if (key == "input_right_context") m_inputRightContext = atoi(v.c_str());
     else if (key == "output_time_lag") m_outputTimeLag = atoi(v.c_str());
+    else if (key == "input_frame_skip") {
+        m_inputFrameSkip = atoi(v.c_str());
+        if (m_inputFrameSkip < 1 || m_inputFrameSkip > 16)
+            throw std::runtime_error("Error while parsing the command line and/or options file: --input_frame_skip must be in 1..16");
+    }
+    else if (key == "input_splice_on_device") m_inputSpliceOnDevice = toBool(key, v);
     else if (key == "autosave") m_autosave = toBool(key, v);
     else if (key == "autosave_best") m_autosaveBest = toBool(key, v);
     else if (key == "autosave_prefix") m_autosavePrefix = v;
@@ -224,6 +235,14 @@ Configuration::Configuration(int argc, const char *argv[])
     if (const char *dev = getenv("CURRENNT_CUDA_DEVICE")) m_device = atoi(dev);       // main.cpp:527-531 (kept under its old name)
     for (size_t i = 0; i < cli.size(); ++i) apply(cli[i].first, cli[i].second);   // command line wins
     if (m_parallelSequences < 1) throw std::runtime_error("Error while parsing the command line and/or options file: parallel_sequences must be >= 1");
+    // The device's augmentation belongs to the SOURCE frames (include/currennt_hip.h, section Input augmentation).  Fractions the
+    // host has already skipped frames of carry network-rate rows, where that rule cannot be applied: it takes the device's splice.
+    if (m_inputFrameSkip > 1 && !m_inputSpliceOnDevice && ((m_inputNoiseOnDevice && m_inputNoiseSigma > 0) || specAugment()))
+        throw std::runtime_error("Error while parsing the command line and/or options file: --input_noise_on_device and --spec_augment_* "
+                                 "with --input_frame_skip above 1 need --input_splice_on_device true");
+    if (m_inputSpliceOnDevice && (m_inputLeftContext < 0 || m_inputLeftContext > 32 || m_inputRightContext < 0 || m_inputRightContext > 32))
+        throw std::runtime_error("Error while parsing the command line and/or options file: --input_splice_on_device true needs "
+                                 "--input_left_context and --input_right_context in 0..32");
 }
 
 }  // namespace currennt_hip

@@ -95,6 +95,10 @@ public:
     bool specAugment() const { return m_specFreqMasks > 0 || m_specTimeMasks > 0; }
     int inputLeftContext() const { return m_inputLeftContext; }
     int inputRightContext() const { return m_inputRightContext; }
+    // --input_frame_skip K: the network runs on every K-th frame; --input_splice_on_device: the fractions go up unspliced at source
+    // rate and the device splices and skips (include/currennt_hip.h, section Input splicing and frame skipping)
+    int inputFrameSkip() const { return m_inputFrameSkip; }
+    bool inputSpliceOnDevice() const { return m_inputSpliceOnDevice; }
     int outputTimeLag() const { return m_outputTimeLag; }
     // autosave options of Configuration.cpp:159-164
     bool autosave() const { return m_autosave; }
@@ -112,7 +116,8 @@ private:
     bool m_weightNoiseOnDevice = false, m_inputNoiseOnDevice = false;
     int m_specFreqMasks = 0, m_specFreqWidth = 0, m_specTimeMasks = 0, m_specTimeWidth = 0;
     real_t m_specTimeRatio = 1;
-    int m_inputLeftContext = 0, m_inputRightContext = 0, m_outputTimeLag = 0;
+    int m_inputLeftContext = 0, m_inputRightContext = 0, m_outputTimeLag = 0, m_inputFrameSkip = 1;
+    bool m_inputSpliceOnDevice = false;
     std::string m_autosavePrefix, m_continueFile, m_serializedOptions;
     bool m_help = false, m_trainingMode = false, m_hybridOnlineBatch = false, m_shuffleFractions = false,
          m_shuffleSequences = false, m_listDevices = false, m_revertStd = true, m_weightsNormal = false;

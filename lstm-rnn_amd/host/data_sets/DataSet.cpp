@@ -36,6 +36,7 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
 {
     if (augment.contextLeft < 0 || augment.contextRight < 0 || augment.outputLag < 0)
         throw std::runtime_error("Negative input context / output time lag");
+    if (augment.frameSkip < 1) throw std::runtime_error("Invalid input frame skip");
     if (fraction <= 0 || fraction > 1) throw std::runtime_error("Invalid fraction");        // DataSet.cpp:457-458
     bool firstFile = true;
     for (size_t fi = 0; fi < ncfiles.size(); ++fi) {
@@ -65,6 +66,7 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
             for (size_t k = 0; k < pieces.size(); ++k) {
                 sequence_t seq;
                 seq.originalSeqIdx = (int)k; seq.length = pieces[k]; seq.seqTag = seqTag;
+                m_totalNetworkTimesteps += (pieces[k] + augment.frameSkip - 1) / augment.frameSkip;
                 seq.inputsBegin = 0; seq.targetsBegin = 0;
                 sequences.push_back(seq);
             }
@@ -139,8 +141,14 @@ void DataSet::shuffleFractions()
 void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
 {
     const int PS = m_parallelSequences;
-    const int ctxL = m_augment.contextLeft, ctxR = m_augment.contextRight, lag = m_augment.outputLag;   // :302-305
-    const int P = m_inputPatternSize, Pf = P * (ctxL + ctxR + 1);
+    const int lag = m_augment.outputLag;                                                       // :302-305
+    const int P = m_inputPatternSize;
+    // --input_frame_skip: the fraction holds network frame j = source frame K * j of every sequence.  A source-rate fraction
+    // (--input_splice_on_device) is packed with K = 1 and no context; the network-rate lengths and pattern types ride along.
+    const bool source = m_augment.spliceOnDevice;
+    const int skip = m_augment.frameSkip, K = source ? 1 : skip;
+    const int ctxL = source ? 0 : m_augment.contextLeft, ctxR = source ? 0 : m_augment.contextRight, Pf = P * (ctxL + ctxR + 1);
+    auto kept = [](int length, int k) { return (length + k - 1) / k; };
     *frac = DataSetFraction();
     frac->m_inputPatternSize = Pf;
     frac->m_outputPatternSize = m_outputPatternSize;
@@ -151,13 +159,17 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
     for (int i = 0; i < PS; ++i) {                                                             // :316-328
         const int seqIdx = globalIdx(i);
         if (seqIdx >= (int)m_sequences.size()) continue;
-        frac->m_maxSeqLength = std::max(frac->m_maxSeqLength, m_sequences[seqIdx].length);
-        frac->m_minSeqLength = std::min(frac->m_minSeqLength, m_sequences[seqIdx].length);
-        DataSetFraction::seq_info_t si = { m_sequences[seqIdx].originalSeqIdx, m_sequences[seqIdx].length, m_sequences[seqIdx].seqTag };
+        frac->m_maxSeqLength = std::max(frac->m_maxSeqLength, kept(m_sequences[seqIdx].length, K));
+        frac->m_minSeqLength = std::min(frac->m_minSeqLength, kept(m_sequences[seqIdx].length, K));
+        DataSetFraction::seq_info_t si = { m_sequences[seqIdx].originalSeqIdx, kept(m_sequences[seqIdx].length, skip), m_sequences[seqIdx].seqTag };
         frac->m_seqInfo.push_back(si);
     }
     if (frac->m_seqInfo.empty()) { frac->m_maxSeqLength = 1; frac->m_minSeqLength = 0; }        // all-dummy fraction (setShard)
     const size_t slots = (size_t)frac->m_maxSeqLength * PS;
+    if (source) {
+        frac->m_netMaxSeqLength = kept(frac->m_maxSeqLength, skip); frac->m_netMinSeqLength = kept(frac->m_minSeqLength, skip);
+        frac->m_netPatTypes.assign((size_t)frac->m_netMaxSeqLength * PS, (char)PATTYPE_NONE);
+    }
     frac->m_inputs.assign(slots * Pf, 0.0f);                                                   // :330-336
     frac->m_patTypes.assign(slots, (char)PATTYPE_NONE);
     if (m_isClassificationData) frac->m_targetClasses.assign(slots, -1);
@@ -183,8 +195,10 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
             for (size_t k = 0; k < noisy.size(); ++k) noisy[k] += dist(m_noiseGen);
             src = noisy.data();
         }
-        for (int t = 0; t < seq.length; ++t) {
-            const size_t slot = (size_t)t * PS + i;
+        const int frames = kept(seq.length, K);
+        for (int j = 0; j < frames; ++j) {
+            const int t = K * j;
+            const size_t slot = (size_t)j * PS + i;
             for (int off = -ctxL, k = 0; off <= ctxR; ++off, ++k) {                            // :346-366, edge frames are repeated
                 const int ts = std::min(std::max(t + off, 0), seq.length - 1);
                 std::copy(src + (size_t)ts * P, src + (size_t)(ts + 1) * P, frac->m_inputs.begin() + slot * Pf + (size_t)k * P);
@@ -196,8 +210,11 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
                           m_targetData.begin() + seq.targetsBegin + (size_t)(t - lag + 1) * m_outputPatternSize,
                           frac->m_outputs.begin() + slot * m_outputPatternSize);
             else std::fill_n(frac->m_outputs.begin() + slot * m_outputPatternSize, m_outputPatternSize, 1.0f);
-            frac->m_patTypes[slot] = (char)(t == 0 ? PATTYPE_FIRST : (t == seq.length - 1 ? PATTYPE_LAST : PATTYPE_NORMAL));   // :400-407
+            frac->m_patTypes[slot] = (char)(j == 0 ? PATTYPE_FIRST : (j == frames - 1 ? PATTYPE_LAST : PATTYPE_NORMAL));   // :400-407
         }
+        if (source)
+            for (int j = 0, n = kept(seq.length, skip); j < n; ++j)
+                frac->m_netPatTypes[(size_t)j * PS + i] = (char)(j == 0 ? PATTYPE_FIRST : (j == n - 1 ? PATTYPE_LAST : PATTYPE_NORMAL));
     }
 }
 

@@ -22,6 +22,14 @@ public:
     int outputPatternSize() const { return m_outputPatternSize; }
     int maxSeqLength() const { return m_maxSeqLength; }
     int minSeqLength() const { return m_minSeqLength; }
+    // The lengths and pattern types every layer behind the input re-layout sees.  They are the fraction's own unless it is a
+    // source-rate fraction for the device to splice and skip (Augment::spliceOnDevice): then maxSeqLength() / minSeqLength() /
+    // patTypes() / inputs() are what is uploaded and these are what include/currennt_hip.h, section Input splicing and frame
+    // skipping, derives from them.  seqInfo(i).length is always the network-rate length.
+    bool sourceRate() const { return !m_netPatTypes.empty(); }
+    int networkMaxSeqLength() const { return m_netPatTypes.empty() ? m_maxSeqLength : m_netMaxSeqLength; }
+    int networkMinSeqLength() const { return m_netPatTypes.empty() ? m_minSeqLength : m_netMinSeqLength; }
+    const Hip::pattype_vector &networkPatTypes() const { return m_netPatTypes.empty() ? m_patTypes : m_netPatTypes; }
     int numSequences() const { return (int)m_seqInfo.size(); }
     const seq_info_t &seqInfo(int seqIdx) const { return m_seqInfo.at(seqIdx); }
     const Hip::pattype_vector &patTypes() const { return m_patTypes; }
@@ -35,7 +43,8 @@ public:
 
 private:
     friend class DataSet;
-    int m_inputPatternSize = 0, m_outputPatternSize = 0, m_maxSeqLength = 0, m_minSeqLength = 0;
+    int m_inputPatternSize = 0, m_outputPatternSize = 0, m_maxSeqLength = 0, m_minSeqLength = 0, m_netMaxSeqLength = 0, m_netMinSeqLength = 0;
+    Hip::pattype_vector m_netPatTypes;
     std::vector<seq_info_t> m_seqInfo;
     Hip::real_vector m_inputs, m_outputs;
     Hip::pattype_vector m_patTypes;
@@ -45,7 +54,10 @@ private:
 
 // what the reference pulls from Configuration::instance() inside _makeFractionTask / _addNoise
 // (DataSet.cpp:252-265,302-305): Gaussian input noise, context splicing, output time lag
-struct Augment { real_t noiseDeviation = 0; int contextLeft = 0, contextRight = 0, outputLag = 0; };
+// frameSkip K (--input_frame_skip): the fractions keep frames K * j of every sequence, each with its context spliced around it and
+// the targets of frame K * j (the lag applies at source rate), as sequences of ceil(length / K) frames.  spliceOnDevice
+// (--input_splice_on_device): the fractions are emitted unspliced at source rate instead, for cn_ctx_set_input_splice
+struct Augment { real_t noiseDeviation = 0; int contextLeft = 0, contextRight = 0, outputLag = 0, frameSkip = 1; bool spliceOnDevice = false; };
 
 class DataSet {
 public:
@@ -73,6 +85,9 @@ public:
     bool getNextFraction(DataSetFraction *frac);
     int totalSequences() const { return m_totalSequences; }
     int totalTimesteps() const { return m_totalTimesteps; }
+    // the frames the network sees: the sum of ceil(length / frameSkip) over the sequences, the pieces of --truncate_seq each on
+    // its own (= totalTimesteps() at a skip of 1).  What a per-frame error rate is taken over.
+    int totalNetworkTimesteps() const { return m_totalNetworkTimesteps; }
     int minSeqLength() const { return m_minSeqLength; }
     int maxSeqLength() const { return m_maxSeqLength; }
     int inputPatternSize() const { return m_inputPatternSize; }                        // per frame, before context splicing
@@ -90,7 +105,7 @@ private:
     double m_loaderSeconds = 0;
     long m_loaderFractions = 0;
     bool m_fractionShuffling = false, m_sequenceShuffling = false, m_isClassificationData = false;
-    int m_parallelSequences = 0, m_totalSequences = 0, m_totalTimesteps = 0, m_minSeqLength = 0, m_maxSeqLength = 0,
+    int m_parallelSequences = 0, m_totalSequences = 0, m_totalTimesteps = 0, m_totalNetworkTimesteps = 0, m_minSeqLength = 0, m_maxSeqLength = 0,
         m_inputPatternSize = 0, m_outputPatternSize = 0, m_numLabels = 0, m_curFirstSeqIdx = -1, m_rank = 0, m_world = 1;
     unsigned m_rngState = 0;
     Hip::real_vector m_outputMeans, m_outputStdevs, m_inputData, m_targetData;

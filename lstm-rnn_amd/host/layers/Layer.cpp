@@ -82,10 +82,10 @@ Hip::real_vector Layer::outputErrors() const { return read(CN_BUF_OUTPUT_ERRORS,
 
 void Layer::loadSequences(const data_sets::DataSetFraction &fraction)
 {
-    m_curMaxSeqLength = fraction.maxSeqLength();
-    m_curMinSeqLength = fraction.minSeqLength();
+    m_curMaxSeqLength = fraction.networkMaxSeqLength();     // (a source-rate fraction: what the device derives from it)
+    m_curMinSeqLength = fraction.networkMinSeqLength();
     m_curNumSeqs = fraction.numSequences();
-    m_patTypes = fraction.patTypes();
+    m_patTypes = fraction.networkPatTypes();
 }
 void Layer::computeForwardPass() { hipCheck(cn_layer_forward(m_handle), m_ctx); }
 void Layer::computeBackwardPass() { hipCheck(cn_layer_backward(m_handle), m_ctx); }
@@ -106,7 +106,8 @@ InputLayer::InputLayer(cn_ctx *ctx, const json::Value &layerChild, int parallelS
 const std::string &InputLayer::type() const { static const std::string s("input"); return s; }
 void InputLayer::loadSequences(const data_sets::DataSetFraction &fraction)
 {
-    if (fraction.inputPatternSize() != size())                                                   // InputLayer.cpp:52-55
+    // (a source-rate fraction brings unspliced patterns: the library holds their size to this layer's at the load)
+    if (fraction.inputPatternSize() != size() && !fraction.sourceRate())   // InputLayer.cpp:52-55
         throw std::runtime_error("Input layer size of " + std::to_string(size()) + " != data input pattern size of " +
                                  std::to_string(fraction.inputPatternSize()));
     Layer::loadSequences(fraction);

@@ -47,6 +47,7 @@ std::shared_ptr<data_sets::DataSet> loadDataSet(const Configuration &config, dat
     std::string type; std::vector<std::string> filenames; real_t fraction = 1; bool fracShuf = false, seqShuf = false; int truncSeqLength = 0;
     data_sets::DataSet::Augment augment;            // context and lag apply to every set (DataSet.cpp:302-305), noise to two (main.cpp:593,613)
     augment.contextLeft = config.inputLeftContext(); augment.contextRight = config.inputRightContext(); augment.outputLag = config.outputTimeLag();
+    augment.frameSkip = config.inputFrameSkip(); augment.spliceOnDevice = config.inputSpliceOnDevice();     // every set, like the contexts
     switch (dsType) {
     case DATA_SET_TRAINING: type = "training set"; filenames = config.trainingFiles(); fraction = config.trainingFraction();
         fracShuf = config.shuffleFractions(); seqShuf = config.shuffleSequences(); truncSeqLength = config.truncateSeqLength();
@@ -73,6 +74,10 @@ std::shared_ptr<data_sets::DataSet> loadDataSet(const Configuration &config, dat
     printf("Sequences:        %d\n", ds->totalSequences());
     printf("Sequence lengths: %d..%d\n", ds->minSeqLength(), ds->maxSeqLength());
     printf("Total timesteps:  %d\n", ds->totalTimesteps());
+    if (config.inputFrameSkip() > 1) printf("Input frame skip: %d (the network sees sequences of %d..%d frames, %d frames in all)\n", config.inputFrameSkip(),
+                                            (ds->minSeqLength() + config.inputFrameSkip() - 1) / config.inputFrameSkip(),
+                                            (ds->maxSeqLength() + config.inputFrameSkip() - 1) / config.inputFrameSkip(), ds->totalNetworkTimesteps());
+    if (config.inputSpliceOnDevice()) printf("Input splicing:   on the device (context %d + %d frames, uploaded unspliced)\n", config.inputLeftContext(), config.inputRightContext());
     if (deviceNoise) printf("Input noise:      sigma %g, generated on the device\n", (double)deviceSigma);
     if (dsType == DATA_SET_TRAINING && config.specAugment())
         printf("SpecAugment:      %d frequency masks of up to %d features, %d time masks of up to %d frames (at most %g of a sequence), on the device\n",
@@ -211,7 +216,7 @@ void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::Data
             } else if (!outputs[psIdx].empty()) {                                                // FORMAT_HTK, main.cpp:432-480
                 std::ofstream file((dir + "/" + base + ".htk").c_str(), std::ofstream::out | std::ios::binary);
                 unsigned tmp = (unsigned)outputs[psIdx].size(); swap32(&tmp); file.write((const char *)&tmp, 4);
-                tmp = (unsigned)(config.featurePeriod() * 1e4); swap32(&tmp); file.write((const char *)&tmp, 4);
+                tmp = (unsigned)(config.featurePeriod() * config.inputFrameSkip() * 1e4); swap32(&tmp); file.write((const char *)&tmp, 4);     // (a row every K source frames)
                 unsigned short tmp2 = (unsigned short)(outputs[psIdx][0].size() * sizeof(float)); swap16(&tmp2); file.write((const char *)&tmp2, 2);
                 tmp2 = (unsigned short)config.outputFeatureKind(); swap16(&tmp2); file.write((const char *)&tmp2, 2);
                 for (size_t t = 0; t < outputs[psIdx].size(); ++t)
@@ -245,6 +250,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
         int maxSeqLength = config.trainingMode()
             ? std::max(trainingSet->maxSeqLength(), std::max(validationSet->maxSeqLength(), testSet->maxSeqLength()))
             : feedForwardSet->maxSeqLength();
+        // --input_frame_skip: the layers run on every K-th frame (the data sets report their lengths at source rate)
+        if (maxSeqLength > 0) maxSeqLength = (maxSeqLength + config.inputFrameSkip() - 1) / config.inputFrameSkip();
 
         if (config.dumpFractions()) {     // host-only check of reader + packer (no GPU needed)
             data_sets::DataSet &ds = config.trainingMode() ? *trainingSet : *feedForwardSet;
@@ -259,7 +266,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                     for (size_t i = 0; i < frac.inputs().size(); ++i) sx += frac.inputs()[i];
                     for (size_t i = 0; i < frac.targetClasses().size(); ++i) if (frac.targetClasses()[i] >= 0) st += frac.targetClasses()[i];
                     for (size_t i = 0; i < frac.outputs().size(); ++i) sx += 1000.0 * frac.outputs()[i];
-                    for (size_t i = 0; i < frac.patTypes().size(); ++i) none += frac.patTypes()[i] == PATTYPE_NONE;
+                    // (T, Tmin, none and lens are network-rate: with --input_splice_on_device what the device derives from the fraction)
+                    for (size_t i = 0; i < frac.networkPatTypes().size(); ++i) none += frac.networkPatTypes()[i] == PATTYPE_NONE;
                     // tags / lens / pieces = the sequences of the fraction, slot by slot: tag, length and piece number under
                     // --truncate_seq (the length sort is std::sort like the reference's, DataSet.cpp:603-605: ties land in an
                     // implementation-defined order, which a checker has to be told)
@@ -271,7 +279,7 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                     }
                     const bool any = frac.numSequences() > 0;
                     printf("FRACTION %d T=%d Tmin=%d seqs=%d none=%d sum_inputs=%.6f sum_targets=%ld first_tag=%s tags=%s lens=%s pieces=%s", idx++,
-                           frac.maxSeqLength(), frac.minSeqLength(), frac.numSequences(), none, sx, st, any ? frac.seqInfo(0).seqTag.c_str() : "-",
+                           frac.networkMaxSeqLength(), frac.networkMinSeqLength(), frac.numSequences(), none, sx, st, any ? frac.seqInfo(0).seqTag.c_str() : "-",
                            any ? order.c_str() : "-", any ? lens.c_str() : "-", any ? pieces.c_str() : "-");
                     if (config.dumpLabels()) {      // --dump_labels: the label sequences a ctc layer would train against
                         long total = 0, sum = 0;
@@ -318,6 +326,10 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
         const bool sameDevice = dp.active && testHook("CN_DP_SAME_DEVICE") != 0;
         NeuralNetwork neuralNetwork(netDoc, config.parallelSequences(), maxSeqLength, inputSize, config.precision(), config.device() + (sameDevice ? 0 : dp.rank), &wi);
         if (config.deterministic() >= 0) hipCheck(cn_ctx_set_option(neuralNetwork.context(), "deterministic", config.deterministic()), neuralNetwork.context());
+        if (config.inputSpliceOnDevice()) {       // once: every set's fractions come unspliced at source rate (DataSet::makeFraction)
+            const cn_input_splice sp = { config.inputLeftContext(), config.inputRightContext(), config.inputFrameSkip() };
+            hipCheck(cn_ctx_set_input_splice(neuralNetwork.context(), &sp), neuralNetwork.context());
+        }
         if (dp.active) {
             // rendezvous: rank 0 draws the id and hands it to the other ranks through their pipes, then every rank joins
             char id[CN_COMM_ID_BYTES];

@@ -72,7 +72,7 @@ int ctcLabelErrors(const Hip::real_vector &out, int PS, int C, int slot, int len
 real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates, real_t *classError)
 {
     real_t error = 0;
-    *classError = (real_t)ds.totalTimesteps();
+    *classError = (real_t)ds.totalNetworkTimesteps();      // (the frames the network classifies: --input_frame_skip)
     const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
     const bool classification = dynamic_cast<layers::MulticlassClassificationLayer *>(&m_neuralNetwork.postOutputLayer()) != 0 ||
                                 dynamic_cast<layers::BinaryClassificationLayer *>(&m_neuralNetwork.postOutputLayer()) != 0;   // Optimizer.cu:52-55
@@ -189,7 +189,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         if (classification) *classError -= (real_t)correct;
     }
     error /= ds.totalSequences();                                           // :99-101
-    *classError /= (real_t)ds.totalTimesteps();
+    *classError /= (real_t)ds.totalNetworkTimesteps();
     if (ctc) *classError = labelCount ? (real_t)labelErrors / (real_t)labelCount : 0;
     return error;
 }

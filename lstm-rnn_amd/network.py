@@ -230,6 +230,7 @@ class NeuralNetwork:
             self.set_option(name, value)
         self.layers = []
         self.T = self.Tmin = self.N = 0
+        self.frame_skip = 1                               # set_input_splice: loads take source-rate fractions, read-backs go by ceil(T / k)
         try:
             names = set()
             prev = None
@@ -335,10 +336,15 @@ class NeuralNetwork:
         f, keep = self._host_descriptor(frac)
         # (the library copies the host arrays into pinned staging memory before it returns: nothing to wait for)
         B.check(self.lib.cn_fraction_load(self.ctx, self.layers[0].handle, self.layers[-1].handle, C.byref(f)), self.ctx)
-        self.T, self.Tmin = f.max_seq_length, f.min_seq_length
-        self.N = self.T * self.PS
+        self._set_current(f)
         if self.layers[-1].type == "ctc" and frac.get("labels") is not None:
             self.set_label_sequences(frac["labels"])
+
+    def _set_current(self, f):
+        """The lengths of the fraction just loaded as the layers see them: f's, or ceil(f's / frame_skip) under set_input_splice."""
+        k = self.frame_skip
+        self.T, self.Tmin = -(-f.max_seq_length // k), -(-f.min_seq_length // k)
+        self.N = self.T * self.PS
 
     def set_label_sequences(self, labels):
         """cn_layer_set_label_sequences: one int array of labels per sequence of the fraction loaded last (a ctc net)."""
@@ -377,8 +383,7 @@ class NeuralNetwork:
         f = self._resident_descriptor(dfrac)
         B.check(self.lib.cn_fraction_load_resident(self.ctx, self.layers[0].handle, self.layers[-1].handle,
                                                    C.byref(f)), self.ctx)
-        self.T, self.Tmin = f.max_seq_length, f.min_seq_length
-        self.N = self.T * self.PS
+        self._set_current(f)
 
     def loss_accumulate(self):
         """Add this fraction's error / #correct to the device-side epoch sums (no host sync)."""
@@ -591,6 +596,19 @@ class NeuralNetwork:
         a = B.InputAugment(float(noise_sigma), int(context[0]), int(context[1]), int(freq_masks), int(freq_width), int(time_masks),
                            int(time_width), int(time_max_permille), int(seed) & (2 ** 64 - 1), int(pass_) & (2 ** 64 - 1))
         B.check(self.lib.cn_ctx_set_input_augment(self.ctx, C.byref(a)), self.ctx)
+
+    def set_input_splice(self, context=(0, 0), frame_skip=1):
+        """cn_ctx_set_input_splice: the loads (and prefetches) that follow take a fraction built WITHOUT context at source rate
+        (make_fraction(xs, ts, PS)); the device splices `context` = (left, right) neighbouring frames into each pattern and keeps
+        every frame_skip-th frame (include/currennt_hip.h, section Input splicing and frame skipping).  Every read-back is then
+        sized by ceil(T / frame_skip).  set_input_splice(None) turns it off; (0, 0) with frame_skip 1 is on, the identity."""
+        if context is None:
+            B.check(self.lib.cn_ctx_set_input_splice(self.ctx, None), self.ctx)
+            self.frame_skip = 1
+            return
+        s = B.InputSplice(int(context[0]), int(context[1]), int(frame_skip))
+        B.check(self.lib.cn_ctx_set_input_splice(self.ctx, C.byref(s)), self.ctx)
+        self.frame_skip = int(frame_skip)
 
     def set_grad_clip(self, max_norm):
         """cn_ctx_set_grad_clip: clip every update's gradient to this global L2 norm (include/currennt_hip.h, section Gradient
