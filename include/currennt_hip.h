@@ -513,6 +513,42 @@ int  cn_ctx_set_grad_clip(cn_ctx *ctx, float max_norm);
 int  cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, int64_t *updates, int64_t *clipped, int64_t *skipped,
                             float *max_norm_seen, int reset);
 
+/* ---- Weight decay (decoupled: Loshchilov & Hutter 2019, "Decoupled Weight Decay Regularization"; no counterpart in the
+ *      reference) -----------------------------------------------------------------------------------------------------------------
+ * One rule, in front of the momentum rule and of the Adam rule alike: the weight shrinks by a fraction of itself that does not pass
+ * through the gradient, the momentum term or Adam's moments.  (Not the coupled L2 term g + decay * w.)
+ *
+ * The rule.  decay is a setting of the context, a float >= 0.  Per update of a layer the host forms
+ *      ld = (float)((double) lr_layer * (double) decay)                      rounded once
+ * where lr_layer is the rate that layer's step uses: the call's learning rate, or the layer's own (cn_layer_set_learning_rate).
+ * Under Adam ld uses the learning rate, not alpha_t.  Per weight the device computes
+ *      w0 = sub_rn(w, mul_rn(ld, w))                                         two fp32 operations, each rounded to nearest, no
+ *                                                                            contraction, denormals kept
+ * and the family's step runs with w0 in place of w:
+ *      momentum:  dl = mom * dl - lr * g;  w = add_rn(w0, dl)
+ *      Adam:      w = sub_rn(w0, (alpha_t * m) / (sqrt(v) + eps_t))          exactly as cn_adam_update states it
+ *
+ * What decays.  Input weights and internal (recurrent) weights only.  Bias weights, peephole weights and the arena's pad entries
+ * never do: for them w0 = w and no operation is performed.  In the flat reference layout of a layer with L units, P inputs and
+ * H = L / directions:
+ *      lstm / blstm:              [0, 4LP) and [4L(P+1), 4L(P+1) + 4LH) decay; the bias block [4LP, 4L(P+1)) and the trailing 3L
+ *                                 peephole weights do not
+ *      feedforward_* / softmax:   [0, LP) decays, the trailing L bias weights do not
+ *
+ * Order and interactions.  The clipping factor scales g only, and the decay term is no part of the norm.  A step the clipping
+ * record skips decays nothing: weights, deltas / moments and operand copies keep every bit.  Batch learning decays once per
+ * update, not per fraction.  Weight noise and weight averaging see the decayed weights as the weights.  Data-parallel: every rank
+ * decays the same weights by the same ld, so the replicas stay bit-identical without an exchange.  Armed updates stay overlapped
+ * with the backward pass (decay is local to a weight) unless clipping defers them; an armed step uses the decay in force when it
+ * was armed.  The operand copies a fused or armed step writes hold the decayed, updated weight.
+ *
+ * With decay 0 the library launches exactly what it launches without these calls and allocates nothing for them. */
+/* The coefficient; 0 = off, and a fresh context is off.  Negative, NaN or infinite: CN_ERR_BAD_ARG.  May be changed between steps;
+ * while an armed update is pending (armed or deferred): CN_ERR_STATE.  Allowed while the weights are swapped with their average:
+ * it only stores a number. */
+int  cn_ctx_set_weight_decay(cn_ctx *ctx, float decay);
+int  cn_ctx_get_weight_decay(const cn_ctx *ctx, float *decay);
+
 /* ---- Weight noise (--weight_noise_sigma, Optimizer.cu:58-84: the reference's only regulariser) ----------------------------------
  * Gaussian noise on the weights, seen by the backward pass alone: every backward product with a weight in it reads w' = w + n, while
  * the forward pass, the error and the update see the clean weights.  The reference draws the noise on the host; here it is

@@ -59,6 +59,8 @@ EXPORTS = [
     # include/currennt_hip.h, section Weight averaging
     "cn_ctx_average_weights", "cn_ctx_swap_weight_average", "cn_ctx_weight_average_state", "cn_layer_read_weight_average",
     "cn_layer_upload_weight_average",
+    # include/currennt_hip.h, section Weight decay
+    "cn_ctx_set_weight_decay", "cn_ctx_get_weight_decay",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -217,6 +219,8 @@ def load_library():
     L.cn_dbg_layer_norm_input.argtypes = [vp, vp, C.c_size_t]
     L.cn_ctx_set_grad_clip.argtypes = [vp, cf]
     L.cn_ctx_grad_clip_stats.argtypes = [vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(cf), ci]
+    L.cn_ctx_set_weight_decay.argtypes = [vp, cf]
+    L.cn_ctx_get_weight_decay.argtypes = [vp, C.POINTER(cf)]
     L.cn_ctx_set_weight_noise.argtypes = [vp, cf, C.c_uint64, C.c_uint64]
     L.cn_dbg_noisy_weights.argtypes = [vp, vp, C.c_size_t]
     L.cn_ctx_set_input_augment.argtypes = [vp, C.POINTER(InputAugment)]

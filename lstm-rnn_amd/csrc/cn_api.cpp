@@ -66,8 +66,10 @@ struct Scratch {
 };
 
 // The optimizer's rule of an update: momentum SGD (lr, mom) or Adam (lr, b1, b2, eps, step); lr is the caller's learning rate,
-// a layer with a rate of its own replaces it (layer_lr)
-struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0; };
+// a layer with a rate of its own replaces it (layer_lr).  decay: the context's weight decay in force when the call came in, or, of
+// an armed rule, when it was armed (cn_ctx_set_weight_decay; 0: off) -- the caller's arguments do not name it, so same_rule
+// does not compare it
+struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0; float decay = 0.f; };
 bool same_rule(const UpdateRule &a, const UpdateRule &b)
 {
     if (a.adam != b.adam) return false;
@@ -197,6 +199,9 @@ struct cn_ctx {
     // by the first non-zero bound -- and whether the record still holds the norm of what weightUpdates holds now (cleared by
     // everything that changes the gradient; the first update call behind that forms the norm again)
     float clip_max = 0.f;
+    // cn_ctx_set_weight_decay (section Weight decay): the coefficient of the update calls that follow (0: off).  Only a number: an
+    // update call copies it into its rule (UpdateRule::decay), an arming call into `arm`.
+    float decay = 0.f;
     ClipRecord *clip_rec = nullptr;
     bool clip_valid = false;
     // ... an armed step cannot run layer by layer behind a GLOBAL norm: with clipping on, arming only records the rule (`arm`) and
@@ -822,6 +827,15 @@ void finalize(cn_ctx *c)
 // ---- optimizer rule of an update launch ---------------------------------------------------------
 // a layer's JSON "learningRate" (SteepestDescentOptimizer.cu:78-80) replaces the rule's
 float layer_lr(const cn_layer *l, const UpdateRule &r) { return l->own_lr >= 0.f ? l->own_lr : r.lr; }
+// Weight decay (include/currennt_hip.h, section Weight decay): ld of a step at rate lr, formed in double and rounded once ...
+float decay_ld(float lr, float decay) { return (float)((double)lr * (double)decay); }
+// ... and the runs of a layer's flat range that decay: the input weights, and the recurrent weights of an LSTM layer
+DecayRanges decay_ranges(const cn_layer *l)
+{
+    const size_t L = (size_t)l->size, P = (size_t)l->P;
+    if (!l->lstm) return DecayRanges{L * P, 0, 0};
+    return DecayRanges{4 * L * P, 4 * L * (P + 1), 4 * L * (P + 1) + 4 * L * (size_t)l->H};
+}
 // The scalars of include/currennt_hip.h (cn_adam_update): formed in double from the float arguments, rounded once
 // lr: the effective rate (layer_lr)
 AdamScalars adam_scalars(const UpdateRule &r, float lr)
@@ -988,11 +1002,13 @@ PackItem &add_pack_item(PackGroup &grp, const cn_layer *l)
 }
 // ... and the step that rides on it, for the item added last: update mode (PackItem::update), the rule with the layer's effective
 // rate; Adam: the item's second moments and the scalars all items share
-void set_pack_update(PackGroup &grp, PackAdam &ad, int mode, const UpdateRule &r, const cn_layer *l)
+// dk: the item's ld, read by the launch when the rule's decay is on
+void set_pack_update(PackGroup &grp, PackAdam &ad, PackDecayArgs &dk, int mode, const UpdateRule &r, const cn_layer *l)
 {
     PackItem &it = grp.item[grp.n - 1];
     it.update = mode; it.w_rw = l->w; it.wu = l->wu; it.wd = l->wd;
     it.lr = layer_lr(l, r); it.mom = r.mom;
+    dk.ld[grp.n - 1] = decay_ld(it.lr, r.decay);
     if (r.adam) {
         const AdamScalars a = adam_scalars(r, it.lr);
         it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
@@ -1008,11 +1024,12 @@ void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule
     cn_ctx *c = l->ctx;
     PackGroup grp{};
     PackAdam ad{};
+    PackDecayArgs dk{};
     PackItem &it = add_pack_item(grp, l);
-    set_pack_update(grp, ad, mode, r, l);
+    set_pack_update(grp, ad, dk, mode, r, l);
     it.wu_rw = l->wu; it.g_in = l->dWin; it.g_rec = l->dWrec; it.g_bias = l->dbias; it.g_peep = l->dpeep;
     if (folds) { it.update = 3; it.f_in = folds[0]; it.f_rec[0] = folds[1]; it.f_rec[1] = folds[2]; it.f_bias = folds[3]; }
-    launch_pack_group(st, c->f32, grp, done, r.adam ? &ad : nullptr);
+    launch_pack_group(st, c->f32, grp, done, r.adam ? &ad : nullptr, nullptr, r.decay != 0.f ? &dk : nullptr);
     l->dirty = false; l->pack_pending = false; l->updated = true; l->noisy_ready = false;
 }
 // armed update without a communicator: unpack + update + operand copies ride on ONE launch behind the gradient GEMMs
@@ -2770,10 +2787,17 @@ static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
 }
 // the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in, at rate lr
 // clip: the record of the step's norm (clip_record below), or null with clipping off -- then the launches are the ones they were
-static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, const ClipRecord *clip, hipEvent_t done = nullptr)
+// decayed (with r.decay on; then the range is ONE layer's): the runs of the range that decay (decay_ranges)
+static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, const ClipRecord *clip, hipEvent_t done = nullptr,
+                        const DecayRanges *decayed = nullptr)
 {
     float *w = c->arena + off, *wu = w + c->total, *wd = w + 2 * c->total;
-    if (clip) {
+    if (r.decay != 0.f) {
+        if (!decayed) throw cn_error(CN_ERR_STATE, "launch_flat: weight decay needs a layer's range");
+        if (r.adam) launch_adam_decay(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), decay_ld(lr, r.decay), *decayed, clip, done);
+        else        launch_sgd_decay(c->stream, w, wu, wd, n, lr, r.mom, decay_ld(lr, r.decay), *decayed, clip, done);
+    }
+    else if (clip) {
         if (r.adam) launch_adam_clip(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), clip, done);
         else        launch_sgd_clip(c->stream, w, wu, wd, n, lr, r.mom, clip, done);
     }
@@ -2794,9 +2818,10 @@ static const ClipRecord *clip_record(cn_ctx *c)
 }
 
 // cn_ctx_arm_update / cn_ctx_arm_adam
-static void arm(cn_ctx *ctx, const UpdateRule &r, const char *fn)
+static void arm(cn_ctx *ctx, UpdateRule r, const char *fn)
 {
     enter(ctx);
+    r.decay = ctx->decay;              // (the armed step records the decay in force now)
     refuse_swapped(ctx, fn);
     if (r.adam) check_adam_args(fn, r);
     for (cn_layer *l : ctx->layers)
@@ -2826,10 +2851,11 @@ int cn_ctx_arm_adam(cn_ctx *ctx, float learning_rate, float beta1, float beta2, 
 }
 
 // cn_sgd_update / cn_adam_update: r.lr is the layer's effective rate (the caller applies the layer's own)
-static void update_layer(cn_layer *layer, const UpdateRule &r, const char *fn)
+static void update_layer(cn_layer *layer, UpdateRule r, const char *fn)
 {
     cn_ctx *c = layer->ctx;
     enter(c);
+    r.decay = c->decay;
     if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, std::string(fn) + ": layer has no weights");
     begin_update(c, r, fn);
     if (layer->updated) {            // armed: this layer's step ran behind its gradient; nothing left but the wait above
@@ -2847,12 +2873,14 @@ static void update_layer(cn_layer *layer, const UpdateRule &r, const char *fn)
         armed.lr = layer_lr(layer, c->arm);
         if (!same_rule(r, armed)) throw_rule_mismatch(fn, r.adam);
         layer->deferred = false;
+        r.decay = c->arm.decay;
         bool any = false;
         for (cn_layer *o : c->layers) any = any || o->deferred;
         if (!any) c->arm_deferred = false;
     }
     Timed tm(c, KC_OTHER);
-    launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr, clip_record(c));
+    const DecayRanges rg = decay_ranges(layer);
+    launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr, clip_record(c), nullptr, &rg);
     layer->dirty = true; layer->noisy_ready = false;
 }
 
@@ -2917,6 +2945,25 @@ int cn_ctx_set_grad_clip(cn_ctx *ctx, float max_norm)
         if (max_norm != ctx->clip_max) ctx->clip_valid = false;       // (the record's factor belongs to the bound it was formed with)
         ctx->clip_max = max_norm;
     });
+}
+
+// ---- weight decay (include/currennt_hip.h, section Weight decay) ----
+int cn_ctx_set_weight_decay(cn_ctx *ctx, float decay)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_weight_decay: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!(decay >= 0.f) || std::isinf(decay)) throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_set_weight_decay: decay must be finite and >= 0 (0 = off)");
+        bool pending = ctx->armed || ctx->arm_deferred;
+        for (cn_layer *l : ctx->layers) pending = pending || l->updated;
+        if (pending) throw cn_error(CN_ERR_STATE, "cn_ctx_set_weight_decay: an armed update is pending (complete it with the *_update* call first)");
+        ctx->decay = decay;
+    });
+}
+int cn_ctx_get_weight_decay(const cn_ctx *ctx, float *decay)
+{
+    if (!ctx || !decay) { g_last_error = "cn_ctx_get_weight_decay: ctx or decay is NULL"; return CN_ERR_BAD_ARG; }
+    *decay = ctx->decay;
+    return CN_OK;
 }
 
 int cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, int64_t *updates, int64_t *clipped, int64_t *skipped,
@@ -3178,9 +3225,10 @@ int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count)
 // (in an unnamed namespace inside extern "C", as it has been: hipcc gives such a function an unmangled GLOBAL symbol, so the
 // library's dynamic symbol table lists "update_all" -- nobody declares it; dropping it is a change of the export list of its own)
 namespace {
-void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
+void update_all(cn_ctx *ctx, UpdateRule r, const char *fn)
 {
     enter(ctx);
+    r.decay = (ctx->armed || ctx->arm_deferred) ? ctx->arm.decay : ctx->decay;
     begin_update(ctx, r, fn);
     // armed: layers whose step ran behind their gradient are complete (the wait above orders this stream behind them); what
     // follows handles the rest (none, normally)
@@ -3219,22 +3267,27 @@ void update_all(cn_ctx *ctx, const UpdateRule &r, const char *fn)
         cn_layer *last = nullptr;
         for (cn_layer *l : ctx->layers)
             if (l->trainable) { own_rates = own_rates || l->own_lr >= 0.f; last = l; }
-        if (!own_rates) launch_flat(ctx, r, 0, ctx->total, r.lr, clip, attach ? ctx->ev_sgd : nullptr);
-        else            // a layer with a "learningRate" of its own: one launch per layer
+        if (!own_rates && r.decay == 0.f) launch_flat(ctx, r, 0, ctx->total, r.lr, clip, attach ? ctx->ev_sgd : nullptr);
+        else            // a layer with a "learningRate" of its own, or weight decay (a layer's blocks): one launch per layer
             for (cn_layer *l : ctx->layers)
-                if (l->trainable) launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), clip, (attach && l == last) ? ctx->ev_sgd : nullptr);
+                if (l->trainable) {
+                    const DecayRanges rg = decay_ranges(l);
+                    launch_flat(ctx, r, l->woff, (size_t)l->nw, layer_lr(l, r), clip, (attach && l == last) ? ctx->ev_sgd : nullptr, &rg);
+                }
     }
     for (cn_layer *l : ctx->layers) if (l->trainable) { l->dirty = true; l->noisy_ready = false; }
     if (grouped) {
         PackGroup grp{};
         PackAdam ad{};
+        PackDecayArgs dk{};
         for (cn_layer *l : ctx->layers) {
             if (!l->trainable) continue;
             add_pack_item(grp, l);
-            if (fused) set_pack_update(grp, ad, 1, r, l);
+            if (fused) set_pack_update(grp, ad, dk, 1, r, l);
             l->dirty = false; l->pack_pending = false;
         }
-        launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr, fused ? clip : nullptr);
+        launch_pack_group(ctx->stream, ctx->f32, grp, nullptr, (fused && r.adam) ? &ad : nullptr, fused ? clip : nullptr,
+                          (fused && r.decay != 0.f) ? &dk : nullptr);
     } else if (ctx->overlap) {
         // (more layers than one group launch takes: the first trainable layer's copy on this stream, its forward pass
         // is next; the others on the side stream, each layer's forward pass waits for them in repack())

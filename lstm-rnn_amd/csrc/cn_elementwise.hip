@@ -16,6 +16,7 @@
 #include "cn_philox_device.h"
 
 #include <float.h>
+#include <type_traits>
 
 namespace cn {
 
@@ -101,6 +102,67 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
 // Clipping on (UPD = 4, include/currennt_hip.h, section Gradient clipping): an update rule with the record of grad_norm_kernel in
 // front of it.  Types and an UPD of their own: the forms without it are instantiated as before.
 template <class B> struct PackClip : B { float scale; int state; };
+// Weight decay on (include/currennt_hip.h, section Weight decay): an update rule with the layer's ld = lr * decay in front of it.
+// A type of its own again, around the plain rule or the clipped one: the forms without it are instantiated as before.  Which block
+// an index lies in is known where the pack bodies fetch it (DEC of pack_fetch): the input and recurrent weights decay, the bias
+// and peephole weights do not and take the plain step.
+template <class B> struct PackDecay : B { float ld; };
+template <class U> struct pack_decays { static constexpr bool value = false; };
+template <class B> struct pack_decays<PackDecay<B>> { static constexpr bool value = true; };
+// w0 = w - ld * w, two operations rounded on their own; then the family's step from w0.
+// (hipcc's __fmul_rn / __fsub_rn are the plain operators, and the compiler's default lets the backend contract a product into the
+// sum that reads it: it made one v_fma_f32 of w - ld * w.  The decay forms state their arithmetic under "contract(off)", which
+// the default -- fast-honor-pragmas -- honours; the family's step is restated here for the same reason, operation by operation
+// as apply_update and adam_step state it.)
+__device__ __forceinline__ float decayed(float w, float ld)
+{
+#pragma clang fp contract(off)
+    const float p = ld * w;
+    return w - p;
+}
+__device__ __forceinline__ float sgd_delta_exact(float mom, float d, float lr, float g)
+{
+#pragma clang fp contract(off)
+    const float a = mom * d, b = lr * g;
+    return a - b;
+}
+__device__ __forceinline__ float sum_exact(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float adam_step_exact(float w, float g, float *m, float *v, float b1, float omb1, float b2, float omb2, float alpha_t, float eps_t)
+{
+#pragma clang fp contract(off)
+    const float m1 = b1 * *m, m2 = omb1 * g;
+    const float mn = m1 + m2;
+    const float gg = g * g;
+    const float v1 = b2 * *v, v2 = omb2 * gg;
+    const float vn = v1 + v2;
+    *m = mn; *v = vn;
+    const float num = alpha_t * mn;
+    const float den = sqrtf(vn) + eps_t;
+    const float q = __fdiv_rn(num, den);
+    return w - q;
+}
+// (DEC: the entry decays; an exempt entry takes the same restated step from w itself)
+template <bool DEC> __device__ __forceinline__ float apply_update_decay(const PackUpd &u, long fi, float g, float ld)
+{
+    const float dl = sgd_delta_exact(u.mom, u.wd[fi], u.lr, g);
+    u.wd[fi] = dl;
+    const float w = u.w_rw[fi];
+    return sum_exact(DEC ? decayed(w, ld) : w, dl);
+}
+template <bool DEC> __device__ __forceinline__ float apply_update_decay(const PackUpdAdam &u, long fi, float g, float ld)
+{
+    const float w = u.w_rw[fi];
+    return adam_step_exact(DEC ? decayed(w, ld) : w, g, u.wd + fi, u.v + fi, u.mom, u.omb1, u.b2, u.omb2, u.lr, u.eps_t);
+}
+template <bool DEC, class U> __device__ __forceinline__ float pack_apply(const U &u, long fi, float g)
+{
+    if constexpr (pack_decays<U>::value) return apply_update_decay<DEC>(u, fi, g, u.ld);
+    else return apply_update(u, fi, g);
+}
 // Weight noise (UPD = 5, include/currennt_hip.h, section Weight noise): the fetch returns w + n(fi), and the bodies write the
 // copies a backward pass reads only.  A type and an UPD of their own again.
 // (philox4x32_10 and the Box-Muller step gauss_noise: cn_philox_device.h)
@@ -110,7 +172,8 @@ __device__ __forceinline__ float weight_noise(const PackNoiseKey &u, long k)
     const uint4 w = philox4x32_10(make_uint4((uint32_t)(k >> 2), 0u, u.pass_lo, u.pass_hi), u.k0, u.k1);
     return gauss_noise(w, k, u.sigma);
 }
-template <int UPD, class U>
+// (DEC: the index lies in a block that decays -- it matters to the PackDecay forms only)
+template <int UPD, bool DEC = true, class U>
 __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
                                             const PackFold *fold = nullptr, long foff = 0)
 {
@@ -119,7 +182,7 @@ __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi,
         if (u.state == CLIP_SKIP) return u.w_rw[fi];          // (the operand copies are still written, from the unchanged weight)
         float g = u.wu[fi];
         if (u.state == CLIP_SCALE) g = __fmul_rn(u.scale, g);
-        const float v = apply_update(u, fi, g);
+        const float v = pack_apply<DEC>(u, fi, g);
         u.w_rw[fi] = v;
         return v;
     } else if constexpr (UPD != 0) {
@@ -131,7 +194,7 @@ __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi,
             u.wu_rw[fi] = g;
         } else if constexpr (UPD == 2) { g = *gp; *gp = 0.f; if (gscale != 1.0f) g = __fmul_rn(gscale, g); u.wu_rw[fi] = g; }
         else g = u.wu[fi];
-        const float v = apply_update(u, fi, g);
+        const float v = pack_apply<DEC>(u, fi, g);
         u.w_rw[fi] = v;
         return v;
     } else return w[fi];
@@ -175,11 +238,11 @@ __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, co
             if constexpr (UPD == 5) continue;                 // (no backward pass reads the bias weights)
             const int k = idx - nIn - nRec;
             const int d = k / (4 * Hp), j = (k / 4) % Hp, gg = k % 4;
-            bias_p[k] = (j < H) ? bias * pack_fetch<UPD>(w, upd, 4L * L * P + gg * L + d * H + j, pg.g_bias + k, 1.0f, &pg.f_bias, k) : 0.f;   // LstmLayer.cu:97-100
+            bias_p[k] = (j < H) ? bias * pack_fetch<UPD, false>(w, upd, 4L * L * P + gg * L + d * H + j, pg.g_bias + k, 1.0f, &pg.f_bias, k) : 0.f;   // LstmLayer.cu:97-100
         } else {
             const int k = idx - nIn - nRec - nB;
             const int d = k / (3 * Hp), pp = (k / Hp) % 3, j = k % Hp;
-            peep_p[k] = (j < H) ? pack_fetch<UPD>(w, upd, 4L * L * (P + 1) + 4L * L * H + pp * L + d * H + j, pg.g_peep + k, 1.0f,
+            peep_p[k] = (j < H) ? pack_fetch<UPD, false>(w, upd, 4L * L * (P + 1) + 4L * L * H + pp * L + d * H + j, pg.g_peep + k, 1.0f,
                                                   &pg.f_bias, nB + k) : 0.f;      // (a slot: the bias sums, then the peephole sums)
         }
     }
@@ -260,7 +323,7 @@ __device__ __forceinline__ void ff_pack_body(const FfGeom &g, float bias, const 
         } else {
             if constexpr (UPD == 5) continue;
             const int j = idx - nW;
-            bias_p[j] = (j < g.L) ? bias * pack_fetch<UPD>(w, upd, (long)g.L * g.P + j, pg.g_bias + j, bias, &pg.f_bias, j) : 0.f;            // FeedForwardLayer.cu:59
+            bias_p[j] = (j < g.L) ? bias * pack_fetch<UPD, false>(w, upd, (long)g.L * g.P + j, pg.g_bias + j, bias, &pg.f_bias, j) : 0.f;            // FeedForwardLayer.cu:59
         }
     }
 }
@@ -352,6 +415,48 @@ __global__ void pack_group_clip_kernel(PackGroup grp, PackAdam ad, const ClipRec
         else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
     }
 }
+// ... and of every update mode with weight decay on (CLIP: mode 1 behind the record, as pack_group_clip_kernel): item i's
+// ld = lr_layer * decay comes in an argument of its own, so that PackItem and the instantiations above stay as they are
+template <bool F32, bool ADAM, bool CLIP>
+__global__ void pack_group_decay_kernel(PackGroup grp, PackAdam ad, PackDecayArgs dk, const ClipRecord *rec)
+{
+    int i = 0;
+    float ld = dk.ld[0];
+    float *v = ad.v[0];
+#pragma unroll
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) { i = k; ld = dk.ld[k]; v = ad.v[k]; }
+    const PackItem it = grp.item[i];
+    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
+    const PackUpd base{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
+    using Rule = typename std::conditional<ADAM, PackUpdAdam, PackUpd>::type;
+    Rule rule;
+    if constexpr (ADAM) rule = PackUpdAdam{base, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t}; else rule = base;
+    if constexpr (CLIP) {
+        const PackDecay<PackClip<Rule>> upd{{rule, rec->scale, rec->state}, ld};
+        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
+        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
+    } else {
+        const PackDecay<Rule> upd{rule, ld};
+        if (it.update == 2) {
+            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}};
+            if (it.lstm) lstm_pack_body<F32, 2>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
+            else         ff_pack_body<F32, 2>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
+        } else if (it.update == 3) {
+            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias};
+            if (it.lstm) lstm_pack_body<F32, 3>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
+            else         ff_pack_body<F32, 3>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
+        } else {
+            if (it.lstm) lstm_pack_body<F32, 1>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
+            else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
+        }
+    }
+}
+template <bool F32, bool ADAM>
+static void launch_pack_group_decay(hipStream_t s, int blocks, hipEvent_t done, const PackGroup &grp, const PackAdam &a, const PackDecayArgs &dk, const ClipRecord *clip)
+{
+    if (clip) hipExtLaunchKernelGGL((pack_group_decay_kernel<F32, ADAM, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, dk, clip);
+    else      hipExtLaunchKernelGGL((pack_group_decay_kernel<F32, ADAM, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, dk, clip);
+}
 // the grid of a grouped launch: item i's workgroups are [grp.first[i], grp.first[i + 1]), one thread per packed entry up to 1024 groups
 static int pack_group_blocks(PackGroup &grp)
 {
@@ -365,10 +470,17 @@ static int pack_group_blocks(PackGroup &grp)
     }
     return blocks;
 }
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip)
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip, const PackDecayArgs *decay)
 {
     const int blocks = pack_group_blocks(grp);
     if (blocks == 0) return;
+    if (decay) {
+        const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
+        const PackAdam a = ad ? *adam : PackAdam{};
+        if (ad) { if (f32) launch_pack_group_decay<true, true>(s, blocks, done, grp, a, *decay, clip); else launch_pack_group_decay<false, true>(s, blocks, done, grp, a, *decay, clip); }
+        else    { if (f32) launch_pack_group_decay<true, false>(s, blocks, done, grp, a, *decay, clip); else launch_pack_group_decay<false, false>(s, blocks, done, grp, a, *decay, clip); }
+        return;
+    }
     if (clip) {
         const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
         const PackAdam a = ad ? *adam : PackAdam{};
@@ -1774,6 +1886,54 @@ void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float 
     if (n == 0) return;
     int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipExtLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, rec);
+}
+
+// sgd_kernel / adam_kernel with weight decay on (include/currennt_hip.h, section Weight decay; CLIP: behind the record too) over
+// ONE layer's flat range: rg names the two runs of it that decay, relative to its start.  Kernels of their own once more.
+__device__ __forceinline__ bool decays(const DecayRanges &rg, size_t i) { return i < rg.a1 || (i >= rg.b0 && i < rg.b1); }
+template <bool CLIP>
+__global__ void sgd_decay_kernel(float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, DecayRanges rg, const ClipRecord *rec)
+{
+    int state = CLIP_NONE; float scale = 1.0f;
+    if constexpr (CLIP) { state = rec->state; scale = rec->scale; if (state == CLIP_SKIP) return; }
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float g = wu[i];
+        if constexpr (CLIP) { if (state == CLIP_SCALE) g = __fmul_rn(scale, g); }
+        const float dl = sgd_delta_exact(mom, wd[i], lr, g);
+        wd[i] = dl;
+        float w0 = w[i];
+        if (decays(rg, i)) w0 = decayed(w0, ld);
+        w[i] = sum_exact(w0, dl);
+    }
+}
+template <bool CLIP>
+__global__ void adam_decay_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a, float ld, DecayRanges rg, const ClipRecord *rec)
+{
+    int state = CLIP_NONE; float scale = 1.0f;
+    if constexpr (CLIP) { state = rec->state; scale = rec->scale; if (state == CLIP_SKIP) return; }
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float g = wu[i];
+        if constexpr (CLIP) { if (state == CLIP_SCALE) g = __fmul_rn(scale, g); }
+        float w0 = w[i];
+        if (decays(rg, i)) w0 = decayed(w0, ld);
+        w[i] = adam_step_exact(w0, g, m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
+    }
+}
+void launch_sgd_decay(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, const DecayRanges &rg,
+                      const ClipRecord *rec, hipEvent_t done)
+{
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    if (rec) hipExtLaunchKernelGGL(sgd_decay_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, ld, rg, rec);
+    else     hipExtLaunchKernelGGL(sgd_decay_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, ld, rg, rec);
+}
+void launch_adam_decay(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, float ld, const DecayRanges &rg,
+                       const ClipRecord *rec, hipEvent_t done)
+{
+    if (n == 0) return;
+    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    if (rec) hipExtLaunchKernelGGL(adam_decay_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, ld, rg, rec);
+    else     hipExtLaunchKernelGGL(adam_decay_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, ld, rg, rec);
 }
 
 }  // namespace cn

@@ -258,8 +258,12 @@ struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
 // adam: required when the group's items say PACK_OPT_ADAM (all items of a group name the same optimizer)
 // clip (nullable; update == 1 items only): the record of grad_norm_kernel -- kernels of their own again (pack_group_clip_kernel),
 // the instantiations without it keep their code
+// decay (nullable; items with an update): weight decay is on (include/currennt_hip.h, section Weight decay) and item i's
+// ld = (float)(lr_layer * decay) -- kernels of their own once more (pack_group_decay_kernel), for every update mode and for clip
 struct ClipRecord;
-void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr, const ClipRecord *clip = nullptr);
+struct PackDecayArgs { float ld[PACK_GROUP_MAX]; };
+void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr, const ClipRecord *clip = nullptr,
+                       const PackDecayArgs *decay = nullptr);
 // Weight noise (include/currennt_hip.h, section Weight noise): the group's items name the NOISY copies in WinT / WrecT / peep_p
 // (the launch writes nothing else) and the clean flat weights in w; item i's key word 0 is k0[i] = seed_lo + ordinal, the other
 // key word (seed_hi ^ "nois"), counter words 2 and 3 and sigma are the group's.  Kernels of their own (pack_group_noise_kernel).
@@ -450,6 +454,15 @@ void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, C
 // launch_sgd / launch_adam with the record in front of the rule: g' = scale * g on CLIP_SCALE, nothing touched on CLIP_SKIP
 void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done = nullptr);
 void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done = nullptr);
+
+// ---- weight decay (include/currennt_hip.h, section Weight decay) ----
+// launch_sgd / launch_adam over ONE layer's flat range [0, n) with w0 = w - ld * w in front of the rule for the entries of
+// [0, a1) and [b0, b1) (the input weights and an LSTM layer's recurrent weights); rec (nullable): the clipping record as above
+struct DecayRanges { size_t a1, b0, b1; };
+void launch_sgd_decay(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, const DecayRanges &rg,
+                      const ClipRecord *rec = nullptr, hipEvent_t done = nullptr);
+void launch_adam_decay(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, float ld, const DecayRanges &rg,
+                       const ClipRecord *rec = nullptr, hipEvent_t done = nullptr);
 
 // ---- weight averaging (include/currennt_hip.h, section Weight averaging; cn_average.hip) ----
 // avg[0 .. n) = copy ? w : avg + omd * (w - avg), every operation an fp32 operation rounded on its own (n a multiple of 4, both

@@ -49,6 +49,12 @@ const char *Configuration::usage()
            "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
            "            --max_grad_norm X (clip every update's gradient to this global L2 norm; a step with a non-finite gradient is\n"
            "                      skipped; default 0 = off)\n"
+           "            --weight_decay X (decoupled weight decay, AdamW-style, for both optimizers: every input and recurrent weight\n"
+           "                      shrinks by learning rate * X of itself per update; biases and peepholes do not; default 0 = off)\n"
+           "            --learning_rate_warmup_updates N (update k <= N runs at k / N of the learning rate; default 0 = off)\n"
+           "            --learning_rate_decay F --learning_rate_decay_patience E --learning_rate_min M (after E epochs in a row\n"
+           "                      without a new lowest validation error -- training error without a validation set -- the rate is\n"
+           "                      multiplied by F, not below M; 0 < F <= 1, default 1 = off; E >= 1, default 1; M >= 0, default 0)\n"
            "            --weight_average_decay D (keep an exponential moving average of the weights, one step behind every update;\n"
            "                      validation, early stopping, trained_network.jsn and .best.jsn use it; 0 < D < 1, default 0 = off)\n"
            "            --weight_average_warmup B (step k >= 2 averages with min(D, k / (k + 9)); default true)\n"
@@ -111,6 +117,29 @@ void Configuration::apply(const std::string &key, const std::string &v)
         m_maxGradNorm = (real_t)atof(v.c_str());
         if (!(m_maxGradNorm >= 0) || std::isinf(m_maxGradNorm))
             throw std::runtime_error("Error while parsing the command line and/or options file: --max_grad_norm must be finite and >= 0 (0 = off)");
+    }
+    else if (key == "weight_decay") {
+        m_weightDecay = (real_t)atof(v.c_str());
+        if (!(m_weightDecay >= 0) || std::isinf(m_weightDecay))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --weight_decay must be finite and >= 0 (0 = off)");
+    }
+    else if (key == "learning_rate_warmup_updates") {
+        m_lrWarmupUpdates = atoll(v.c_str());
+        if (m_lrWarmupUpdates < 0) throw std::runtime_error("Error while parsing the command line and/or options file: --learning_rate_warmup_updates must be >= 0");
+    }
+    else if (key == "learning_rate_decay") {
+        m_lrDecay = atof(v.c_str());
+        if (!(m_lrDecay > 0 && m_lrDecay <= 1))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --learning_rate_decay must be in (0, 1] (1 = off)");
+    }
+    else if (key == "learning_rate_decay_patience") {
+        m_lrDecayPatience = atoi(v.c_str());
+        if (m_lrDecayPatience < 1) throw std::runtime_error("Error while parsing the command line and/or options file: --learning_rate_decay_patience must be >= 1");
+    }
+    else if (key == "learning_rate_min") {
+        m_lrMin = atof(v.c_str());
+        if (!(m_lrMin >= 0) || std::isinf(m_lrMin))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --learning_rate_min must be finite and >= 0");
     }
     else if (key == "weight_average_decay") {
         m_weightAverageDecay = (real_t)atof(v.c_str());

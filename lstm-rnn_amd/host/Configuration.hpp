@@ -42,6 +42,12 @@ public:
     // --max_grad_norm: bound on the global L2 norm of an update's gradient (include/currennt_hip.h, section Gradient clipping;
     // no counterpart in the reference); 0 = off
     real_t maxGradNorm() const { return m_maxGradNorm; }
+    real_t weightDecay() const { return m_weightDecay; }
+    long long learningRateWarmupUpdates() const { return m_lrWarmupUpdates; }
+    double learningRateDecay() const { return m_lrDecay; }
+    int learningRateDecayPatience() const { return m_lrDecayPatience; }
+    double learningRateMin() const { return m_lrMin; }
+    bool learningRateSchedule() const { return m_lrWarmupUpdates > 0 || m_lrDecay < 1.0; }
     // --weight_average_decay: decay of the exponential moving average of the weights that validation, early stopping and the saved
     // networks use (include/currennt_hip.h, section Weight averaging; no counterpart in the reference); 0 = off.
     // --weight_average_warmup: step k >= 2 uses min(decay, k / (k + 9))
@@ -128,6 +134,10 @@ private:
            m_testFraction = 1, m_weightsUniformMin = -0.1f, m_weightsUniformMax = 0.1f, m_weightsNormalSigma = 0.1f, m_weightsNormalMean = 0;
     real_t m_adamBeta1 = 0.9f, m_adamBeta2 = 0.999f, m_adamEpsilon = 1e-8f;
     real_t m_maxGradNorm = 0;
+    real_t m_weightDecay = 0;
+    long long m_lrWarmupUpdates = 0;
+    double m_lrDecay = 1.0, m_lrMin = 0.0;
+    int m_lrDecayPatience = 1;
     real_t m_weightAverageDecay = 0;
     bool m_weightAverageWarmup = true;
     std::string m_optimizer = "steepest_descent";

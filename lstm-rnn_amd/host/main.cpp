@@ -395,10 +395,18 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 printf("Momentum:                  %g\n\n", (double)config.momentum());
             }
             if (config.maxGradNorm() > 0) printf("Max. gradient norm:        %g\n\n", (double)config.maxGradNorm());
+            if (config.weightDecay() > 0) printf("Weight decay:              %g (decoupled; input and recurrent weights)\n\n", (double)config.weightDecay());
+            if (config.learningRateSchedule())
+                printf("Learning rate schedule:    warm-up %lld updates, decay %g after %d epochs without a new lowest error, min %g\n\n",
+                       config.learningRateWarmupUpdates(), config.learningRateDecay(), config.learningRateDecayPatience(), config.learningRateMin());
             if (config.weightNoiseOnDevice()) printf("Weight noise:              sigma %g, generated on the device\n\n", (double)config.weightNoiseSigma());
             if (config.weightAverageDecay() > 0)
                 printf("Weight averaging:          decay %g, warm-up %s\n\n", (double)config.weightAverageDecay(), config.weightAverageWarmup() ? "on" : "off");
             optimizer.setMaxGradNorm(config.maxGradNorm());
+            if (config.weightDecay() > 0) optimizer.setWeightDecay(config.weightDecay());
+            optimizer.setLearningRateSchedule(optimizers::LearningRateSchedule(config.learningRateWarmupUpdates(), config.learningRateDecay(),
+                                                                               config.learningRateDecayPatience(), config.learningRateMin(),
+                                                                               (double)config.learningRate()));
             optimizer.setWeightAverage(config.weightAverageDecay(), config.weightAverageWarmup());
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
             // --weight_noise_on_device: seed = --random_seed on every rank (no rank offset: the replicas stay identical)
@@ -417,6 +425,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 printf("done.\n\n");
                 if (optimizer.weightAverageStartsFresh())
                     printf("Weight averaging: the autosave file holds no average; it starts with the next update.\n\n");
+                if (optimizer.learningRateScheduleStartsFresh())
+                    printf("Learning rate schedule: the autosave file holds no schedule state; it starts fresh.\n\n");
             }
 
             printf("Starting training...\n\n");
@@ -468,6 +478,11 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 if (config.maxGradNorm() > 0) {
                     const optimizers::Optimizer::ClipStats cs = optimizer.takeClipStats();
                     printf("         gradient norm: max %g, clipped %lld, skipped %lld of %lld updates\n", (double)cs.maxNormSeen, cs.clipped, cs.skipped, cs.updates);
+                }
+                // the learning-rate schedule: the rate the next update would use (one line behind the row, like clipping's)
+                if (config.learningRateSchedule()) {
+                    const optimizers::LearningRateSchedule &sch = optimizer.learningRateSchedule();
+                    printf("         learning rate: %g (scale %g, %lld updates)\n", (double)sch.rate(), sch.state().scale, (long long)sch.state().updates);
                 }
                 if (config.autosave() && root) saveState(config, neuralNetwork, optimizer, infoRows);  // main.cpp:275-277
             }

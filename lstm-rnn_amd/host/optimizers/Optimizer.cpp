@@ -1,6 +1,8 @@
 #include "Optimizer.hpp"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <limits>
 #include <vector>
 
@@ -155,7 +157,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
                     layer->setWeights(noisy);
                 }
             }
-            if (m_hybridOnlineBatch && !hostNoise) _armUpdate();
+            if (m_hybridOnlineBatch && !hostNoise) { _setScheduledLayerRates(); _armUpdate(); }
             m_neuralNetwork.computeBackwardPass();
             if (hostNoise) {
                 hipCheck(cn_ctx_join(m_neuralNetwork.context()), m_neuralNetwork.context());   // gradient GEMMs still read the noisy operands
@@ -207,6 +209,11 @@ bool Optimizer::train()
     _scoreValidationSet();
     if (_dueThisEpoch(m_testSet, m_testEvery)) m_curTestError = _processDataSet(m_testSet, false, &m_curTestClassError);
     if (swapped) swapWeightAverage();
+    // learning-rate schedule: the epoch's monitored error, beside early stopping (which is untouched)
+    if (m_schedule.on()) {
+        if (m_validationSet.empty()) m_schedule.epochEnd((double)m_curTrainingError);
+        else if (_dueThisEpoch(m_validationSet, m_validateEvery)) m_schedule.epochEnd((double)m_curValidationError);
+    }
     if (_shouldStop()) {
         _restoreWeights();          // training ends on the best weights seen, not on the last ones
         m_finished = true;
@@ -218,12 +225,25 @@ bool Optimizer::train()
 // device noise: every path to an update comes through here)
 void Optimizer::_completeUpdate()
 {
+    _setScheduledLayerRates();          // (the values the arming call named, if one came: the count below is what moves them)
     _updateWeights();
+    m_schedule.countUpdate();
     if (!(m_avgDecay > 0)) return;
     const int64_t k = ++m_avgSteps;
     double decay = (double)m_avgDecay;
     if (m_avgWarmup && k >= 2) decay = std::min(decay, (double)k / ((double)k + 9.0));
     hipCheck(cn_ctx_average_weights(m_neuralNetwork.context(), (float)decay), m_neuralNetwork.context());
+}
+
+void Optimizer::_setScheduledLayerRates()
+{
+    if (!m_schedule.on()) return;
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (layer && layer->learningRate() >= 0.0)
+            hipCheck(cn_layer_set_learning_rate(layer->handle(), m_schedule.scaled(layer->learningRate())), m_neuralNetwork.context());
+    }
 }
 
 bool Optimizer::swapWeightAverage()
@@ -329,6 +349,16 @@ void Optimizer::exportState(json::Value *jsonDoc) const
     for (const IntField &f : StateTable::ints()) jsonDoc->addMember(f.key, json::Value(this->*f.member));
     for (const RealField &f : StateTable::reals()) jsonDoc->addMember(f.key, json::Value((double)(this->*f.member)));
     _exportWeights(jsonDoc, "optimizer_best_weights", m_bestWeights);
+    // learning-rate schedule: its four state members (the two doubles as text with 17 digits: the file's numbers keep 9)
+    if (m_schedule.on()) {
+        const LearningRateSchedule::State &st = m_schedule.state();
+        char scale[40], lowest[40];
+        snprintf(scale, sizeof(scale), "%.17g", st.scale); snprintf(lowest, sizeof(lowest), "%.17g", st.lowest);
+        jsonDoc->addMember("optimizer_updates", json::Value((double)st.updates));
+        jsonDoc->addMember("learning_rate_scale", json::Value(std::string(scale)));
+        jsonDoc->addMember("learning_rate_bad_epochs", json::Value(st.bad));
+        jsonDoc->addMember("learning_rate_lowest_error", json::Value(std::string(lowest)));
+    }
     // weight averaging: the average (laid out like optimizer_best_weights) and the number of averaging steps taken
     if (m_avgDecay > 0) {
         const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
@@ -349,6 +379,18 @@ void Optimizer::importState(const json::Value &jsonDoc)
     for (const IntField &f : StateTable::ints()) this->*f.member = jsonDoc[f.key].getInt();
     for (const RealField &f : StateTable::reals()) this->*f.member = (real_t)jsonDoc[f.key].getDouble();
     _importWeights(jsonDoc, "optimizer_best_weights", &m_bestWeights);
+    // learning-rate schedule on, and the file has no state of it (it was written without a schedule): the schedule starts fresh
+    if (m_schedule.on()) {
+        if (jsonDoc.hasMember("optimizer_updates") && jsonDoc.hasMember("learning_rate_scale") && jsonDoc.hasMember("learning_rate_bad_epochs") &&
+            jsonDoc.hasMember("learning_rate_lowest_error")) {
+            LearningRateSchedule::State st;
+            st.updates = (int64_t)jsonDoc["optimizer_updates"].getDouble();
+            st.scale = strtod(jsonDoc["learning_rate_scale"].getString().c_str(), nullptr);
+            st.bad = jsonDoc["learning_rate_bad_epochs"].getInt();
+            st.lowest = strtod(jsonDoc["learning_rate_lowest_error"].getString().c_str(), nullptr);
+            m_schedule.setState(st);
+        } else m_scheduleStartsFresh = true;
+    }
     // weight averaging off: an average in the file is ignored.  On, and the file has none (it was written without averaging): the
     // average starts fresh at the next update
     if (!(m_avgDecay > 0)) return;
@@ -416,7 +458,7 @@ SteepestDescentOptimizer::SteepestDescentOptimizer(NeuralNetwork &neuralNetwork,
 void SteepestDescentOptimizer::_armUpdate()
 {
     NeuralNetwork &nn = _neuralNetwork();
-    hipCheck(cn_ctx_arm_update(nn.context(), m_learningRate, m_momentum), nn.context());
+    hipCheck(cn_ctx_arm_update(nn.context(), _scheduledRate(m_learningRate), m_momentum), nn.context());
 }
 
 void SteepestDescentOptimizer::_updateWeights()
@@ -434,8 +476,14 @@ void SteepestDescentOptimizer::_updateWeights()
         if (!layer) continue;
         real_t lr = m_learningRate;
         if (layer->learningRate() >= 0.0) lr = layer->learningRate();        // SteepestDescentOptimizer.cu:78-80
+        lr = _scheduledRate(lr);
         hipCheck(cn_sgd_update(layer->handle(), lr, m_momentum), nn.context());
     }
+}
+
+void Optimizer::setWeightDecay(real_t decay)
+{
+    hipCheck(cn_ctx_set_weight_decay(m_neuralNetwork.context(), decay), m_neuralNetwork.context());
 }
 
 void Optimizer::setMaxGradNorm(real_t maxNorm)
@@ -463,7 +511,7 @@ void AdamOptimizer::_armUpdate()
     NeuralNetwork &nn = _neuralNetwork();
     ++m_step;
     m_armed = true;
-    hipCheck(cn_ctx_arm_adam(nn.context(), m_learningRate, m_beta1, m_beta2, m_epsilon, m_step), nn.context());
+    hipCheck(cn_ctx_arm_adam(nn.context(), _scheduledRate(m_learningRate), m_beta1, m_beta2, m_epsilon, m_step), nn.context());
 }
 
 void AdamOptimizer::_updateWeights()
@@ -481,6 +529,7 @@ void AdamOptimizer::_updateWeights()
         if (!layer) continue;
         real_t lr = m_learningRate;
         if (layer->learningRate() >= 0.0) lr = layer->learningRate();        // a layer's own "learningRate" is its Adam step size
+        lr = _scheduledRate(lr);
         hipCheck(cn_adam_update(layer->handle(), lr, m_beta1, m_beta2, m_epsilon, m_step), nn.context());
     }
 }

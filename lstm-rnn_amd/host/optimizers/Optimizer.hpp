@@ -9,6 +9,7 @@
 #include "../Json.hpp"
 #include "../NeuralNetwork.hpp"
 #include "../data_sets/DataSet.hpp"
+#include "LearningRateSchedule.hpp"
 
 namespace currennt_hip {
 namespace optimizers {
@@ -41,6 +42,18 @@ public:
     void setMaxGradNorm(real_t maxNorm);
     struct ClipStats { float maxNormSeen; long long updates, clipped, skipped; };
     ClipStats takeClipStats();
+    // --weight_decay (include/currennt_hip.h, section Weight decay): set once on the context, 0 = off; every update of either
+    // optimizer and either learning mode then decays the input and recurrent weights by lr * decay of themselves
+    void setWeightDecay(real_t decay);
+    // --learning_rate_warmup_updates / --learning_rate_decay / --learning_rate_decay_patience / --learning_rate_min
+    // (LearningRateSchedule.hpp): every update runs at the schedule's factor -- the global rate and a layer's own "learningRate"
+    // alike, the armed call and the completing call of one step at the same value -- and every epoch that has a monitored error
+    // (the validation error where one was computed, the average's under weight averaging; the training error without a
+    // validation set) reports it to the schedule.  The state travels with the autosave.  A schedule that is off changes nothing.
+    void setLearningRateSchedule(const LearningRateSchedule &schedule) { m_schedule = schedule; }
+    const LearningRateSchedule &learningRateSchedule() const { return m_schedule; }
+    // importState found no schedule state in the autosave file although the schedule is on: it starts fresh
+    bool learningRateScheduleStartsFresh() const { return m_scheduleStartsFresh; }
     // --weight_average_decay / --weight_average_warmup (include/currennt_hip.h, section Weight averaging): one averaging step behind
     // every completed update, whichever optimizer and learning mode; step k (from 1, kept here: the library keeps no clock, and it
     // travels with the autosave) uses `decay`, with warm-up min(decay, k / (k + 9)) for k >= 2.  Between an epoch's training pass
@@ -82,6 +95,8 @@ protected:
     void _storeWeights();                                               // :151-158
     void _restoreWeights();                                             // :160-168
     NeuralNetwork &_neuralNetwork() { return m_neuralNetwork; }
+    // `rate` as the update about to be armed or made uses it (the schedule's factor; `rate` itself with the schedule off)
+    real_t _scheduledRate(real_t rate) const { return m_schedule.on() ? m_schedule.scaled(rate) : rate; }
     // (the reference's `_curWeightUpdates()`, the epoch sum of batch learning, lives on the device: cn_ctx_accumulate_updates /
     // cn_ctx_take_accumulated)
 
@@ -106,6 +121,9 @@ private:
     bool m_avgWarmup = true, m_avgStartsFresh = false;
     int64_t m_avgSteps = 0;             // averaging steps taken so far
     void _completeUpdate();             // _updateWeights(), then the averaging step
+    LearningRateSchedule m_schedule;
+    bool m_scheduleStartsFresh = false;
+    void _setScheduledLayerRates();     // schedule on: the layers' own rates at the factor of the update about to be armed or made
 protected:
     static void _exportWeights(json::Value *jsonDoc, const char *arrayName, const std::vector<Hip::real_vector> &weights);   // :106-123
     static void _importWeights(const json::Value &jsonDoc, const char *arrayName, std::vector<Hip::real_vector> *weights);   // :125-149

@@ -624,6 +624,17 @@ class NeuralNetwork:
         return dict(last_norm=np.float32(f[0].value), last_scale=np.float32(f[1].value), updates=n[0].value, clipped=n[1].value,
                     skipped=n[2].value, max_norm_seen=np.float32(f[2].value))
 
+    def set_weight_decay(self, decay):
+        """cn_ctx_set_weight_decay: decoupled weight decay of the updates that follow (include/currennt_hip.h, section Weight
+        decay): every input and recurrent weight shrinks by lr * decay of itself in front of the optimizer's step; 0 turns it off."""
+        B.check(self.lib.cn_ctx_set_weight_decay(self.ctx, float(decay)), self.ctx)
+
+    def weight_decay(self):
+        """cn_ctx_get_weight_decay: the coefficient in force (np.float32)."""
+        d = C.c_float()
+        B.check(self.lib.cn_ctx_get_weight_decay(self.ctx, C.byref(d)), self.ctx)
+        return np.float32(d.value)
+
     def accumulate_updates(self, first):
         """Batch learning (Optimizer.cu:72-85): add this fraction's weightUpdates of all layers to the epoch sum on the device
         (`first`: copy instead of add)."""
