@@ -78,7 +78,10 @@ typedef enum cn_layer_kind {
     /* Connectionist Temporal Classification (Graves et al. 2006; no counterpart in the reference): behind a softmax layer of the
      * same size (>= 2) whose LAST unit is the blank.  It reads nothing from cn_fraction.target_classes / targets (and
      * output_pattern_size is not checked against it); its targets are label sequences, cn_layer_set_label_sequences below. */
-    CN_LAYER_CTC                          /* "ctc"                        csrc/cn_ctc.hip                  */
+    CN_LAYER_CTC,                         /* "ctc"                        csrc/cn_ctc.hip                  */
+    /* Above: the kinds cn_layer_create takes.  Behind them, on this line so that the list of those kinds still ends with ctc: a
+     * hidden layer that splices its predecessor's neighbouring frames (no counterpart in the reference), created by
+     * cn_layer_create_context alone, section Context layers below; csrc/cn_context.hip */ CN_LAYER_CONTEXT
 } cn_layer_kind;
 
 /* which device vector cn_layer_read / cn_layer_device_ptr addresses */
@@ -751,6 +754,52 @@ int  cn_layer_set_residual(cn_layer *layer, int enable);
  * eps not finite or <= 0.  May be called between fractions; takes effect with the layer's next forward pass.  The first enabling
  * call allocates the normalised copy (the size of the preceding layer's operand copy) and one float per row. */
 int  cn_layer_set_layer_norm(cn_layer *layer, int enable, float eps);
+
+/* ---- Context layers (no counterpart in the reference, whose only splicing is that of the input patterns, DataSet.cpp:346-366;
+ *      Waibel et al. 1989, Peddinti et al. 2015: time-delay layers) ----------------------------------------------------------------
+ * A layer of its own kind, CN_LAYER_CONTEXT, without weights: its output for a frame is the preceding layer's output for that
+ * frame and for its neighbours, side by side.  A feedforward_* layer behind it is a time-delay layer.  The preceding layer may be
+ * of any kind that may have a follower: input, lstm, blstm, feedforward_*, softmax, or another context layer.
+ *
+ * Let L, R, D be the three members, B = L + R + 1 and P the preceding layer's size.  The layer's size is B * P,
+ * cn_layer_weight_count is 0, and it is neither trainable nor a post output layer.  len_s is the number of rows of slot s in the
+ * current fraction whose pattern type is not NONE (a sequence lies in its slot from t = 0 without holes).
+ *
+ * Forward.  For a real frame (t, s), block b = c / P and unit u = c % P of column c < B * P:
+ *      ts           = clamp(t + (b - L) * D, 0, len_s - 1)
+ *      out[t][s][c] = x_op[ts][s][u]
+ * x_op: what the preceding layer's followers read -- its sum if it is residual, never a dropped or normalised copy.  Units are the
+ * reference layout's (blstm: the forward units, then the backward ones): whatever padding the preceding layer's rows have, unit u
+ * of block b is column b * P + u of this layer, as cn_layer_read(.., CN_BUF_OUTPUTS, ..) returns it.  The copy is exact in every
+ * precision: operand to operand, nothing is rounded (CN_PREC_BF16 behind a feed-forward layer: that layer's bf16 operand copy).
+ * Rows that are not real frames (dummy frames, pad slots) are zeros: a feed-forward predecessor's act(bias) on dummy rows never
+ * appears.  Edges replicate, as in section Input splicing: a context layer directly behind the input layer produces, bit for bit,
+ * what cn_ctx_set_input_splice {L, R, 1} produces for D = 1.
+ *
+ * Backward.  e is the layer's own outputErrors as its follower wrote them, fp32 in every precision; only real rows are read.  When
+ * the preceding layer takes errors -- it is trainable, or a context layer whose own predecessor takes errors -- its outputErrors
+ * become, for real frame (ts, s) and unit u,
+ *      dx[ts][s][u] = sum over b = 0 .. B-1 (outer, ascending)
+ *                     sum over j = 0 .. len_s-1 (inner, ascending) with clamp(j + (b - L) * D, 0, len_s - 1) == ts
+ *                         e[j][s][b * P + u]
+ * single fp32 additions in exactly that order, starting from +0.0f, without atomics: the result is held to bits and is the same
+ * bits from run to run.  Every other row of the preceding layer's outputErrors of the current fraction, and its pad columns, are
+ * written as 0.  (For interior ts each b contributes at most one j; only the first and the last frame of a sequence collect runs,
+ * of at most max(L, R) * D terms per block.)  Otherwise -- directly behind the input layer, say -- the backward pass does nothing,
+ * and the follower's backward pass hands no error back.
+ *
+ * The follower is any layer that may follow a dense layer: P = B * P of the context layer.  It may drop, normalise, or be residual
+ * (when its size is B * P); it reads, normalises or adds the context layer's output like any other predecessor's.  A post output
+ * layer directly behind a context layer is refused (it needs a trainable preceding layer).  cn_layer_set_dropout,
+ * cn_layer_set_residual, cn_layer_set_layer_norm and the weight entry points refuse a context layer: CN_ERR_BAD_ARG.
+ *
+ * With no context layer in the net the library launches exactly what it launches without this section and allocates nothing for
+ * it. */
+/* 0 <= left, right <= 32 and 1 <= dilation <= 16, else CN_ERR_BAD_ARG.  Allocates the layer's outputs and outputErrors, and with the
+ * context's first such layer a table of one int per slot.  cn_layer_create(ctx, CN_LAYER_CONTEXT, ...) fails with CN_ERR_BAD_ARG and names this function. */
+int  cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, cn_layer **out);
+/* The members of a context layer (any pointer may be NULL); a layer of another kind: CN_ERR_BAD_ARG. */
+int  cn_layer_context(const cn_layer *layer, int *left, int *right, int *dilation);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,9 @@ LAYER_KINDS = {
     "weightedsse": 9, "wf": 10, "ce": 11, "rmse": 12, "binary_classification": 13,
     "ctc": 14,                # csrc/cn_ctc.hip; no counterpart in the reference
 }
+# CN_LAYER_CONTEXT, type string "context" (csrc/cn_context.hip): behind the kinds above in cn_layer_kind and no entry of the table,
+# because cn_layer_create does not take it -- a context layer has members of its own and comes from cn_layer_create_context
+KIND_CONTEXT = 15
 
 # cn_buffer
 BUF = {
@@ -61,6 +64,8 @@ EXPORTS = [
     "cn_layer_upload_weight_average",
     # include/currennt_hip.h, section Weight decay
     "cn_ctx_set_weight_decay", "cn_ctx_get_weight_decay",
+    # include/currennt_hip.h, section Context layers
+    "cn_layer_create_context", "cn_layer_context",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -230,6 +235,8 @@ def load_library():
     L.cn_ctx_weight_average_state.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     L.cn_layer_read_weight_average.argtypes = [vp, vp, C.c_size_t]
     L.cn_layer_upload_weight_average.argtypes = [vp, vp, C.c_size_t]
+    L.cn_layer_create_context.argtypes = [vp, vp, ci, ci, ci, C.POINTER(vp)]
+    L.cn_layer_context.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     _LIB = L
     return L
 

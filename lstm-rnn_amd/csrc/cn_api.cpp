@@ -125,6 +125,10 @@ struct cn_ctx {
     static size_t pat_bytes(size_t maxN, size_t guard) { return ((maxN + 2 * guard + 15) & ~(size_t)15) + (4 + 2 * maxN) * sizeof(int); }
     int *rowmap_of(char *pat_raw) const { return pat_raw ? (int *)(pat_raw + ((pat_maxN + 2 * pat_guard + 15) & ~(size_t)15)) : nullptr; }
     int est_real = 0;                                 // estimate of the current fraction's real frames (dispatch only)
+    // context layers (include/currennt_hip.h, section Context layers): len_s of every slot [PSp], allocated with the first such
+    // layer and formed on the device by the first context layer's pass over a fraction (cx_serial: of load number frac_serial)
+    uint64_t frac_serial = 0, cx_serial = 0;
+    int *cx_len = nullptr;
     int *d_tcls = nullptr;
     float *d_loss = nullptr;      // [2] per-call (error, #correct as int bits)
     float *d_loss_acc = nullptr;  // [2] running sums for cn_loss_accumulate
@@ -288,6 +292,12 @@ struct cn_layer {
     float *res_e = nullptr;               // dense layers: [maxN][Lp] the outputErrors as handed in (launch_ff_delta overwrites err in place)
     bool summed = false;                  // the last forward pass summed ...
     ResArgs res{};                        // ... with this geometry: what its followers read and what its backward pass adds go by the record
+
+    // context layer (include/currennt_hip.h, section Context layers): its members, and the geometry of its last forward pass,
+    // which its backward pass goes by
+    bool context = false;
+    int cx_left = 0, cx_right = 0, cx_dil = 1;
+    ContextArgs cx{};
 
     // lstm internals
     float *acts = nullptr, *cell = nullptr, *th = nullptr;
@@ -679,6 +689,11 @@ void launch_prefetch(cn_ctx *c, hipStream_t st)
     else relayout(st, c, p.input, p.post, p.f, alt, p.aug, p.splice, p.aug_tab);
     p.launched = true;
 }
+// Does a backward pass hand `p` an error: is there a K8 that writes p's outputErrors, and somebody who reads them?  A trainable
+// layer; or a context layer whose own predecessor does (it folds what it receives into that layer's outputErrors).  The input
+// layer and a context layer behind it take none.
+bool takes_err(const cn_layer *p) { return p->trainable || (p->context && takes_err(p->prev)); }
+
 void ensure_fork_events(cn_layer *l)
 {
     if (l->ev_fork) return;
@@ -695,7 +710,7 @@ template <typename F> void on_side(cn_layer *l, F &&f, bool fork_attached = fals
     // The first trainable layer's gradient work has nothing to run beside: only the weight update follows.  On the main
     // stream it saves the two cross-stream hand-offs (fork, join) in front of the update.
     const bool tail_on_main = !opt().tail_on_side;
-    if (tail_on_main && l->prev && !l->prev->trainable && !fork_attached) { f(c->stream, nullptr); return; }
+    if (tail_on_main && l->prev && !takes_err(l->prev) && !fork_attached) { f(c->stream, nullptr); return; }
     ensure_fork_events(l);
     if (!fork_attached) HIP_CHECK(hipEventRecord(l->ev_fork, c->stream));
     // a recurrent kernel follows on the main stream when the preceding layer is an LSTM layer: slow lane (a CU-masked stream, so
@@ -1061,7 +1076,7 @@ void residual_sum(cn_layer *l)
 // layer's outputErrors as its follower handed them in.
 void residual_add_error(cn_layer *l, const float *e)
 {
-    if (!l->summed || !l->prev->trainable) return;
+    if (!l->summed || !takes_err(l->prev)) return;
     Timed tm(l->ctx, KC_OTHER);
     launch_residual_bwd(l->ctx->stream, l->res, l->ctx->d_pat, e, l->prev->err);
 }
@@ -1087,7 +1102,7 @@ const void *normalized_input(cn_layer *l, const void *x)
 // stream meanwhile; nobody writes it.)
 void normalize_handed_back_error(cn_layer *l)
 {
-    if (!l->normed || !l->prev->trainable) return;
+    if (!l->normed || !takes_err(l->prev)) return;
     Timed tm(l->ctx, KC_OTHER);
     launch_layernorm_bwd(l->ctx->stream, l->ctx->f32, l->ln, l->ctx->d_pat, l->in_norm, l->ln_rstd, l->prev->err);
 }
@@ -1196,6 +1211,37 @@ void noise_ahead(cn_ctx *c)
     c->noise_wait = true;
 }
 
+// ---- context layers (include/currennt_hip.h, section Context layers) ----
+// The slot lengths of the current fraction, formed on the device on the context's stream, once per fraction
+void context_lengths(cn_ctx *c)
+{
+    if (c->cx_serial == c->frac_serial) return;
+    launch_context_lengths(c->stream, c->d_pat, c->T, c->PSp, c->cx_len);
+    c->cx_serial = c->frac_serial;
+}
+void context_forward(cn_layer *l)
+{
+    cn_ctx *c = l->ctx;
+    const cn_layer *p = l->prev;
+    ContextArgs &a = l->cx;
+    a.T = c->T; a.PSp = c->PSp; a.P = l->P; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
+    a.xLp = p->Lp; a.xH = p->lstm ? p->H : 0; a.xHp = p->lstm ? p->Hp : 0; a.xdirs = p->lstm ? p->dirs : 0;
+    Timed tm(c, KC_OTHER);
+    context_lengths(c);
+    launch_context_fwd(c->stream, c->f32, a, c->cx_len, follower_operand(p), l->out_op);
+}
+// behind the follower's K8 (and its mask / normalisation / skip term) on the main stream: the preceding layer's outputErrors.
+// Nothing to do when that layer takes none -- the follower then had no K8 either.
+void context_backward(cn_layer *l)
+{
+    cn_ctx *c = l->ctx;
+    if (!takes_err(l->prev)) return;
+    if (l->cx.T != c->T || l->cx.PSp != c->PSp) throw cn_error(CN_ERR_STATE, "cn_layer_backward: the context layer has no forward pass of the current fraction");
+    Timed tm(c, KC_OTHER);
+    context_lengths(c);
+    launch_context_bwd(c->stream, l->cx, c->cx_len, l->err, l->prev->err);
+}
+
 void lstm_forward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
@@ -1249,13 +1295,13 @@ void lstm_backward(cn_layer *l)
             check_rec_lds(l, true);
             // no K8 behind this kernel (the preceding layer is the input layer): the side stream forks from it directly
             const bool tail_on_side = opt().tail_on_side;
-            hipEvent_t fork = (tail_on_side && !l->prev->trainable && !c->timing) ? fork_event(l) : nullptr;
+            hipEvent_t fork = (tail_on_side && !takes_err(l->prev) && !c->timing) ? fork_event(l) : nullptr;
             launch_lstm_backward(c->stream, c->prec, r, fork);
             fork_attached = fork != nullptr;
         }
         HIP_CHECK(hipGetLastError());
     }
-    if (l->prev->trainable) {   // K8 (LstmLayer.cu:990-1009): one K = R product instead of 4*dirs
+    if (takes_err(l->prev)) {   // K8 (LstmLayer.cu:990-1009): one K = R product instead of 4*dirs
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
         g.A = l->delta_op; g.lda = R; g.B = noisy ? l->nWinT : l->WinT; g.ldb = R;
@@ -1266,7 +1312,7 @@ void lstm_backward(cn_layer *l)
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
     }
-    if (l->prev->trainable) mask_handed_back_error(l);    // (K8 carries the fork: K9 does not read prev->err and starts beside this)
+    if (takes_err(l->prev)) mask_handed_back_error(l);    // (K8 carries the fork: K9 does not read prev->err and starts beside this)
     normalize_handed_back_error(l);
     residual_add_error(l, l->err);        // (the recurrent kernels only read l->err: LstmRec::err is const, the hand-written loops only load from it)
     // K9 runs on the side stream: it only feeds weightUpdates, forked AFTER K8 so the critical-path GEMM has the chip to itself, and running beside the
@@ -1386,7 +1432,7 @@ void ff_backward(cn_layer *l)
             if (l->kind == CN_LAYER_SOFTMAX) l->sm_lazy_next = false;   // no fused consumer: lazy rows would be normalised on demand every pass
             const float *y = posteriors(l);                 // (the branch: act' of a marked layer is taken at its own output, not at the sum)
             // a marked layer hands its outputErrors on as they came in: launch_ff_delta below overwrites them in place
-            if (l->summed && l->prev->trainable)
+            if (l->summed && takes_err(l->prev))
                 HIP_CHECK(hipMemcpyAsync(l->res_e, l->err, (size_t)N * l->Lp * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             if (l->mcc_pending) launch_mcc_backward(c->stream, y, c->d_tcls, N, l->size, l->Lp, l->err);
             if (l->kind == CN_LAYER_SOFTMAX) launch_softmax_bwd(c->stream, y, l->err, c->d_pat, N, l->size, l->Lp);
@@ -1396,7 +1442,7 @@ void ff_backward(cn_layer *l)
         l->mcc_pending = false;
     }
     bool fork_attached = false;
-    if (l->prev->trainable) {   // FeedForwardLayer.cu:188-198
+    if (takes_err(l->prev)) {   // FeedForwardLayer.cu:188-198
         Timed tm(c, KC_GEMM_WIDE);
         GemmNT g{};
         g.A = l->delta_op; g.lda = l->Lp; g.B = noisy ? l->nWinT : l->WinT; g.ldb = l->Lp;
@@ -1407,7 +1453,7 @@ void ff_backward(cn_layer *l)
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
     }
-    if (l->prev->trainable) mask_handed_back_error(l);
+    if (takes_err(l->prev)) mask_handed_back_error(l);
     normalize_handed_back_error(l);
     residual_add_error(l, l->res_e);
     on_side(l, [&](hipStream_t st, hipEvent_t join) {
@@ -1554,7 +1600,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart); hipFree(ctx->aug_tab); hipFree(ctx->pf.aug_tab);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault); hipFree(ctx->cx_len);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -1801,6 +1847,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
     int rc = guarded([&] {
         enter(ctx);
         if (size <= 0) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: layer size must be positive");
+        if (kind == CN_LAYER_CONTEXT) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: a context layer has members of its own: use cn_layer_create_context");
         if (kind == CN_LAYER_INPUT) {
             if (preceding) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create: the input layer has no preceding layer");
             if (parallel_sequences <= 0 || max_seq_length <= 0)
@@ -1971,6 +2018,53 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
     return CN_OK;
 }
 
+int cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, cn_layer **out)
+{
+    if (!ctx || !out) { g_last_error = "cn_layer_create_context: NULL argument"; return CN_ERR_BAD_ARG; }
+    *out = nullptr;
+    cn_layer *l = nullptr;
+    int rc = guarded([&] {
+        enter(ctx);
+        if (!preceding) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: preceding layer required");
+        if (preceding->ctx != ctx) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: preceding layer belongs to another context");
+        if (preceding->post) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: a post output layer must be the last layer");
+        if (left < 0 || left > 32 || right < 0 || right > 32)
+            throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: left and right must lie in 0..32 (" + std::to_string(left) + ", " + std::to_string(right) + ")");
+        if (dilation < 1 || dilation > 16)
+            throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: dilation must lie in 1..16 (" + std::to_string(dilation) + ")");
+        l = new cn_layer;
+        l->ctx = ctx; l->kind = CN_LAYER_CONTEXT; l->prev = preceding; l->context = true;
+        l->cx_left = left; l->cx_right = right; l->cx_dil = dilation;
+        l->ordinal = ctx->next_ordinal;
+        l->PS = preceding->PS; l->maxT = preceding->maxT; l->PSp = ctx->PSp;
+        l->P = preceding->size; l->Pp = preceding->Lp;
+        l->size = (left + right + 1) * l->P;
+        l->Lp = round_up(l->size, 32);                    // dense rows, whatever padding the preceding layer's have
+        const size_t maxN = l->maxN();
+        l->out_op = dalloc(l, maxN * l->Lp * ctx->esz());
+        l->err = (float *)dalloc(l, maxN * l->Lp * sizeof(float));
+        if (!ctx->cx_len) {
+            HIP_CHECK(hipMalloc((void **)&ctx->cx_len, (size_t)l->PSp * sizeof(int)));
+            HIP_CHECK(hipMemsetAsync(ctx->cx_len, 0, (size_t)l->PSp * sizeof(int), ctx->stream));
+        }
+        preceding->has_follower = true;                   // (a feed-forward or softmax predecessor keeps its operand copy for the gather)
+        ctx->layers.push_back(l);
+        ++ctx->next_ordinal;
+    });
+    if (rc != CN_OK) { if (l) { for (void *p : l->owned) hipFree(p); delete l; } return rc; }
+    *out = l;
+    return CN_OK;
+}
+
+int cn_layer_context(const cn_layer *layer, int *left, int *right, int *dilation)
+{
+    if (!layer || !layer->context) { g_last_error = "cn_layer_context: not a context layer"; return CN_ERR_BAD_ARG; }
+    if (left) *left = layer->cx_left;
+    if (right) *right = layer->cx_right;
+    if (dilation) *dilation = layer->cx_dil;
+    return CN_OK;
+}
+
 int cn_layer_destroy(cn_layer *layer)
 {
     if (!layer) return CN_OK;
@@ -2101,6 +2195,7 @@ static void set_current(cn_ctx *ctx, const cn_fraction *f)
     ctx->T = T; ctx->Tmin = f->min_seq_length; ctx->N = T * ctx->PSp; ctx->Next = T * ctx->PS; ctx->numSeqs = f->num_sequences;
     ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2);
     ctx->loaded = true;
+    ++ctx->frac_serial;
 }
 // the alternate buffers a prefetch re-laid its fraction out into become the current ones
 static void swap_in_prefetched(cn_ctx *ctx, cn_layer *input, cn_layer *post_output)
@@ -2310,9 +2405,10 @@ int cn_layer_forward(cn_layer *layer)
         require_loaded(layer->ctx);
         finalize(layer->ctx);
         join_side(layer->ctx);
-        if (layer->trainable && !layer->prev->trainable && opt().noise_ahead) noise_ahead(layer->ctx);
+        if (layer->trainable && !takes_err(layer->prev) && opt().noise_ahead) noise_ahead(layer->ctx);
         if (layer->lstm) lstm_forward(layer);
         else if (layer->trainable) ff_forward(layer);
+        else if (layer->context) context_forward(layer);
         /* input and post output layers: no-op (InputLayer.cpp:62-65, SsePostOutputLayer.cu:134-137) */
     });
 }
@@ -2333,6 +2429,7 @@ int cn_layer_backward(cn_layer *layer)
         if (layer->trainable) c->clip_valid = false;        // (the gradient changes: the next update call forms its norm)
         if (layer->lstm) lstm_backward(layer);
         else if (layer->trainable) ff_backward(layer);
+        else if (layer->context) context_backward(layer);
         else if (layer->post) {
             Timed tm(c, KC_OTHER);
             cn_layer *o = layer->prev;
@@ -2601,6 +2698,7 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
                 for (int d = 0; d < layer->dirs; ++d) launch_unpad(c->stream, opbf, follower_operand(layer), layer->Lp, d * Hp, 1, N, H, tmp, layer->size, d * H, c->PS, c->PSp);
             else if (layer->summed) launch_unpad(c->stream, opbf, layer->res_sum, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
             else if (layer->trainable) launch_unpad(c->stream, false, posteriors(layer), layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
+            else if (layer->context) launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
             else throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no outputs");
             break;
         case CN_BUF_OUTPUT_ERRORS:

@@ -1,0 +1,148 @@
+// Context layers: a hidden layer that splices its predecessor's neighbouring frames (include/currennt_hip.h, section Context
+// layers; no counterpart in the reference, which splices the input patterns only).  gfx950 only.
+//
+//   context_len_kernel   len[s] = frames of slot s whose pattern type is not NONE, for every slot of a time step (pad slots: 0)
+//   context_fwd_kernel   out[t][s][b * P + u] (op) = x[clamp(t + (b - L) * D, 0, len_s - 1)][s][u] (op), bits copied; zeros on
+//                        the rows that are no real frames and in pad columns
+//   context_bwd_kernel   dx[ts][s][u] (fp32) = the sum of e[j][s][b * P + u] over the (b, j) that read frame ts, b ascending, then
+//                        j ascending, single fp32 additions from +0.0f; zeros on every other row below N and in pad columns
+// All three are streaming kernels: grid-stride loops, no LDS, no atomics.  The context layer's rows are dense (unit u of block b
+// at column b * P + u); the predecessor's may be split (a blstm: direction d's unit j at d * Hp + j), which res_col / res_unit of
+// cn_unit_map_device.h translate.
+//
+// Thread map, as in cn_splice.hip: a thread owns VEC neighbouring columns of one row and stores them as one 16-byte piece (the
+// gather: 4 fp32 / 8 bf16 operands of a context row; the fold: 4 fp32 of a predecessor row), neighbouring threads own
+// neighbouring pieces, so a wave stores one contiguous KiB and loads runs of contiguous units of one source row.  Where P and a
+// split predecessor's H are multiples of VEC a piece lies in one block and one direction and its source starts on 16 bytes: it
+// is loaded as one piece too (RUN).  Otherwise (the headline's H = 125) the piece is put together from element loads, which
+// neighbouring lanes still take from neighbouring addresses: the scalar path, which also serves a source that does not start on
+// 16 bytes.  The stores are always whole pieces: both kernels write buffers of this library's own allocation whose rows are
+// multiples of 32 elements (cn_layer_create*).  At the sizes of a fraction both buffers stay in the L2 / MALL.
+#include <type_traits>
+
+#include "cn_internal.h"
+#include "cn_unit_map_device.h"
+
+namespace cn {
+
+// one wave per slot: lane i counts the frames t = i, i + 64, ..., the lanes' counts are added across the wave
+__global__ __launch_bounds__(64) void context_len_kernel(const char *__restrict__ pat, int T, int PSp, int *__restrict__ len)
+{
+    const int s = blockIdx.x;
+    int n = 0;
+    for (int t = threadIdx.x; t < T; t += 64) n += pat[(long)t * PSp + s] != 0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d, 64);
+    if (threadIdx.x == 0) len[s] = n;
+}
+
+// the first frame of slot s that block b of frame t reads; len >= 1
+__device__ __forceinline__ int context_src(const ContextArgs &a, int t, int b, int len) { return max(0, min(t + (b - a.left) * a.dil, len - 1)); }
+
+template <bool F32, int VEC, bool RUN>
+__global__ __launch_bounds__(256) void context_fwd_kernel(ContextArgs a, const int *__restrict__ len, const void *__restrict__ x, void *__restrict__ out)
+{
+    typedef typename std::conditional<F32, unsigned, unsigned short>::type op_t;      // (the bits of an operand: nothing is rounded)
+    static_assert(VEC * sizeof(op_t) == 16, "a piece is 16 bytes");
+    const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const int pieces = a.Lp / VEC, width = a.B * a.P;
+    const long total = (long)a.T * a.PSp * pieces;
+    for (long idx = tid; idx < total; idx += nth) {
+        const long n = idx / pieces; const int c0 = (int)(idx % pieces) * VEC;
+        const int t = (int)(n / a.PSp), s = (int)(n % a.PSp);
+        const int ln = len[s];
+        const bool live = t < ln && c0 < width;           // (no holes: the real frames of a slot are t = 0 .. len - 1)
+        int b = 0, u = 0;                                  // block and unit of the piece's first column
+        if (live) { b = c0 / a.P; u = c0 - b * a.P; }
+        if constexpr (RUN) {
+            uint4 o = make_uint4(0u, 0u, 0u, 0u);
+            if (live) o = *(const uint4 *)((const op_t *)x + ((long)context_src(a, t, b, ln) * a.PSp + s) * a.xLp + res_col(u, a.xH, a.xHp));
+            *(uint4 *)((op_t *)out + n * a.Lp + c0) = o;
+        } else {
+            union { op_t e[VEC]; uint4 q; } v;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                op_t w = 0;
+                if (live && c0 + i < width) {
+                    w = ((const op_t *)x)[((long)context_src(a, t, b, ln) * a.PSp + s) * a.xLp + res_col(u, a.xH, a.xHp)];
+                    if (++u == a.P) { u = 0; ++b; }
+                }
+                v.e[i] = w;
+            }
+            *(uint4 *)((op_t *)out + n * a.Lp + c0) = v.q;
+        }
+    }
+}
+
+template <bool RUN>
+__global__ __launch_bounds__(256) void context_bwd_kernel(ContextArgs a, const int *__restrict__ len, const float *__restrict__ e, float *__restrict__ dx)
+{
+    constexpr int VEC = 4;                                  // a piece is four fp32
+    const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const int pieces = a.xLp / VEC;
+    const long total = (long)a.T * a.PSp * pieces;
+    for (long idx = tid; idx < total; idx += nth) {
+        const long n = idx / pieces; const int c0 = (int)(idx % pieces) * VEC;
+        const int t = (int)(n / a.PSp), s = (int)(n % a.PSp);
+        const int ln = len[s];
+        // the units of the piece's columns: consecutive from u0, the first cnt columns (Hp is a multiple of 32: a piece lies in one
+        // direction and its pad columns come last); RUN: all four or none
+        const int u0 = res_unit(c0, a.P, a.xH, a.xHp, a.xdirs);
+        const int cnt = res_units_in_group(c0, VEC, a.P, a.xH, a.xHp, a.xdirs);
+        float acc[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
+        if (t < ln && cnt > 0) {
+            for (int b = 0; b < a.B; ++b) {
+                // the frames j of the slot with clamp(j + o, 0, len - 1) == t: j = t - o inside the sequence, and the runs that
+                // the clamp folds onto its first and its last frame
+                const int o = (b - a.left) * a.dil;
+                const int jlo = max(t == 0 ? 0 : t - o, 0), jhi = min(t == ln - 1 ? ln - 1 : t - o, ln - 1);
+                for (int j = jlo; j <= jhi; ++j) {
+                    const float *p = e + ((long)j * a.PSp + s) * a.Lp + b * a.P + u0;
+                    if constexpr (RUN) {
+                        const float4 v = *(const float4 *)p;
+                        acc[0] = __fadd_rn(acc[0], v.x); acc[1] = __fadd_rn(acc[1], v.y); acc[2] = __fadd_rn(acc[2], v.z); acc[3] = __fadd_rn(acc[3], v.w);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) if (i < cnt) acc[i] = __fadd_rn(acc[i], p[i]);
+                    }
+                }
+            }
+        }
+        *(float4 *)(dx + n * a.xLp + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+static int context_blocks(long work) { long b = (work + 255) / 256; return (int)(b > 2048 ? 2048 : b); }
+// is every piece of `vec` elements one run: every block of P units and every direction of a split predecessor a whole number of them
+static bool context_runs(const ContextArgs &a, int vec) { return a.P % vec == 0 && a.xH % vec == 0; }
+
+void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int *len)
+{
+    if (PSp <= 0) return;
+    hipLaunchKernelGGL(context_len_kernel, dim3(PSp), dim3(64), 0, s, pat, T, PSp, len);
+}
+
+void launch_context_fwd(hipStream_t s, bool f32, const ContextArgs &a, const int *len, const void *x, void *out)
+{
+    const long rows = (long)a.T * a.PSp; if (rows <= 0) return;
+    const int vec = f32 ? 4 : 8;
+    const bool runs = context_runs(a, vec) && ((size_t)x & 15) == 0;
+    const int blocks = context_blocks(rows * (a.Lp / vec));
+#define CN_CONTEXT_FWD(F32, VEC, RUN) hipLaunchKernelGGL((context_fwd_kernel<F32, VEC, RUN>), dim3(blocks), dim3(256), 0, s, a, len, x, out)
+    if (f32) { if (runs) CN_CONTEXT_FWD(true, 4, true); else CN_CONTEXT_FWD(true, 4, false); }
+    else     { if (runs) CN_CONTEXT_FWD(false, 8, true); else CN_CONTEXT_FWD(false, 8, false); }
+#undef CN_CONTEXT_FWD
+}
+
+void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, const float *e, float *dx)
+{
+    const long rows = (long)a.T * a.PSp; if (rows <= 0) return;
+    const bool runs = context_runs(a, 4) && ((size_t)e & 15) == 0;
+    const int blocks = context_blocks(rows * (a.xLp / 4));
+    if (runs) hipLaunchKernelGGL(context_bwd_kernel<true>, dim3(blocks), dim3(256), 0, s, a, len, e, dx);
+    else      hipLaunchKernelGGL(context_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, a, len, e, dx);
+}
+
+}  // namespace cn

@@ -350,6 +350,20 @@ struct ResArgs {
 void launch_residual_fwd(hipStream_t s, bool f32, const ResArgs &a, const char *pat, const void *branch, const void *x, void *sum);
 // prev_err[N][xLp] (fp32) += e[N][Lp] (fp32) on the rows with pat[row] != 0, unit by unit
 void launch_residual_bwd(hipStream_t s, const ResArgs &a, const char *pat, const float *e, float *prev_err);
+// ---- context layers (include/currennt_hip.h, section Context layers; cn_context.hip) ----
+// The geometry of one forward pass of one context layer: T time steps of PSp slots; B = left + right + 1 blocks of the preceding
+// layer's P units in rows Lp = round_up(B * P, 32) wide, block b at columns [b * P, (b + 1) * P); the preceding layer's rows are
+// xLp wide with (xH, xHp, xdirs) -- xH = 0: a dense layer, the input layer or another context layer, unit u at column u; else
+// direction d's units at columns [d * xHp, d * xHp + xH).
+struct ContextArgs {
+    int T, PSp, P, B, left, dil, Lp, xLp, xH, xHp, xdirs;
+};
+// len[PSp]: the frames of every slot whose pattern type is not NONE, from pat[t * PSp + s], t < T (one wave per slot)
+void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int *len);
+// out[T * PSp][Lp] (op) gathered from x[T * PSp][xLp] (op), bits copied; rows t >= len[s] and pad columns are written as zeros
+void launch_context_fwd(hipStream_t s, bool f32, const ContextArgs &a, const int *len, const void *x, void *out);
+// dx[T * PSp][xLp] (fp32), every row and column written: the fold of e[T * PSp][Lp] (fp32) in the stated order, zeros elsewhere
+void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, const float *e, float *dx);
 // delta = act'(y) * err (in place on err, all N slots: FeedForwardLayer.cu:72-79), op copy for the GEMMs
 void launch_ff_delta(hipStream_t s, bool f32, int act, const float *y, float *err, void *delta_op, int N, int L, int Lp);
 // column sums of delta over the N slots (FeedForwardLayer.cu:82-102): colsum[j] += sum_n err[n][j]

@@ -18,10 +18,12 @@ layers::Layer *LayerFactory::createLayer(cn_ctx *ctx, const std::string &layerTy
     if (layerType == "softmax") return new SoftmaxLayer(ctx, layerChild, weightsSection, *precedingLayer);
     if (layerType == "lstm") return new LstmLayer(ctx, layerChild, weightsSection, *precedingLayer, false);
     if (layerType == "blstm") return new LstmLayer(ctx, layerChild, weightsSection, *precedingLayer, true);
+    if (layerType == "context") return new ContextLayer(ctx, layerChild, *precedingLayer);       // no counterpart in the reference
     if (layerType == "sse" || layerType == "weightedsse" || layerType == "rmse" || layerType == "ce" || layerType == "wf" ||
         layerType == "binary_classification" || layerType == "multiclass_classification" || layerType == "ctc") {
         if (!precedingLayer->isTrainable())                                                      // LayerFactory.cu:68-70
-            throw std::runtime_error("Cannot add post output layer after a non trainable layer");
+            throw std::runtime_error("Cannot add post output layer after a non trainable layer" +
+                                     (precedingLayer->type() == "context" ? " (the context layer '" + precedingLayer->name() + "')" : std::string()));
         if (layerType == "sse") return new SsePostOutputLayer(ctx, layerChild, *precedingLayer);
         if (layerType == "weightedsse") return new WeightedSsePostOutputLayer(ctx, layerChild, *precedingLayer);
         if (layerType == "rmse") return new RmsePostOutputLayer(ctx, layerChild, *precedingLayer);

@@ -41,7 +41,7 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
             throw std::runtime_error("Invalid value 'residual' in layer '" + m_name + "': the layer's size " + std::to_string(m_size) +
                                      " differs from the preceding layer's size " + std::to_string(precedingLayer->size()));
     }
-    if (precedingLayer && precedingLayer->residual() && !trainableKind)
+    if (precedingLayer && precedingLayer->residual() && !trainableKind && kind != CN_LAYER_CONTEXT)
         throw std::runtime_error("Invalid value 'residual' in layer '" + precedingLayer->name() + "': a post output layer cannot follow a residual layer directly");
     // "layer_norm": true marks a trainable layer whose input products read a normalised copy of its input, "layer_norm_eps" is the
     // eps under the square root (include/currennt_hip.h, section Layer normalization; the reference has none).  The refusals are
@@ -63,8 +63,14 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
             throw std::runtime_error("Invalid value 'layer_norm' in layer '" + m_name + "': the preceding layer's size " +
                                      std::to_string(precedingLayer->size()) + " is below 2");
     }
-    hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
-                             precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
+    if (kind == CN_LAYER_CONTEXT) {        // (a kind with members of its own and an entry point of its own)
+        int left, right, dilation;
+        contextMembers(layerChild, m_name, m_size, precedingLayer, &left, &right, &dilation);
+        hipCheck(cn_layer_create_context(ctx, precedingLayer->handle(), left, right, dilation, &m_handle), ctx);
+    } else {
+        hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
+                                 precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
+    }
     if (m_residual) hipCheck(cn_layer_set_residual(m_handle, 1), ctx);
     if (m_layerNorm) hipCheck(cn_layer_set_layer_norm(m_handle, 1, m_layerNormEps), ctx);
 }
@@ -98,6 +104,43 @@ void Layer::exportLayer(json::Value *layersArray) const
     o.addMember("type", type());
     o.addMember("size", size());
     layersArray->pushBack(o);
+}
+
+// ---- ContextLayer ---------------------------------------------------------------------------
+// The refusals are the library's (include/currennt_hip.h, section Context layers), said here with the layer's name; the size
+// check uses the reference's text for a size that does not fit the preceding layer (PostOutputLayer.cpp:58-59).
+void Layer::contextMembers(const json::Value &layerChild, const std::string &name, int size, const Layer *precedingLayer,
+                           int *left, int *right, int *dilation)
+{
+    struct Member { const char *key; int dflt, lo, hi; int *out; };
+    const Member members[3] = {{"left", 0, 0, 32, left}, {"right", 0, 0, 32, right}, {"dilation", 1, 1, 16, dilation}};
+    for (int k = 0; k < 3; ++k) {
+        const Member &m = members[k];
+        *m.out = m.dflt;
+        if (!layerChild.hasMember(m.key)) continue;
+        const json::Value &v = layerChild[m.key];
+        if (!v.isNumber() || v.getDouble() != std::floor(v.getDouble()) || v.getDouble() < m.lo || v.getDouble() > m.hi)
+            throw std::runtime_error(std::string("Invalid value '") + m.key + "' in layer '" + name + "': an integer in " + std::to_string(m.lo) +
+                                     ".." + std::to_string(m.hi) + " expected");
+        *m.out = v.getInt();
+    }
+    const int blocks = *left + *right + 1;
+    if (size != blocks * precedingLayer->size())
+        throw std::runtime_error("Size mismatch: " + std::to_string(size) + " vs. " + std::to_string(blocks * precedingLayer->size()) + " in layer '" + name +
+                                 "' (" + std::to_string(blocks) + " frames of the preceding layer's " + std::to_string(precedingLayer->size()) + " units)");
+}
+ContextLayer::ContextLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer)
+    : Layer(ctx, layerChild, CN_LAYER_CONTEXT, &precedingLayer, precedingLayer.parallelSequences(), precedingLayer.maxSeqLength(), 0.f)
+    , m_left(0), m_right(0), m_dilation(1)
+{
+    hipCheck(cn_layer_context(m_handle, &m_left, &m_right, &m_dilation), ctx);
+}
+const std::string &ContextLayer::type() const { static const std::string s("context"); return s; }
+void ContextLayer::exportLayer(json::Value *layersArray) const
+{
+    Layer::exportLayer(layersArray);
+    json::Value &o = (*layersArray)[layersArray->size() - 1];
+    o.addMember("left", m_left); o.addMember("right", m_right); o.addMember("dilation", m_dilation);
 }
 
 // ---- InputLayer -----------------------------------------------------------------------------

@@ -50,6 +50,9 @@ public:
 
 protected:
     Hip::real_vector read(cn_buffer which, int dir, size_t count) const;
+    // the members of a "context" layer description, checked: the constructor below creates such a layer from them
+    static void contextMembers(const json::Value &layerChild, const std::string &name, int size, const Layer *precedingLayer,
+                               int *left, int *right, int *dilation);
 
     cn_ctx *m_ctx;
     cn_layer *m_handle;
@@ -67,6 +70,21 @@ public:
     InputLayer(cn_ctx *ctx, const json::Value &layerChild, int parallelSequences, int maxSeqLength);
     const std::string &type() const;
     void loadSequences(const data_sets::DataSetFraction &fraction);
+};
+
+// A hidden layer without weights that splices its preceding layer's neighbouring frames (include/currennt_hip.h, section Context
+// layers; no counterpart in the reference): JSON "left" / "right" (default 0) frames at steps of "dilation" (default 1), and a
+// "size" of (left + right + 1) x the preceding layer's size
+class ContextLayer : public Layer {
+public:
+    ContextLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer);
+    const std::string &type() const;
+    int left() const { return m_left; }
+    int right() const { return m_right; }
+    int dilation() const { return m_dilation; }
+    void exportLayer(json::Value *layersArray) const;
+private:
+    int m_left, m_right, m_dilation;
 };
 
 class TrainableLayer : public Layer {                     // layers/TrainableLayer.{hpp,cu}

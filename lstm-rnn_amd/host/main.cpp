@@ -95,6 +95,8 @@ void printLayers(const NeuralNetwork &nn)                                       
         printf("[size: %d", nn.layers()[i]->size());
         const layers::TrainableLayer *tl = dynamic_cast<const layers::TrainableLayer *>(nn.layers()[i].get());
         if (tl) { printf(", bias: %.1lf, weights: %d", (double)tl->bias(), tl->weightCount()); weights += tl->weightCount(); }
+        if (const layers::ContextLayer *cl = dynamic_cast<const layers::ContextLayer *>(nn.layers()[i].get()))
+            printf(", context -%d..+%d x%d", cl->left(), cl->right(), cl->dilation());
         if (nn.layers()[i]->residual()) printf(", residual");
         if (nn.layers()[i]->layerNorm()) printf(", layer_norm");
         printf("]\n");

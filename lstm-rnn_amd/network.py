@@ -28,7 +28,7 @@ class Layer:
         if "size" not in desc:
             raise RuntimeError("Missing value 'size' in layer '%s'" % desc["name"])   # Layer.cpp:56-57
         self.name, self.type, self.size = desc["name"], desc["type"], int(desc["size"])
-        if self.type not in B.LAYER_KINDS:
+        if self.type not in B.LAYER_KINDS and self.type != "context":
             raise RuntimeError("Unknown layer type '%s'" % self.type)                  # LayerFactory.cu:86
         self.trainable = self.type in _TRAINABLE
         self.post = self.type in _POST
@@ -40,10 +40,23 @@ class Layer:
             raise RuntimeError("Invalid value 'residual' in layer '%s': a post output layer cannot follow a residual layer directly" % prev.name)
         h = C.c_void_p()
         L = net.lib
-        B.check(L.cn_layer_create(net.ctx, B.LAYER_KINDS[self.type], prev.handle if prev else None,
-                                  self.size, self.bias,
-                                  net.parallel_sequences if prev is None else 0,
-                                  net.max_seq_length if prev is None else 0, C.byref(h)), net.ctx)
+        if self.type == "context":
+            # "left" / "right" (default 0) neighbouring frames of the preceding layer at steps of "dilation" (default 1) beside
+            # each frame (include/currennt_hip.h, section Context layers).  The size is checked here, with the reference's text;
+            # the members' ranges are the library's to refuse (CN_ERR_BAD_ARG)
+            if prev is None:
+                raise RuntimeError("The first layer is not an input layer")
+            self.left, self.right, self.dilation = self._int_member(desc, "left", 0), self._int_member(desc, "right", 0), self._int_member(desc, "dilation", 1)
+            blocks = self.left + self.right + 1
+            if blocks >= 1 and self.size != blocks * prev.size:
+                raise RuntimeError("Size mismatch: %d vs. %d in layer '%s' (%d frames of the preceding layer's %d units)"
+                                   % (self.size, blocks * prev.size, self.name, blocks, prev.size))
+            B.check(L.cn_layer_create_context(net.ctx, prev.handle, self.left, self.right, self.dilation, C.byref(h)), net.ctx)
+        else:
+            B.check(L.cn_layer_create(net.ctx, B.LAYER_KINDS[self.type], prev.handle if prev else None,
+                                      self.size, self.bias,
+                                      net.parallel_sequences if prev is None else 0,
+                                      net.max_seq_length if prev is None else 0, C.byref(h)), net.ctx)
         self.handle = h
         self.weight_count = L.cn_layer_weight_count(h) if self.trainable else 0
         if self.trainable and self.learning_rate >= 0.0:       # cn_sgd_update_all honours it too (SteepestDescentOptimizer.cu:78-80)
@@ -92,6 +105,26 @@ class Layer:
         if self.type in ("lstm", "blstm"):
             self.dirs = 2 if self.type == "blstm" else 1
             self.H = self.size // self.dirs
+
+    def _int_member(self, desc, member, default):
+        v = desc.get(member, default)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise RuntimeError("Invalid value '%s' in layer '%s': an integer expected" % (member, self.name))
+        return v
+
+    def context(self):
+        """cn_layer_context: (left, right, dilation) of a context layer."""
+        l, r, d = C.c_int(), C.c_int(), C.c_int()
+        B.check(self.net.lib.cn_layer_context(self.handle, C.byref(l), C.byref(r), C.byref(d)), self.net.ctx)
+        return l.value, r.value, d.value
+
+    def forward(self):
+        """cn_layer_forward of this layer alone."""
+        B.check(self.net.lib.cn_layer_forward(self.handle), self.net.ctx)
+
+    def backward(self):
+        """cn_layer_backward of this layer alone."""
+        B.check(self.net.lib.cn_layer_backward(self.handle), self.net.ctx)
 
     # -- buffers in reference layout -----------------------------------------------------------
     def _read(self, which, count, direction=0):
