@@ -784,23 +784,31 @@ void timing_collect(cn_ctx *c)
 // ---- geometry -------------------------------------------------------------------------------
 int pad_units(int H) { return H > 512 ? round_up(H, 64) : round_up(H, 32); }
 
-LstmGeom lstm_geom(const cn_layer *l)
+// the map of a layer's own output rows (cn_unit_map.h); a follower's P and Pp are its L and Lp (cn_layer_create*)
+UnitMap unit_map(const cn_layer *l)
 {
-    LstmGeom g;
-    g.P = l->P; g.Pp = l->Pp; g.L = l->size; g.H = l->H; g.Hp = l->Hp; g.dirs = l->dirs;
-    g.prevH = l->prev->lstm ? l->prev->H : 0;
-    g.prevHp = l->prev->lstm ? l->prev->Hp : 0;
-    g.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
-    return g;
+    return UnitMap{l->size, l->Lp, l->lstm ? l->H : 0, l->lstm ? l->Hp : 0, l->lstm ? l->dirs : 0};
 }
-FfGeom ff_geom(const cn_layer *l)
+// does every unit have the same column in both maps (of the same L units)?  Only two directions split a row.
+bool same_columns(const UnitMap &a, const UnitMap &b)
 {
-    FfGeom g;
-    g.P = l->P; g.Pp = l->Pp; g.L = l->size; g.Lp = l->Lp;
-    g.prevH = l->prev->lstm ? l->prev->H : 0;
-    g.prevHp = l->prev->lstm ? l->prev->Hp : 0;
-    g.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
-    return g;
+    const bool sa = a.H && a.dirs == 2, sb = b.H && b.dirs == 2;
+    return sa == sb && (!sa || a.Hp == b.Hp);
+}
+LstmGeom lstm_geom(const cn_layer *l) { return LstmGeom{l->size, l->H, l->Hp, l->dirs, unit_map(l->prev)}; }
+FfGeom ff_geom(const cn_layer *l) { return FfGeom{l->size, l->Lp, unit_map(l->prev)}; }
+// Read-back of a layer's rows: `frames` host rows (PS slots per time step, PSp on the device) of map m at src, unpadded into the
+// reference layout [frames][m.L] and copied to `host`; the stream is synchronised
+void read_rows(cn_ctx *c, const void *src, bool src_is_bf16, const UnitMap &m, int frames, int PS, int PSp, float *host)
+{
+    const size_t bytes = (size_t)frames * m.L * sizeof(float);
+    const Scratch scratch(bytes);
+    float *tmp = scratch.get();
+    if (m.H)
+        for (int d = 0; d < m.dirs; ++d) launch_unpad(c->stream, src_is_bf16, src, m.Lp, d * m.Hp, 1, frames, m.H, tmp, m.L, d * m.H, PS, PSp);
+    else launch_unpad(c->stream, src_is_bf16, src, m.Lp, 0, 1, frames, m.L, tmp, m.L, 0, PS, PSp);
+    HIP_CHECK(hipMemcpyAsync(host, tmp, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 int ff_act(cn_layer_kind k)
 {
@@ -1063,11 +1071,8 @@ void residual_sum(cn_layer *l)
     if (!l->residual) return;
     const cn_layer *p = l->prev;
     ResArgs &a = l->res;
-    a.N = c->N; a.L = l->size; a.Lp = l->Lp;
-    a.H = l->lstm ? l->H : 0; a.Hp = l->lstm ? l->Hp : 0; a.dirs = l->lstm ? l->dirs : 0;
-    a.xLp = p->Lp; a.xH = p->lstm ? p->H : 0; a.xHp = p->lstm ? p->Hp : 0; a.xdirs = p->lstm ? p->dirs : 0;
-    const bool two = l->lstm && l->dirs == 2, xtwo = p->lstm && p->dirs == 2;     // (one direction: unit u at column u, like a dense layer)
-    a.same_map = two == xtwo && (!two || l->Hp == p->Hp);
+    a.N = c->N; a.own = unit_map(l); a.prev = unit_map(p);
+    a.same_map = same_columns(a.own, a.prev);
     Timed tm(c, KC_OTHER);
     launch_residual_fwd(c->stream, c->f32, a, c->d_pat, l->out_op, follower_operand(p), l->res_sum);
     l->summed = true;
@@ -1089,10 +1094,8 @@ const void *normalized_input(cn_layer *l, const void *x)
     cn_ctx *c = l->ctx;
     l->normed = l->layer_norm;
     if (!l->normed) return x;
-    const cn_layer *p = l->prev;
     LnArgs &a = l->ln;
-    a.N = c->N; a.P = l->P; a.Pp = l->Pp; a.PS = c->PS; a.PSp = c->PSp; a.eps = l->ln_eps;
-    a.prevH = p->lstm ? p->H : 0; a.prevHp = p->lstm ? p->Hp : 0; a.prevDirs = p->lstm ? p->dirs : 0;
+    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev); a.eps = l->ln_eps;
     Timed tm(c, KC_OTHER);
     launch_layernorm_fwd(c->stream, c->f32, a, c->d_pat, x, l->in_norm, l->ln_rstd);
     return l->in_norm;
@@ -1119,8 +1122,7 @@ const void *forward_input(cn_layer *l)
     l->dropped = c->drop_enable && l->drop_rate > 0.f;
     if (!l->dropped) return x;
     DropArgs &a = l->drop;
-    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.P = l->P; a.Pp = l->Pp;
-    a.prevH = l->prev->lstm ? l->prev->H : 0; a.prevHp = l->prev->lstm ? l->prev->Hp : 0; a.prevDirs = l->prev->lstm ? l->prev->dirs : 0;
+    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev);
     a.k0 = (uint32_t)c->drop_seed + (uint32_t)l->ordinal; a.k1 = (uint32_t)(c->drop_seed >> 32);
     a.pass_lo = (uint32_t)c->drop_pass; a.pass_hi = (uint32_t)(c->drop_pass >> 32);
     a.thr = (uint32_t)std::floor((double)l->drop_rate * 4294967296.0);
@@ -1224,8 +1226,8 @@ void context_forward(cn_layer *l)
     cn_ctx *c = l->ctx;
     const cn_layer *p = l->prev;
     ContextArgs &a = l->cx;
-    a.T = c->T; a.PSp = c->PSp; a.P = l->P; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
-    a.xLp = p->Lp; a.xH = p->lstm ? p->H : 0; a.xHp = p->lstm ? p->Hp : 0; a.xdirs = p->lstm ? p->dirs : 0;
+    a.T = c->T; a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
+    a.prev = unit_map(p);
     Timed tm(c, KC_OTHER);
     context_lengths(c);
     launch_context_fwd(c->stream, c->f32, a, c->cx_len, follower_operand(p), l->out_op);
@@ -2649,7 +2651,7 @@ int cn_layer_write_output_errors(cn_layer *layer, const float *host, size_t coun
         layer->mcc_pending = false;
         layer->err_in_delta = false;
         HIP_CHECK(hipMemsetAsync(layer->err, 0, (size_t)c->N * layer->Lp * sizeof(float), c->stream));
-        launch_pad_f32(c->stream, tmp, c->Next, layer->size, layer->err, layer->Lp, layer->lstm ? layer->H : 0, layer->lstm ? layer->Hp : 0, c->PS, c->PSp);
+        launch_pad_f32(c->stream, tmp, c->Next, layer->err, unit_map(layer), c->PS, c->PSp);
         HIP_CHECK(hipStreamSynchronize(c->stream));
     });
 }
@@ -2687,32 +2689,29 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
             width = layer->H;
         }
         if (count != (size_t)N * width) throw cn_error(CN_ERR_SHAPE, "cn_layer_read: count != T*PS*width");
-        const Scratch scratch(count * sizeof(float));
-        float *tmp = scratch.get();
-        const int R = layer->dirs * 4 * layer->Hp, Hp = layer->Hp, H = layer->H;
-        switch (which) {
-        case CN_BUF_OUTPUTS:
-            if (layer->kind == CN_LAYER_INPUT)        // the operand copy of the inputs (bf16 mode: rounded to bf16)
-                launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            else if (layer->lstm)     // (a marked layer: the sum its followers read)
-                for (int d = 0; d < layer->dirs; ++d) launch_unpad(c->stream, opbf, follower_operand(layer), layer->Lp, d * Hp, 1, N, H, tmp, layer->size, d * H, c->PS, c->PSp);
-            else if (layer->summed) launch_unpad(c->stream, opbf, layer->res_sum, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            else if (layer->trainable) launch_unpad(c->stream, false, posteriors(layer), layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            else if (layer->context) launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
+        if (which == CN_BUF_OUTPUTS) {
+            // what the followers read (bf16 mode: rounded to bf16; a marked layer: its sum); of a dense trainable layer that
+            // did not sum, its fp32 outputs
+            if (layer->kind == CN_LAYER_INPUT || layer->lstm || layer->summed || layer->context)
+                read_rows(c, follower_operand(layer), opbf, unit_map(layer), N, c->PS, c->PSp, host);
+            else if (layer->trainable) read_rows(c, posteriors(layer), false, unit_map(layer), N, c->PS, c->PSp, host);
             else throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no outputs");
-            break;
-        case CN_BUF_OUTPUT_ERRORS:
+            return;
+        }
+        if (which == CN_BUF_OUTPUT_ERRORS) {
             if (!layer->err) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no outputErrors");
             if (layer->mcc_pending) {     // the deferred multiclass error injection becomes visible here
                 launch_mcc_backward(c->stream, posteriors(layer), c->d_tcls, c->N, layer->size, layer->Lp, layer->err);
                 layer->mcc_pending = false;
             }
-            if (layer->lstm)
-                for (int d = 0; d < layer->dirs; ++d) launch_unpad(c->stream, false, layer->err, layer->Lp, d * Hp, 1, N, H, tmp, layer->size, d * H, c->PS, c->PSp);
-            else if (layer->err_in_delta)      // fused softmax backward in bf16 mode: only the operand copy exists
-                launch_unpad(c->stream, true, layer->delta_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            else launch_unpad(c->stream, false, layer->err, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-            break;
+            const bool in_delta = !layer->lstm && layer->err_in_delta;      // fused softmax backward in bf16 mode: only the operand copy exists
+            read_rows(c, in_delta ? layer->delta_op : (const void *)layer->err, in_delta, unit_map(layer), N, c->PS, c->PSp, host);
+            return;
+        }
+        const Scratch scratch(count * sizeof(float));
+        float *tmp = scratch.get();
+        const int R = layer->dirs * 4 * layer->Hp, Hp = layer->Hp, H = layer->H;
+        switch (which) {
         case CN_BUF_LSTM_CELL_STATES:
             launch_unpad(c->stream, false, layer->cell, layer->Lp, dir * Hp, 1, N, H, tmp, H, 0, c->PS, c->PSp); break;
         case CN_BUF_LSTM_TMP_OUTPUTS:
@@ -3127,15 +3126,7 @@ int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count)
         if (!layer->summed) throw cn_error(CN_ERR_STATE, "cn_dbg_residual_branch: the layer's last forward pass did not sum");
         const int N = c->Next;
         if (count != (size_t)N * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_dbg_residual_branch: count != T*PS*size");
-        const Scratch scratch(count * sizeof(float));
-        float *tmp = scratch.get();
-        const bool opbf = !c->f32;
-        if (layer->lstm)
-            for (int d = 0; d < layer->dirs; ++d)
-                launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, d * layer->Hp, 1, N, layer->H, tmp, layer->size, d * layer->H, c->PS, c->PSp);
-        else launch_unpad(c->stream, opbf, layer->out_op, layer->Lp, 0, 1, N, layer->size, tmp, layer->size, 0, c->PS, c->PSp);
-        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
+        read_rows(c, layer->out_op, !c->f32, unit_map(layer), N, c->PS, c->PSp, host);
     });
 }
 
@@ -3168,15 +3159,8 @@ int cn_dbg_layer_norm_input(cn_layer *layer, float *host, size_t count)
         // the geometry of the forward pass that wrote the copy (its record), not of whatever fraction is loaded now
         const LnArgs &a = layer->ln;
         const int frames = a.N / a.PSp * a.PS;
-        if (count != (size_t)frames * a.P) throw cn_error(CN_ERR_SHAPE, "cn_dbg_layer_norm_input: count != T*PS*size of the preceding layer (of that forward pass)");
-        const Scratch scratch(count * sizeof(float));
-        float *tmp = scratch.get();
-        const bool opbf = !c->f32;
-        if (a.prevH)
-            for (int d = 0; d < a.prevDirs; ++d) launch_unpad(c->stream, opbf, layer->in_norm, a.Pp, d * a.prevHp, 1, frames, a.prevH, tmp, a.P, d * a.prevH, a.PS, a.PSp);
-        else launch_unpad(c->stream, opbf, layer->in_norm, a.Pp, 0, 1, frames, a.P, tmp, a.P, 0, a.PS, a.PSp);
-        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (count != (size_t)frames * a.prev.L) throw cn_error(CN_ERR_SHAPE, "cn_dbg_layer_norm_input: count != T*PS*size of the preceding layer (of that forward pass)");
+        read_rows(c, layer->in_norm, !c->f32, a.prev, frames, a.PS, a.PSp, host);
     });
 }
 
@@ -3213,15 +3197,8 @@ int cn_dbg_dropout_input(cn_layer *layer, float *host, size_t count)
         // the geometry of the forward pass that wrote the copy (its record), not of whatever fraction is loaded now
         const DropArgs &a = layer->drop;
         const int frames = a.N / a.PSp * a.PS;
-        if (count != (size_t)frames * a.P) throw cn_error(CN_ERR_SHAPE, "cn_dbg_dropout_input: count != T*PS*size of the preceding layer (of that forward pass)");
-        const Scratch scratch(count * sizeof(float));
-        float *tmp = scratch.get();
-        const bool opbf = !c->f32;
-        if (a.prevH)
-            for (int d = 0; d < a.prevDirs; ++d) launch_unpad(c->stream, opbf, layer->in_drop, a.Pp, d * a.prevHp, 1, frames, a.prevH, tmp, a.P, d * a.prevH, a.PS, a.PSp);
-        else launch_unpad(c->stream, opbf, layer->in_drop, a.Pp, 0, 1, frames, a.P, tmp, a.P, 0, a.PS, a.PSp);
-        HIP_CHECK(hipMemcpyAsync(host, tmp, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (count != (size_t)frames * a.prev.L) throw cn_error(CN_ERR_SHAPE, "cn_dbg_dropout_input: count != T*PS*size of the preceding layer (of that forward pass)");
+        read_rows(c, layer->in_drop, !c->f32, a.prev, frames, a.PS, a.PSp, host);
     });
 }
 
@@ -3296,10 +3273,8 @@ int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count)
             return out;
         };
         NoiseUnpackGeom g{};
-        g.lstm = layer->lstm ? 1 : 0; g.P = layer->P; g.Pp = layer->Pp; g.L = layer->size; g.Lp = layer->Lp;
-        g.dirs = layer->dirs; g.H = layer->H; g.Hp = layer->Hp;
-        g.prevH = layer->prev->lstm ? layer->prev->H : 0; g.prevHp = layer->prev->lstm ? layer->prev->Hp : 0;
-        g.prevDirs = layer->prev->lstm ? layer->prev->dirs : 0;
+        g.lstm = layer->lstm ? 1 : 0; g.L = layer->size; g.Lp = layer->Lp;
+        g.dirs = layer->dirs; g.H = layer->H; g.Hp = layer->Hp; g.prev = unit_map(layer->prev);
         const size_t R = (size_t)layer->dirs * 4 * layer->Hp;
         const std::vector<float> WinT = fetch(layer->nWinT, layer->lstm ? R * layer->Pp : (size_t)layer->Lp * layer->Pp);
         std::vector<float> WrecT, peep;

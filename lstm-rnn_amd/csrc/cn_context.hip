@@ -7,8 +7,7 @@
 //   context_bwd_kernel   dx[ts][s][u] (fp32) = the sum of e[j][s][b * P + u] over the (b, j) that read frame ts, b ascending, then
 //                        j ascending, single fp32 additions from +0.0f; zeros on every other row below N and in pad columns
 // All three are streaming kernels: grid-stride loops, no LDS, no atomics.  The context layer's rows are dense (unit u of block b
-// at column b * P + u); the predecessor's may be split (a blstm: direction d's unit j at d * Hp + j), which res_col / res_unit of
-// cn_unit_map_device.h translate.
+// at column b * P + u); the predecessor's may be split (a blstm), which its map (cn_unit_map.h) translates.
 //
 // Thread map, as in cn_splice.hip: a thread owns VEC neighbouring columns of one row and stores them as one 16-byte piece (the
 // gather: 4 fp32 / 8 bf16 operands of a context row; the fold: 4 fp32 of a predecessor row), neighbouring threads own
@@ -21,7 +20,6 @@
 #include <type_traits>
 
 #include "cn_internal.h"
-#include "cn_unit_map_device.h"
 
 namespace cn {
 
@@ -45,7 +43,7 @@ __global__ __launch_bounds__(256) void context_fwd_kernel(ContextArgs a, const i
     typedef typename std::conditional<F32, unsigned, unsigned short>::type op_t;      // (the bits of an operand: nothing is rounded)
     static_assert(VEC * sizeof(op_t) == 16, "a piece is 16 bytes");
     const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    const int pieces = a.Lp / VEC, width = a.B * a.P;
+    const int pieces = a.Lp / VEC, width = a.B * a.prev.L;
     const long total = (long)a.T * a.PSp * pieces;
     for (long idx = tid; idx < total; idx += nth) {
         const long n = idx / pieces; const int c0 = (int)(idx % pieces) * VEC;
@@ -53,10 +51,10 @@ __global__ __launch_bounds__(256) void context_fwd_kernel(ContextArgs a, const i
         const int ln = len[s];
         const bool live = t < ln && c0 < width;           // (no holes: the real frames of a slot are t = 0 .. len - 1)
         int b = 0, u = 0;                                  // block and unit of the piece's first column
-        if (live) { b = c0 / a.P; u = c0 - b * a.P; }
+        if (live) { b = c0 / a.prev.L; u = c0 - b * a.prev.L; }
         if constexpr (RUN) {
             uint4 o = make_uint4(0u, 0u, 0u, 0u);
-            if (live) o = *(const uint4 *)((const op_t *)x + ((long)context_src(a, t, b, ln) * a.PSp + s) * a.xLp + res_col(u, a.xH, a.xHp));
+            if (live) o = *(const uint4 *)((const op_t *)x + ((long)context_src(a, t, b, ln) * a.PSp + s) * a.prev.Lp + a.prev.col(u));
             *(uint4 *)((op_t *)out + n * a.Lp + c0) = o;
         } else {
             union { op_t e[VEC]; uint4 q; } v;
@@ -64,8 +62,8 @@ __global__ __launch_bounds__(256) void context_fwd_kernel(ContextArgs a, const i
             for (int i = 0; i < VEC; ++i) {
                 op_t w = 0;
                 if (live && c0 + i < width) {
-                    w = ((const op_t *)x)[((long)context_src(a, t, b, ln) * a.PSp + s) * a.xLp + res_col(u, a.xH, a.xHp)];
-                    if (++u == a.P) { u = 0; ++b; }
+                    w = ((const op_t *)x)[((long)context_src(a, t, b, ln) * a.PSp + s) * a.prev.Lp + a.prev.col(u)];
+                    if (++u == a.prev.L) { u = 0; ++b; }
                 }
                 v.e[i] = w;
             }
@@ -79,16 +77,15 @@ __global__ __launch_bounds__(256) void context_bwd_kernel(ContextArgs a, const i
 {
     constexpr int VEC = 4;                                  // a piece is four fp32
     const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    const int pieces = a.xLp / VEC;
+    const int pieces = a.prev.Lp / VEC;
     const long total = (long)a.T * a.PSp * pieces;
     for (long idx = tid; idx < total; idx += nth) {
         const long n = idx / pieces; const int c0 = (int)(idx % pieces) * VEC;
         const int t = (int)(n / a.PSp), s = (int)(n % a.PSp);
         const int ln = len[s];
-        // the units of the piece's columns: consecutive from u0, the first cnt columns (Hp is a multiple of 32: a piece lies in one
-        // direction and its pad columns come last); RUN: all four or none
-        const int u0 = res_unit(c0, a.P, a.xH, a.xHp, a.xdirs);
-        const int cnt = res_units_in_group(c0, VEC, a.P, a.xH, a.xHp, a.xdirs);
+        // the units of the piece's columns: consecutive from u0, the first cnt columns (cn_unit_map.h); RUN: all four or none
+        const int u0 = a.prev.unit(c0);
+        const int cnt = a.prev.units_in_group(c0, VEC);
         float acc[VEC];
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(256) void context_bwd_kernel(ContextArgs a, const i
                 const int o = (b - a.left) * a.dil;
                 const int jlo = max(t == 0 ? 0 : t - o, 0), jhi = min(t == ln - 1 ? ln - 1 : t - o, ln - 1);
                 for (int j = jlo; j <= jhi; ++j) {
-                    const float *p = e + ((long)j * a.PSp + s) * a.Lp + b * a.P + u0;
+                    const float *p = e + ((long)j * a.PSp + s) * a.Lp + b * a.prev.L + u0;
                     if constexpr (RUN) {
                         const float4 v = *(const float4 *)p;
                         acc[0] = __fadd_rn(acc[0], v.x); acc[1] = __fadd_rn(acc[1], v.y); acc[2] = __fadd_rn(acc[2], v.z); acc[3] = __fadd_rn(acc[3], v.w);
@@ -110,13 +107,13 @@ __global__ __launch_bounds__(256) void context_bwd_kernel(ContextArgs a, const i
                 }
             }
         }
-        *(float4 *)(dx + n * a.xLp + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        *(float4 *)(dx + n * a.prev.Lp + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
 }
 
 static int context_blocks(long work) { long b = (work + 255) / 256; return (int)(b > 2048 ? 2048 : b); }
 // is every piece of `vec` elements one run: every block of P units and every direction of a split predecessor a whole number of them
-static bool context_runs(const ContextArgs &a, int vec) { return a.P % vec == 0 && a.xH % vec == 0; }
+static bool context_runs(const ContextArgs &a, int vec) { return a.prev.L % vec == 0 && a.prev.H % vec == 0; }
 
 void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int *len)
 {
@@ -140,7 +137,7 @@ void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, con
 {
     const long rows = (long)a.T * a.PSp; if (rows <= 0) return;
     const bool runs = context_runs(a, 4) && ((size_t)e & 15) == 0;
-    const int blocks = context_blocks(rows * (a.xLp / 4));
+    const int blocks = context_blocks(rows * (a.prev.Lp / 4));
     if (runs) hipLaunchKernelGGL(context_bwd_kernel<true>, dim3(blocks), dim3(256), 0, s, a, len, e, dx);
     else      hipLaunchKernelGGL(context_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, a, len, e, dx);
 }

@@ -30,20 +30,6 @@ template <bool F32> __device__ __forceinline__ void st_op(void *base, long idx, 
     if constexpr (F32) ((float *)base)[idx] = v; else ((__bf16 *)base)[idx] = (__bf16)v;
 }
 
-// reference feature index of a padded column of the preceding layer's output, -1 for padding.
-// An LSTM layer stores direction d at columns [d*Hp, d*Hp+H); every other layer is dense.
-__device__ __forceinline__ int unpad_col(int pc, int P, int prevH, int prevHp, int prevDirs)
-{
-    if (prevH == 0) return pc < P ? pc : -1;
-    int dd = pc / prevHp, jj = pc % prevHp;
-    return (dd < prevDirs && jj < prevH) ? dd * prevH + jj : -1;
-}
-__device__ __forceinline__ int pad_col(int i, int prevH, int prevHp)
-{
-    if (prevH == 0) return i;
-    return (i / prevH) * prevHp + (i % prevH);
-}
-
 // ---------------------------------------------------------------------------------------------
 // LSTM weight packing (flat layout: LstmLayer.hpp:36-55, LstmLayer.cu:535-541,583-596)
 // ---------------------------------------------------------------------------------------------
@@ -207,7 +193,7 @@ __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, co
                                                void *Wrec, void *WrecT, float *bias_p, float *peep_p, int first, int count,
                                                const U &upd = U{}, const PackGrad &pg = PackGrad{})
 {
-    const int P = g.P, Pp = g.Pp, L = g.L, H = g.H, Hp = g.Hp, dirs = g.dirs;
+    const int P = g.prev.L, Pp = g.prev.Lp, L = g.L, H = g.H, Hp = g.Hp, dirs = g.dirs;
     const long R = (long)dirs * 4 * Hp;                 // packed gate rows
     const long nIn = R * Pp, nRec = (long)dirs * 4 * Hp * Hp, nB = (long)dirs * 4 * Hp, nPe = (long)dirs * 3 * Hp;
     const long total = nIn + nRec + nB + nPe;
@@ -217,7 +203,7 @@ __device__ __forceinline__ void lstm_pack_body(const LstmGeom &g, float bias, co
             // one unit with a single 16-byte access
             const int r = idx / Pp, pc = idx % Pp;
             const int d = r / (4 * Hp), j = (r / 4) % Hp, gg = r % 4;
-            const int i = unpad_col(pc, P, g.prevH, g.prevHp, g.prevDirs);
+            const int i = g.prev.unit(pc);
             float v = 0.f;
             if (j < H && i >= 0) v = pack_fetch<UPD>(w, upd, (long)gg * L * P + (long)d * H * P + (long)j * P + i, pg.g_in + (long)r * Pp + pc, 1.0f,
                                                      &pg.f_in, (long)r * Pp + pc);   // dWin[r][pc]
@@ -257,7 +243,7 @@ __global__ void lstm_pack_kernel(LstmGeom g, float bias, const float *w, void *W
 void launch_lstm_pack(hipStream_t s, bool f32, const LstmGeom &g, float bias, const float *w,
                       void *Win, void *WinT, void *Wrec, void *WrecT, float *bias_p, float *peep_p)
 {
-    long total = (long)g.dirs * 4 * g.Hp * (g.Pp + g.Hp + 1) + (long)g.dirs * 3 * g.Hp;
+    long total = (long)g.dirs * 4 * g.Hp * (g.prev.Lp + g.Hp + 1) + (long)g.dirs * 3 * g.Hp;
     int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
     if (f32) hipLaunchKernelGGL(lstm_pack_kernel<true>, dim3(blocks), dim3(256), 0, s, g, bias, w, Win, WinT, Wrec, WrecT, bias_p, peep_p);
     else     hipLaunchKernelGGL(lstm_pack_kernel<false>, dim3(blocks), dim3(256), 0, s, g, bias, w, Win, WinT, Wrec, WrecT, bias_p, peep_p);
@@ -268,7 +254,7 @@ void launch_lstm_pack(hipStream_t s, bool f32, const LstmGeom &g, float bias, co
 // a separate memset (padded entries only ever receive exact zeros).
 __global__ void lstm_unpack_kernel(LstmGeom g, float *dWin, float *dWrec, float *dbias, float *dpeep, float *wu)
 {
-    const int P = g.P, Pp = g.Pp, L = g.L, H = g.H, Hp = g.Hp;
+    const int P = g.prev.L, Pp = g.prev.Lp, L = g.L, H = g.H, Hp = g.Hp;
     const long nIn = 4L * L * P, nB = 4L * L, nRec = 4L * L * H, nPe = 3L * L;
     const long total = nIn + nB + nRec + nPe;
     for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -276,7 +262,7 @@ __global__ void lstm_unpack_kernel(LstmGeom g, float *dWin, float *dWrec, float 
         if (idx < nIn) {
             const int gg = idx / ((long)L * P), rem = idx % ((long)L * P);
             const int blk = rem / P, i = rem % P, d = blk / H, j = blk % H;
-            float *src = &dWin[(((long)d * Hp + j) * 4 + gg) * Pp + pad_col(i, g.prevH, g.prevHp)];
+            float *src = &dWin[(((long)d * Hp + j) * 4 + gg) * Pp + g.prev.col(i)];
             v = *src; *src = 0.f;
         } else if (idx < nIn + nB) {
             const int k = idx - nIn, gg = k / L, blk = k % L, d = blk / H, j = blk % H;
@@ -299,7 +285,7 @@ __global__ void lstm_unpack_kernel(LstmGeom g, float *dWin, float *dWrec, float 
 
 void launch_lstm_unpack_grads(hipStream_t s, const LstmGeom &g, float *dWin, float *dWrec, float *dbias, float *dpeep, float *wu, hipEvent_t done)
 {
-    long total = (long)g.L * (4 * (g.P + 1) + 4 * g.H + 3);
+    long total = (long)g.L * (4 * (g.prev.L + 1) + 4 * g.H + 3);
     int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipExtLaunchKernelGGL(lstm_unpack_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, g, dWin, dWrec, dbias, dpeep, wu);
 }
@@ -312,18 +298,19 @@ template <bool F32, int UPD = 0, class U = PackUpd>
 __device__ __forceinline__ void ff_pack_body(const FfGeom &g, float bias, const float *w, void *W, void *WT, float *bias_p, int first, int count,
                                              const U &upd = U{}, const PackGrad &pg = PackGrad{})
 {
-    const long nW = (long)g.Lp * g.Pp, total = nW + g.Lp;
+    const int P = g.prev.L, Pp = g.prev.Lp;
+    const long nW = (long)g.Lp * Pp, total = nW + g.Lp;
     for (long idx = (blockIdx.x - first) * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)count * blockDim.x) {
         if (idx < nW) {
-            const int j = idx / g.Pp, pc = idx % g.Pp;
-            const int i = unpad_col(pc, g.P, g.prevH, g.prevHp, g.prevDirs);
-            float v = (j < g.L && i >= 0) ? pack_fetch<UPD>(w, upd, (long)j * g.P + i, pg.g_in + (long)j * g.Pp + pc, 1.0f, &pg.f_in, (long)j * g.Pp + pc) : 0.f;
-            if constexpr (UPD != 5) st_op<F32>(W, (long)j * g.Pp + pc, v);
+            const int j = idx / Pp, pc = idx % Pp;
+            const int i = g.prev.unit(pc);
+            float v = (j < g.L && i >= 0) ? pack_fetch<UPD>(w, upd, (long)j * P + i, pg.g_in + (long)j * Pp + pc, 1.0f, &pg.f_in, (long)j * Pp + pc) : 0.f;
+            if constexpr (UPD != 5) st_op<F32>(W, (long)j * Pp + pc, v);
             st_op<F32>(WT, (long)pc * g.Lp + j, v);
         } else {
             if constexpr (UPD == 5) continue;
             const int j = idx - nW;
-            bias_p[j] = (j < g.L) ? bias * pack_fetch<UPD, false>(w, upd, (long)g.L * g.P + j, pg.g_bias + j, bias, &pg.f_bias, j) : 0.f;            // FeedForwardLayer.cu:59
+            bias_p[j] = (j < g.L) ? bias * pack_fetch<UPD, false>(w, upd, (long)g.L * P + j, pg.g_bias + j, bias, &pg.f_bias, j) : 0.f;            // FeedForwardLayer.cu:59
         }
     }
 }
@@ -463,8 +450,8 @@ static int pack_group_blocks(PackGroup &grp)
     int blocks = 0;
     for (int i = 0; i < grp.n; ++i) {
         const PackItem &it = grp.item[i];
-        const long total = it.lstm ? (long)it.lg.dirs * 4 * it.lg.Hp * (it.lg.Pp + it.lg.Hp + 1) + (long)it.lg.dirs * 3 * it.lg.Hp
-                                   : (long)it.fg.Lp * it.fg.Pp + it.fg.Lp;
+        const long total = it.lstm ? (long)it.lg.dirs * 4 * it.lg.Hp * (it.lg.prev.Lp + it.lg.Hp + 1) + (long)it.lg.dirs * 3 * it.lg.Hp
+                                   : (long)it.fg.Lp * it.fg.prev.Lp + it.fg.Lp;
         int b = (int)((total + 255) / 256); if (b > 1024) b = 1024;
         grp.first[i] = blocks; blocks += b;
     }
@@ -525,7 +512,7 @@ void launch_pack_group_noise(hipStream_t s, bool f32, PackGroup &grp, const Pack
 }
 void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const float *w, void *W, void *WT, float *bias_p)
 {
-    long total = (long)g.Lp * g.Pp + g.Lp;
+    long total = (long)g.Lp * g.prev.Lp + g.Lp;
     int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
     if (f32) hipLaunchKernelGGL(ff_pack_kernel<true>, dim3(blocks), dim3(256), 0, s, g, bias, w, W, WT, bias_p);
     else     hipLaunchKernelGGL(ff_pack_kernel<false>, dim3(blocks), dim3(256), 0, s, g, bias, w, W, WT, bias_p);
@@ -533,11 +520,12 @@ void launch_ff_pack(hipStream_t s, bool f32, const FfGeom &g, float bias, const 
 
 __global__ void ff_unpack_kernel(FfGeom g, float bias, float *dW, float *colsum, float *wu)
 {
-    const long nW = (long)g.L * g.P, total = nW + g.L;
+    const int P = g.prev.L;
+    const long nW = (long)g.L * P, total = nW + g.L;
     for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         if (idx < nW) {
-            const int j = idx / g.P, i = idx % g.P;
-            float *src = &dW[(long)j * g.Pp + pad_col(i, g.prevH, g.prevHp)];
+            const int j = idx / P, i = idx % P;
+            float *src = &dW[(long)j * g.prev.Lp + g.prev.col(i)];
             wu[idx] = *src; *src = 0.f;
         } else {
             wu[idx] = bias * colsum[idx - nW];                                     // FeedForwardLayer.cu:94-100
@@ -547,7 +535,7 @@ __global__ void ff_unpack_kernel(FfGeom g, float bias, float *dW, float *colsum,
 }
 void launch_ff_unpack_grads(hipStream_t s, const FfGeom &g, float bias, float *dW, float *colsum, float *wu, hipEvent_t done)
 {
-    long total = (long)g.L * (g.P + 1);
+    long total = (long)g.L * (g.prev.L + 1);
     int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipExtLaunchKernelGGL(ff_unpack_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, g, bias, dW, colsum, wu);
 }
@@ -673,26 +661,26 @@ void launch_unpad(hipStream_t s, bool src_is_bf16, const void *src, long ld, int
     else             hipLaunchKernelGGL(unpad_kernel<false>, dim3(blocks), dim3(256), 0, s, src, ld, col0, cstride, N, L, dst, ldd, dcol0, PS, PSp);
 }
 
-__global__ void pad_f32_kernel(const float *src, int N, int L, float *dst, long ld, int prevH, int prevHp, int PS, int PSp)
+__global__ void pad_f32_kernel(const float *src, int N, float *dst, UnitMap m, int PS, int PSp)
 {
-    const long total = (long)N * L;
+    const long total = (long)N * m.L;
     for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long n = idx / L; const int j = idx % L;
-        dst[((n / PS) * PSp + n % PS) * ld + pad_col(j, prevH, prevHp)] = src[idx];
+        const long n = idx / m.L; const int j = idx % m.L;
+        dst[((n / PS) * PSp + n % PS) * m.Lp + m.col(j)] = src[idx];
     }
 }
-void launch_pad_f32(hipStream_t s, const float *src, int N, int L, float *dst, long ld, int prevH, int prevHp, int PS, int PSp)
+void launch_pad_f32(hipStream_t s, const float *src, int N, float *dst, const UnitMap &m, int PS, int PSp)
 {
-    long total = (long)N * L; if (total <= 0) return;
+    long total = (long)N * m.L; if (total <= 0) return;
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pad_f32_kernel, dim3(blocks), dim3(256), 0, s, src, N, L, dst, ld, prevH, prevHp, PS, PSp);
+    hipLaunchKernelGGL(pad_f32_kernel, dim3(blocks), dim3(256), 0, s, src, N, dst, m, PS, PSp);
 }
 
 // ---------------------------------------------------------------------------------------------
 // dropout on a layer's input (include/currennt_hip.h, section Dropout): the mask is a pure function of (key, frame, unit) in the
 // REFERENCE layout, so both kernels first undo the padding of their element.  Plain streaming kernels: one thread owns four
-// neighbouring padded columns of one row (Pp and every direction's pitch are multiples of 4, so the four lie in one direction)
-// and moves them with one 8-byte (bf16) or 16-byte (fp32) load and store.
+// neighbouring padded columns of one row (a group of cn_unit_map.h) and moves them with one 8-byte (bf16) or 16-byte (fp32) load
+// and store.
 // ---------------------------------------------------------------------------------------------
 // Bit k of the result: padded element (row, pc + k) is a kept unit of a real slot.  Four reference units share one Philox call
 // (counter word 0 = unit >> 2).  The four columns are the units base .. base + 3 of the reference layout; they straddle two
@@ -701,14 +689,9 @@ __device__ __forceinline__ unsigned drop_keep4(const DropArgs &a, long row, int 
 {
     const long t = row / a.PSp; const int ps = (int)(row % a.PSp);
     if (ps >= a.PS) return 0u;
-    int base, cnt;                                        // first unit, units among the four columns
-    if (a.prevH == 0) { base = pc; cnt = a.P - pc; }
-    else {
-        const int dd = pc / a.prevHp, jj = pc % a.prevHp;
-        base = dd * a.prevH + jj; cnt = dd < a.prevDirs ? a.prevH - jj : 0;
-    }
+    const int cnt = a.prev.units_in_group(pc, 4);         // units among the four columns: base, base + 1, ...
     if (cnt <= 0) return 0u;
-    cnt = min(cnt, 4);
+    const int base = a.prev.unit(pc);
     const uint32_t n = (uint32_t)(t * a.PS + ps);
     const int sh = base & 3;
     const uint4 w0 = philox4x32_10(make_uint4((uint32_t)(base >> 2), n, a.pass_lo, a.pass_hi), a.k0, a.k1);
@@ -728,11 +711,11 @@ __device__ __forceinline__ unsigned drop_keep4(const DropArgs &a, long row, int 
 template <bool F32>
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(DropArgs a, const void *__restrict__ src, void *__restrict__ dst)
 {
-    const int q = a.Pp >> 2;
+    const int q = a.prev.Lp >> 2;
     const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (idx >= (long)a.N * q) return;
     const long row = idx / q; const int pc = (int)(idx % q) << 2;
-    const long off = row * a.Pp + pc;
+    const long off = row * a.prev.Lp + pc;
     const unsigned keep = drop_keep4(a, row, pc);
     if constexpr (F32) {
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -755,11 +738,11 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(DropArgs a, const void
 }
 __global__ __launch_bounds__(256) void dropout_bwd_kernel(DropArgs a, float *__restrict__ err)
 {
-    const int q = a.Pp >> 2;
+    const int q = a.prev.Lp >> 2;
     const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (idx >= (long)a.N * q) return;
     const long row = idx / q; const int pc = (int)(idx % q) << 2;
-    float4 *p = (float4 *)(err + row * a.Pp + pc);
+    float4 *p = (float4 *)(err + row * a.prev.Lp + pc);
     const unsigned keep = drop_keep4(a, row, pc);
     float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
     if (keep) x = *p;
@@ -767,7 +750,7 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(DropArgs a, float *__r
     x.z = (keep & 4u) ? x.z * a.scale : 0.f; x.w = (keep & 8u) ? x.w * a.scale : 0.f;
     *p = x;
 }
-static int dropout_blocks(const DropArgs &a) { return (int)(((long)a.N * (a.Pp >> 2) + 255) / 256); }
+static int dropout_blocks(const DropArgs &a) { return (int)(((long)a.N * (a.prev.Lp >> 2) + 255) / 256); }
 void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *src, void *dst)
 {
     const int blocks = dropout_blocks(a); if (blocks <= 0) return;

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/currennt_hip.h"
+#include "cn_unit_map.h"
 
 namespace cn {
 
@@ -219,7 +220,9 @@ int lstm_cluster_bwd_cus(int prec, const LstmRec &p);     // CUs the backward cl
 void lstm_cluster_stream_gone(hipStream_t s);         // cn_ctx_destroy: the per-device launch gate forgets the stream
 
 // ---- element-wise / packing kernels -----------------------------------------------------------
-struct LstmGeom { int P, Pp, L, H, Hp, dirs; int prevH, prevHp, prevDirs; /* prevH=0: identity column map */ };
+// (prev, here and in every struct below: the map of the preceding layer's rows, cn_unit_map.h -- its L units are this layer's
+// inputs, its Lp columns the pitch of the input operand)
+struct LstmGeom { int L, H, Hp, dirs; UnitMap prev; };
 
 // flat fp32 reference weights -> packed op copies + fp32 bias/peephole vectors
 void launch_lstm_pack(hipStream_t s, bool f32, const LstmGeom &g, float bias, const float *w,
@@ -227,7 +230,7 @@ void launch_lstm_pack(hipStream_t s, bool f32, const LstmGeom &g, float bias, co
 // packed fp32 gradients -> flat reference layout
 // (the packed accumulators are cleared as they are read)
 void launch_lstm_unpack_grads(hipStream_t s, const LstmGeom &g, float *dWin, float *dWrec, float *dbias, float *dpeep, float *wu, hipEvent_t done = nullptr);
-struct FfGeom { int P, Pp, L, Lp; int prevH, prevHp, prevDirs; };
+struct FfGeom { int L, Lp; UnitMap prev; };
 // all trainable layers' operand copies in one launch
 constexpr int PACK_GROUP_MAX = 8;
 // deterministic mode, update == 2: where the partial sums of one packed gradient array lie (nparts == 0: read the packed
@@ -313,10 +316,9 @@ void launch_fraction_load_splice(hipStream_t s, bool f32, const AugArgs &a, bool
                                  void *dst, int Pp, int *rm, int maxN, int Tmin_net);
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
 // The key of one forward pass of one layer, and the geometry that maps a padded element to the reference (frame, unit) the mask
-// is stated in: row r = t * PSp + ps <-> frame n = t * PS + ps (pad slots ps >= PS: zeros); column -> unit as unpad_col does
-// (prevH = 0: dense, units [0, P); else direction d's units at columns [d * prevHp, d * prevHp + prevH)).  Pp is a multiple of 4.
+// is stated in: row r = t * PSp + ps <-> frame n = t * PS + ps (pad slots ps >= PS: zeros); column -> unit by the map of the rows
 struct DropArgs {
-    int N, PS, PSp, P, Pp, prevH, prevHp, prevDirs;
+    int N, PS, PSp; UnitMap prev;
     uint32_t k0, k1, pass_lo, pass_hi, thr;    // Philox key ((seed_lo + ordinal), seed_hi), counter words 2 and 3, keep threshold
     float scale;
 };
@@ -325,25 +327,22 @@ void launch_dropout_fwd(hipStream_t s, bool f32, const DropArgs &a, const void *
 // err[N][Pp] (fp32) masked and rescaled in place with the same key
 void launch_dropout_bwd(hipStream_t s, const DropArgs &a, float *err);
 // ---- layer normalization of a layer's input (include/currennt_hip.h, section Layer normalization; cn_layernorm.hip) ----
-// The geometry of one forward pass of one marked layer: N = T * PSp rows of Pp columns holding the preceding layer's P units
-// (prevH = 0: dense, units [0, P); else direction d's units at columns [d * prevHp, d * prevHp + prevH)); Pp and prevHp are
-// multiples of 32.  PS / PSp: slots per time step without and with pad slots (what the debug hook unpads with).
+// The geometry of one forward pass of one marked layer: N = T * PSp rows of the preceding layer's map.  PS / PSp: slots per time
+// step without and with pad slots (what the debug hook unpads with).
 struct LnArgs {
-    int N, P, Pp, prevH, prevHp, prevDirs, PS, PSp;
+    int N, PS, PSp; UnitMap prev;
     float eps;
 };
-// xn[N][Pp] (op) = the normalised x[N][Pp] (op) on the rows with pat[row] != 0, zeros on the other rows (dummy frames, pad slots)
+// (Pp = prev.Lp)  xn[N][Pp] (op) = the normalised x[N][Pp] (op) on the rows with pat[row] != 0, zeros on the other rows (dummy frames, pad slots)
 // and in pad columns; rstd[N]: 1 / sqrt(var + eps) of every real row as a float, 0 elsewhere
 void launch_layernorm_fwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *x, void *xn, float *rstd);
 // err[N][Pp] (fp32), dL/d xn, rewritten in place as dL/dx from the forward pass's xn and rstd; zeros on the rows with pat[row] == 0
 void launch_layernorm_bwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *xn, const float *rstd, float *err);
 // ---- residual connections (include/currennt_hip.h, section Residual connections; cn_residual.hip) ----
-// The geometry of one forward pass of one marked layer: N = T * PSp rows, L units in both layers; the marked layer's rows are Lp
-// wide with its units at the columns of (H, Hp, dirs), the preceding layer's xLp wide with (xH, xHp, xdirs) -- H = 0: a dense
-// layer or the input layer, unit u at column u; else direction d's units at columns [d * Hp, d * Hp + H).  same_map: unit u has
-// the same column in both (the 16-byte path).  Every row width and Hp is a multiple of 32.
+// The geometry of one forward pass of one marked layer: N = T * PSp rows; the marked layer's own map and the preceding layer's,
+// of the same L units (Lp = own.Lp, xLp = prev.Lp below).  same_map: unit u has the same column in both (the 16-byte path).
 struct ResArgs {
-    int N, L, Lp, H, Hp, dirs, xLp, xH, xHp, xdirs, same_map;
+    int N; UnitMap own, prev; int same_map;
 };
 // sum[N][Lp] (op) = branch[N][Lp] (op) + x[N][xLp] (op), one rounding to the operand type, on the rows with pat[row] != 0;
 // the branch on the other rows (dummy frames, pad slots); pad columns are written as zeros
@@ -352,11 +351,9 @@ void launch_residual_fwd(hipStream_t s, bool f32, const ResArgs &a, const char *
 void launch_residual_bwd(hipStream_t s, const ResArgs &a, const char *pat, const float *e, float *prev_err);
 // ---- context layers (include/currennt_hip.h, section Context layers; cn_context.hip) ----
 // The geometry of one forward pass of one context layer: T time steps of PSp slots; B = left + right + 1 blocks of the preceding
-// layer's P units in rows Lp = round_up(B * P, 32) wide, block b at columns [b * P, (b + 1) * P); the preceding layer's rows are
-// xLp wide with (xH, xHp, xdirs) -- xH = 0: a dense layer, the input layer or another context layer, unit u at column u; else
-// direction d's units at columns [d * xHp, d * xHp + xH).
+// layer's P = prev.L units in rows Lp = round_up(B * P, 32) wide, block b at columns [b * P, (b + 1) * P); xLp = prev.Lp below.
 struct ContextArgs {
-    int T, PSp, P, B, left, dil, Lp, xLp, xH, xHp, xdirs;
+    int T, PSp, B, left, dil, Lp; UnitMap prev;
 };
 // len[PSp]: the frames of every slot whose pattern type is not NONE, from pat[t * PSp + s], t < T (one wave per slot)
 void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int *len);
@@ -511,7 +508,7 @@ void launch_ctc_errors(hipStream_t s, const CtcArgs &a);
 // gather a padded row-major fp32/op matrix into the reference layout [N][L]
 // (host row n = t*PS + s maps to device row t*PSp + s)
 void launch_unpad(hipStream_t s, bool src_is_bf16, const void *src, long ld, int col0, int cstride, int N, int L, float *dst, long ldd, int dcol0, int PS, int PSp);
-// scatter host-provided [N][L] fp32 into a padded fp32 matrix (tests)
-void launch_pad_f32(hipStream_t s, const float *src, int N, int L, float *dst, long ld, int prevH, int prevHp, int PS, int PSp);
+// scatter host-provided [N][m.L] fp32 into the padded fp32 rows of map m (tests)
+void launch_pad_f32(hipStream_t s, const float *src, int N, float *dst, const UnitMap &m, int PS, int PSp);
 
 }  // namespace cn

@@ -10,10 +10,9 @@
 // over rows.  A lane owns 16 bytes of every 64-lane trip across the row (G columns); the row is loaded once and held in
 // registers across the statistics passes and the store (TRIPS = 1, 2, 4 or 8 trips, unrolled), and only a row wider than 2048
 // columns is read again per pass (TRIPS = 0).  Per-lane partial sums are doubles, the wave sum is a __shfl_xor butterfly: every lane
-// ends with the same bits.  The statistics run over the units of the reference layout (cn_unit_map_device.h), never over pad
+// ends with the same bits.  The statistics run over the units of the reference layout (cn_unit_map.h), never over pad
 // columns.  No LDS.
 #include "cn_internal.h"
-#include "cn_unit_map_device.h"
 
 namespace cn {
 
@@ -59,9 +58,9 @@ __device__ __forceinline__ LnGroup ln_group(const LnArgs &a, int t, int lane)
 {
     const int c = (t * 64 + lane) * G;
     LnGroup g;
-    g.inside = c < a.Pp;
-    g.c = g.inside ? c : a.Pp - G;
-    g.cnt = g.inside ? res_units_in_group(c, G, a.P, a.prevH, a.prevHp, a.prevDirs) : 0;
+    g.inside = c < a.prev.Lp;
+    g.c = g.inside ? c : a.prev.Lp - G;
+    g.cnt = g.inside ? a.prev.units_in_group(c, G) : 0;
     return g;
 }
 
@@ -73,8 +72,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnArgs a, const char
     constexpr bool HELD = TRIPS > 0;
     constexpr int NT = HELD ? TRIPS : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nt = HELD ? TRIPS : (a.Pp + 64 * G - 1) / (64 * G);
-    const double inv_p = 1.0 / (double)a.P;
+    const int nt = HELD ? TRIPS : (a.prev.Lp + 64 * G - 1) / (64 * G);
+    const double inv_p = 1.0 / (double)a.prev.L;
     LnGroup grp[NT];                                      // (HELD: the same for every row)
     if constexpr (HELD) {
 #pragma unroll
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnArgs a, const char
     }
     auto group = [&](int t) { if constexpr (HELD) return grp[t]; else return ln_group<G>(a, t, lane); };
     for (long row = (long)blockIdx.x * 4 + wave; row < a.N; row += (long)gridDim.x * 4) {
-        const long base = row * a.Pp;
+        const long base = row * a.prev.Lp;
         if (pat[row] == 0) {                              // dummy frame or pad slot (the wave's rows are its own: a uniform branch)
             const float z[G] = {};
 #pragma unroll NT
@@ -142,8 +141,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnArgs a, const char
     constexpr bool HELD = TRIPS > 0;
     constexpr int NT = HELD ? TRIPS : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nt = HELD ? TRIPS : (a.Pp + 64 * G - 1) / (64 * G);
-    const double inv_p = 1.0 / (double)a.P;
+    const int nt = HELD ? TRIPS : (a.prev.Lp + 64 * G - 1) / (64 * G);
+    const double inv_p = 1.0 / (double)a.prev.L;
     LnGroup grp[NT];
     if constexpr (HELD) {
 #pragma unroll
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(LnArgs a, const char
     }
     auto group = [&](int t) { if constexpr (HELD) return grp[t]; else return ln_group<G>(a, t, lane); };
     for (long row = (long)blockIdx.x * 4 + wave; row < a.N; row += (long)gridDim.x * 4) {
-        const long base = row * a.Pp;
+        const long base = row * a.prev.Lp;
         if (pat[row] == 0) {
 #pragma unroll NT
             for (int t = 0; t < (HELD ? NT : nt); ++t) {
@@ -212,14 +211,14 @@ static int ln_blocks(int N) { const int b = (N + 3) / 4; return b > 2048 ? 2048 
 void launch_layernorm_fwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *x, void *xn, float *rstd)
 {
     if (a.N <= 0) return;
-    const int blocks = ln_blocks(a.N), trips = ln_trips(a.Pp, f32 ? 4 : 8);
+    const int blocks = ln_blocks(a.N), trips = ln_trips(a.prev.Lp, f32 ? 4 : 8);
     if (f32) { LN_LAUNCH(layernorm_fwd_kernel, true, a, pat, x, xn, rstd) }
     else     { LN_LAUNCH(layernorm_fwd_kernel, false, a, pat, x, xn, rstd) }
 }
 void launch_layernorm_bwd(hipStream_t s, bool f32, const LnArgs &a, const char *pat, const void *xn, const float *rstd, float *err)
 {
     if (a.N <= 0) return;
-    const int blocks = ln_blocks(a.N), trips = ln_trips(a.Pp, 4);
+    const int blocks = ln_blocks(a.N), trips = ln_trips(a.prev.Lp, 4);
     if (f32) { LN_LAUNCH(layernorm_bwd_kernel, true, a, pat, xn, rstd, err) }
     else     { LN_LAUNCH(layernorm_bwd_kernel, false, a, pat, xn, rstd, err) }
 }

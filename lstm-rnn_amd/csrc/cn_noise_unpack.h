@@ -6,23 +6,16 @@
 #include <stddef.h>
 #include <vector>
 
+#include "cn_unit_map.h"
+
 namespace cn {
 
 struct NoiseUnpackGeom {
     int lstm;                             // 1: LSTM layer (dirs, H, Hp used), 0: dense layer (L, Lp used)
-    int P, Pp;                            // preceding layer's size / padded width
     int L, Lp;                            // layer size; dense layers: padded width
     int dirs, H, Hp;
-    int prevH, prevHp, prevDirs;          // prevH = 0: the preceding layer is dense (identity column map)
+    UnitMap prev;                         // the preceding layer's rows: the columns of WinT's rows
 };
-
-// reference feature of a padded column of the preceding layer's output, -1 for padding (unpad_col of cn_elementwise.hip)
-inline int noise_unpad_col(const NoiseUnpackGeom &g, int pc)
-{
-    if (g.prevH == 0) return pc < g.P ? pc : -1;
-    const int dd = pc / g.prevHp, jj = pc % g.prevHp;
-    return (dd < g.prevDirs && jj < g.prevH) ? dd * g.prevH + jj : -1;
-}
 
 // WinT: LSTM [Pp][dirs*4*Hp] (row r = (d*Hp + j)*4 + gate), dense [Pp][Lp]; WrecT: [dirs][Hp][4*Hp] (k = 4*j + gate contiguous);
 // peep: [dirs][3][Hp].  flat: the layer's weight vector, whose entries with a noisy counterpart are overwritten (the bias entries
@@ -31,10 +24,10 @@ inline size_t noise_unpack(const NoiseUnpackGeom &g, const std::vector<float> &W
                            const std::vector<float> &peep, std::vector<float> &flat)
 {
     size_t bad = 0;
-    const long P = g.P, L = g.L;
+    const long P = g.prev.L, L = g.L;
     if (!g.lstm) {
-        for (int pc = 0; pc < g.Pp; ++pc) {
-            const int i = noise_unpad_col(g, pc);
+        for (int pc = 0; pc < g.prev.Lp; ++pc) {
+            const int i = g.prev.unit(pc);
             for (int j = 0; j < g.Lp; ++j) {
                 const float v = WinT[(size_t)pc * g.Lp + j];
                 if (j < g.L && i >= 0) flat[(size_t)j * P + i] = v;
@@ -44,8 +37,8 @@ inline size_t noise_unpack(const NoiseUnpackGeom &g, const std::vector<float> &W
         return bad;
     }
     const long H = g.H, Hp = g.Hp, R = (long)g.dirs * 4 * Hp;
-    for (int pc = 0; pc < g.Pp; ++pc) {
-        const int i = noise_unpad_col(g, pc);
+    for (int pc = 0; pc < g.prev.Lp; ++pc) {
+        const int i = g.prev.unit(pc);
         for (long r = 0; r < R; ++r) {
             const long d = r / (4 * Hp), j = (r / 4) % Hp, gg = r % 4;
             const float v = WinT[(size_t)pc * R + r];

@@ -13,11 +13,12 @@ using namespace cn;
 static int failures = 0;
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
-static void check_lstm(int P, int Pp, int dirs, int H, int Hp, int prevH, int prevHp, int prevDirs)
+static void check_lstm(const UnitMap &prev, int dirs, int H, int Hp)
 {
+    const int P = prev.L, Pp = prev.Lp;
     NoiseUnpackGeom g{};
-    g.lstm = 1; g.P = P; g.Pp = Pp; g.L = dirs * H; g.Lp = dirs * Hp; g.dirs = dirs; g.H = H; g.Hp = Hp;
-    g.prevH = prevH; g.prevHp = prevHp; g.prevDirs = prevDirs;
+    g.lstm = 1; g.L = dirs * H; g.Lp = dirs * Hp; g.dirs = dirs; g.H = H; g.Hp = Hp;
+    g.prev = prev;
     const long L = g.L, R = (long)dirs * 4 * Hp;
     const size_t nw = (size_t)(L * (4 * (P + 1) + 4 * H + 3));
     std::vector<float> w(nw);
@@ -26,7 +27,7 @@ static void check_lstm(int P, int Pp, int dirs, int H, int Hp, int prevH, int pr
     for (long r = 0; r < R; ++r)
         for (int pc = 0; pc < Pp; ++pc) {
             const long d = r / (4 * Hp), j = (r / 4) % Hp, gg = r % 4;
-            const int i = noise_unpad_col(g, pc);
+            const int i = g.prev.unit(pc);
             if (j < H && i >= 0) WinT[(size_t)pc * R + r] = w[(size_t)(gg * L * P + d * H * P + j * P + i)];
         }
     for (long d = 0; d < dirs; ++d)
@@ -51,16 +52,17 @@ static void check_lstm(int P, int Pp, int dirs, int H, int Hp, int prevH, int pr
     }
 }
 
-static void check_ff(int P, int Pp, int L, int Lp, int prevH, int prevHp, int prevDirs)
+static void check_ff(const UnitMap &prev, int L, int Lp)
 {
+    const int P = prev.L, Pp = prev.Lp;
     NoiseUnpackGeom g{};
-    g.lstm = 0; g.P = P; g.Pp = Pp; g.L = L; g.Lp = Lp; g.dirs = 1; g.prevH = prevH; g.prevHp = prevHp; g.prevDirs = prevDirs;
+    g.lstm = 0; g.L = L; g.Lp = Lp; g.dirs = 1; g.prev = prev;
     const size_t nw = (size_t)L * (P + 1);
     std::vector<float> w(nw);
     for (size_t k = 0; k < nw; ++k) w[k] = 1.0f + (float)k;
     std::vector<float> WT((size_t)Pp * Lp, 0.f), none;
     for (int pc = 0; pc < Pp; ++pc) {
-        const int i = noise_unpad_col(g, pc);
+        const int i = g.prev.unit(pc);
         for (int j = 0; j < L; ++j) if (i >= 0) WT[(size_t)pc * Lp + j] = w[(size_t)j * P + i];
     }
     std::vector<float> flat(nw, -1.f);
@@ -74,11 +76,11 @@ static void check_ff(int P, int Pp, int L, int Lp, int prevH, int prevHp, int pr
 
 int main()
 {
-    check_lstm(5, 8, 2, 6, 32, 0, 0, 0);            // blstm 12 on a 5-wide input
-    check_lstm(12, 64, 1, 7, 32, 6, 32, 2);         // lstm 7 behind that blstm: columns of two padded directions
-    check_lstm(3, 4, 1, 32, 32, 0, 0, 0);           // no pad units
-    check_ff(7, 32, 6, 32, 7, 32, 1);               // feedforward 6 behind an lstm 7
-    check_ff(6, 32, 4, 32, 0, 0, 0);                // softmax 4 behind a dense layer
+    check_lstm({5, 8, 0, 0, 0}, 2, 6, 32);          // blstm 12 on a 5-wide input
+    check_lstm({12, 64, 6, 32, 2}, 1, 7, 32);       // lstm 7 behind that blstm: columns of two padded directions
+    check_lstm({3, 4, 0, 0, 0}, 1, 32, 32);         // no pad units
+    check_ff({7, 32, 7, 32, 1}, 6, 32);             // feedforward 6 behind an lstm 7
+    check_ff({6, 32, 0, 0, 0}, 4, 32);              // softmax 4 behind a dense layer
     std::printf(failures ? "noise_unpack: %d checks FAILED\n" : "noise_unpack: ok\n", failures);
     return failures ? 1 : 0;
 }
