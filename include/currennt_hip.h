@@ -530,6 +530,8 @@ int  cn_ctx_grad_clip_stats(cn_ctx *ctx, float *last_norm, float *last_scale, in
  * and the family's step runs with w0 in place of w:
  *      momentum:  dl = mom * dl - lr * g;  w = add_rn(w0, dl)
  *      Adam:      w = sub_rn(w0, (alpha_t * m) / (sqrt(v) + eps_t))          exactly as cn_adam_update states it
+ * The LAMB family (section LAMB) does NOT apply this rule: there the term decay * w of the same weights enters the direction u, in
+ * front of the layer's trust ratio, and no w0 is formed.
  *
  * What decays.  Input weights and internal (recurrent) weights only.  Bias weights, peephole weights and the arena's pad entries
  * never do: for them w0 = w and no operation is performed.  In the flat reference layout of a layer with L units, P inputs and
@@ -800,6 +802,77 @@ int  cn_layer_set_layer_norm(cn_layer *layer, int enable, float eps);
 int  cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, cn_layer **out);
 /* The members of a context layer (any pointer may be NULL); a layer of another kind: CN_ERR_BAD_ARG. */
 int  cn_layer_context(const cn_layer *layer, int *left, int *right, int *dilation);
+
+/* ---- LAMB (You et al. 2020, "Large Batch Optimization for Deep Learning"; no counterpart in the reference) ---------------------
+ * A third update family beside the cn_sgd_* and cn_adam_* trios, with the same three entry points and the same protocol: Adam's
+ * moments give a direction u per weight, and every LAYER's step is scaled by a trust ratio |w| / |u| of its own, so that the
+ * size of a layer's step is about lr times the size of its weights.
+ *
+ * State.  All state is fp32.  The first moments m live in CN_BUF_WEIGHT_DELTAS and the second moments v in
+ * CN_BUF_ADAM_SECOND_MOMENTS, as under Adam (zero at the first call unless uploaded); cn_buffer does not change.  The direction u
+ * is one scratch vector of the arena's length, an allocation of its own made by the first LAMB call together with one small
+ * record per trainable layer.  A context belongs to the family of its first update or arm call: LAMB after Adam or steepest
+ * descent, or the reverse, fails with CN_ERR_STATE.  The library keeps no clock: `step` (>= 1) is the caller's count of updates.
+ *
+ * Host scalars.  From the float arguments the host forms, in double, rounded once to float,
+ *      omb1 = 1 - beta1      omb2 = 1 - beta2
+ *      c_t   = sqrt(1 - beta2^step) / (1 - beta1^step)
+ *      eps_t = eps * sqrt(1 - beta2^step)
+ * (Adam's alpha_t is lr * c_t; here lr stays outside the quotient, because the trust ratio multiplies it.)
+ *
+ * Pass 1, per arena entry i of a layer (i counted from the layer's first entry; n, the layer's padded count, is its weight count
+ * rounded up to a multiple of four by pad entries that are zero).  Every operation is a single fp32 operation rounded to nearest:
+ * no contraction, correctly rounded sqrt and division, denormals kept.  g is the layer's weightUpdates entry as the clipping
+ * record hands it over (g' = mul_rn(scale, g) on a clipped step, see Gradient clipping).
+ *      m = beta1*m + omb1*g          v = beta2*v + omb2*(g*g)            (the operations of Adam, in the same order)
+ *      r = div_rn(mul_rn(c_t, m), add_rn(sqrt_rn(v), eps_t))
+ *      u = decays(i) ? add_rn(r, mul_rn(decay, w)) : r
+ * decays(i) is the set the Weight decay section names (input and recurrent weights; never bias, peephole or pad entries), and
+ * `decay` is the context's cn_ctx_set_weight_decay coefficient itself, not ld.  Under LAMB the decay term enters the direction,
+ * as in the paper: the w0 = w - ld*w rule of the Weight decay section is NOT applied.  With decay 0 no operation is performed
+ * for it.
+ *
+ * The two sums, per layer.  Sw = sum of w[i]^2 over the weights as they stood before the step, Su = sum of u[i]^2, i = 0 .. n-1.
+ * Both are formed in DOUBLE (each square formed in double from the float, so exact), in exactly the order the Gradient clipping
+ * section states for S, applied to the layer's n entries: L = 16384 lanes, ascending within a lane, then fourteen pairwise levels
+ * over neighbouring lanes.  The order depends on i and n alone -- not on the grid, the CU count, the precision mode or the
+ * "deterministic" option.
+ *
+ * Ratio and step.
+ *      nw = (float) sqrt(Sw)       nu = (float) sqrt(Su)                 (correctly rounded double sqrt, rounded once to float)
+ *      ratio = 1                                   if nw == 0, nu == 0, or Sw or Su is not finite
+ *      ratio = div_rn(nw, nu), then raised to min_ratio if below it
+ *                              and lowered to max_ratio if above it (max_ratio != 0)      otherwise
+ *      step  = mul_rn(lr_layer, ratio)
+ *      w     = sub_rn(w, mul_rn(step, u))          for every entry of the layer
+ * lr_layer is the call's rate or the layer's own (cn_layer_set_learning_rate).  {ratio, nw, nu} is the layer's record
+ * (cn_layer_trust_ratio).  A non-finite gradient without clipping poisons m as under Adam; set a clipping bound
+ * (cn_ctx_set_grad_clip, the driver's --max_grad_norm) to have such a step skipped.  A step the clipping record skips leaves
+ * w, m, v, the layer's record and the operand copies bit for bit as they were.
+ *
+ * Interactions.  Batch learning updates once per epoch sum (cn_ctx_take_accumulated, then the update).  Weight noise and weight
+ * averaging see the updated weights as the weights.  Data-parallel: every rank forms the same sums of the same reduced gradient in
+ * the same order, so the replicas stay bit-identical without an exchange.  Armed updates: the direction pass writes a layer's m
+ * and v before the layer's ratio is known, so an armed LAMB step is accepted and checked and then applied by the completing
+ * cn_lamb_update_all or per-layer cn_lamb_update call (which must name the armed values, else CN_ERR_STATE) -- the deferral
+ * clipping uses; the overlap of the update with the backward pass is lost.  While the weights are swapped with their average the
+ * calls fail with CN_ERR_STATE like the other update calls.  Argument errors as for Adam.
+ *
+ * Without any LAMB call the library launches exactly what it launches today and allocates nothing for this section. */
+/* beside cn_adam_update: the LAMB step of one layer (its own sums, its own ratio) at `learning_rate` as given */
+int  cn_lamb_update(cn_layer *layer, float learning_rate, float beta1, float beta2, float eps, int64_t step);
+/* beside cn_adam_update_all: every trainable layer -- one direction launch and one apply launch for all of them, then the operand
+ * copies; a layer with a learning rate of its own takes it as its lr_layer.  Orders itself behind cn_allreduce_grads. */
+int  cn_lamb_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step);
+/* beside cn_ctx_arm_adam: accepted and checked; the step is applied by the completing call (see Armed updates above) */
+int  cn_ctx_arm_lamb(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step);
+/* The bounds of every layer's ratio; a fresh context has 0 and 0, and max_ratio = 0 means no upper bound.  Negative, NaN, infinite,
+ * or min_ratio > max_ratio with max_ratio != 0: CN_ERR_BAD_ARG.  While an armed update is pending: CN_ERR_STATE. */
+int  cn_ctx_set_trust_bounds(cn_ctx *ctx, float min_ratio, float max_ratio);
+int  cn_ctx_get_trust_bounds(const cn_ctx *ctx, float *min_ratio, float *max_ratio);
+/* The record of the layer's last LAMB step that was not skipped: *ratio (bounds applied), *weight_norm = nw, *update_norm = nu; 1, 0, 0
+ * before the first.  Any pointer may be NULL.  A layer without weights: CN_ERR_BAD_ARG.                              [sync] */
+int  cn_layer_trust_ratio(cn_layer *layer, float *ratio, float *weight_norm, float *update_norm);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,8 @@ EXPORTS = [
     "cn_ctx_set_weight_decay", "cn_ctx_get_weight_decay",
     # include/currennt_hip.h, section Context layers
     "cn_layer_create_context", "cn_layer_context",
+    # include/currennt_hip.h, section LAMB
+    "cn_lamb_update", "cn_lamb_update_all", "cn_ctx_arm_lamb", "cn_ctx_set_trust_bounds", "cn_ctx_get_trust_bounds", "cn_layer_trust_ratio",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -191,6 +193,12 @@ def load_library():
     L.cn_adam_update.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
     L.cn_adam_update_all.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
     L.cn_ctx_arm_adam.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_lamb_update.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_lamb_update_all.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_ctx_arm_lamb.argtypes = [vp, cf, cf, cf, cf, C.c_int64]
+    L.cn_ctx_set_trust_bounds.argtypes = [vp, cf, cf]
+    L.cn_ctx_get_trust_bounds.argtypes = [vp, C.POINTER(cf), C.POINTER(cf)]
+    L.cn_layer_trust_ratio.argtypes = [vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
     L.cn_ctx_accumulate_updates.argtypes = [vp, ci]
     L.cn_ctx_take_accumulated.argtypes = [vp]
     L.cn_ctx_timing_enable.argtypes = [vp, ci]

@@ -68,11 +68,12 @@ struct Scratch {
 // The optimizer's rule of an update: momentum SGD (lr, mom) or Adam (lr, b1, b2, eps, step); lr is the caller's learning rate,
 // a layer with a rate of its own replaces it (layer_lr).  decay: the context's weight decay in force when the call came in, or, of
 // an armed rule, when it was armed (cn_ctx_set_weight_decay; 0: off) -- the caller's arguments do not name it, so same_rule
-// does not compare it
-struct UpdateRule { bool adam = false; float lr = 0.f, mom = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0; float decay = 0.f; };
+// does not compare it.  lamb (include/currennt_hip.h, section LAMB): Adam's arguments and moments (adam is set too), the layer-wise
+// trust ratio on top
+struct UpdateRule { bool adam = false, lamb = false; float lr = 0.f, mom = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f; int64_t step = 0; float decay = 0.f; };
 bool same_rule(const UpdateRule &a, const UpdateRule &b)
 {
-    if (a.adam != b.adam) return false;
+    if (a.adam != b.adam || a.lamb != b.lamb) return false;
     return a.adam ? a.lr == b.lr && a.b1 == b.b1 && a.b2 == b.b2 && a.eps == b.eps && a.step == b.step
                   : a.lr == b.lr && a.mom == b.mom;
 }
@@ -189,9 +190,14 @@ struct cn_ctx {
     UpdateRule arm;
     // Optimizer family of the context's first update / arm call (0: none yet).  weightDeltas is the momentum term under one and the
     // first moment under the other, so a context stays with its family.
-    enum { FAMILY_NONE = 0, FAMILY_SGD, FAMILY_ADAM };
+    enum { FAMILY_NONE = 0, FAMILY_SGD, FAMILY_ADAM, FAMILY_LAMB };
     int family = FAMILY_NONE;
     float *adam_v = nullptr;              // Adam's second moments, [total] like a part of the arena, zeroed; allocated at the first Adam call
+    // LAMB (include/currennt_hip.h, section LAMB): the direction u, [total] like a part of the arena, and one record per trainable
+    // layer (cn_layer::lamb_rec), both allocated at the first LAMB call; the trust bounds (cn_ctx_set_trust_bounds; 0 / 0: none)
+    float *lamb_u = nullptr;
+    LambRecord *lamb_recs = nullptr;
+    float trust_min = 0.f, trust_max = 0.f;
 
     // Weight averaging (include/currennt_hip.h, section Weight averaging): the average, [total] like a part of the arena, allocated
     // by the first averaging step (which copies the weights) or the first upload (a copy of the weights, then the layer's part);
@@ -308,6 +314,7 @@ struct cn_layer {
     // parameters (flat reference layout, inside the ctx arena)
     size_t woff = 0;
     int nw = 0;
+    int lamb_rec = -1;                    // index of the layer's LambRecord (ensure_lamb)
     float *w = nullptr, *wu = nullptr, *wd = nullptr;
     float own_lr = -1.f;                  // JSON "learningRate" (TrainableLayer.cu:58); negative: the optimizer's
     std::vector<float> pending_w;         // set_weights before the arena exists
@@ -878,12 +885,40 @@ void ensure_adam_v(cn_ctx *c)
     HIP_CHECK(hipMemsetAsync(c->adam_v, 0, c->total * sizeof(float), c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));          // (once per context: the side and communication streams use it too)
 }
+// LAMB's scalars (include/currennt_hip.h, section LAMB): lr stays outside the quotient
+LambScalars lamb_scalars(const cn_ctx *c, const UpdateRule &r)
+{
+    const double b1 = r.b1, b2 = r.b2, t = (double)r.step;
+    const double c2 = std::sqrt(1.0 - std::pow(b2, t)), c1 = 1.0 - std::pow(b1, t);
+    LambScalars s;
+    s.b1 = r.b1; s.b2 = r.b2; s.omb1 = (float)(1.0 - b1); s.omb2 = (float)(1.0 - b2);
+    s.c_t = (float)(c2 / c1); s.eps_t = (float)((double)r.eps * c2);
+    s.decay = r.decay; s.min_ratio = c->trust_min; s.max_ratio = c->trust_max;
+    return s;
+}
+// the first LAMB call: the direction vector and the layers' records (ratio 1, norms 0)
+void ensure_lamb(cn_ctx *c)
+{
+    ensure_adam_v(c);
+    if (c->lamb_u || !c->total) return;
+    std::vector<LambRecord> recs;
+    for (cn_layer *l : c->layers)
+        if (l->trainable) { l->lamb_rec = (int)recs.size(); LambRecord r{}; r.ratio = 1.0f; recs.push_back(r); }
+    HIP_CHECK(hipMalloc((void **)&c->lamb_u, c->total * sizeof(float)));
+    HIP_CHECK(hipMalloc((void **)&c->lamb_recs, recs.size() * sizeof(LambRecord)));
+    HIP_CHECK(hipMemsetAsync(c->lamb_u, 0, c->total * sizeof(float), c->stream));
+    HIP_CHECK(hipMemcpyAsync(c->lamb_recs, recs.data(), recs.size() * sizeof(LambRecord), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+int rule_family(const UpdateRule &r) { return r.lamb ? cn_ctx::FAMILY_LAMB : r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD; }
 void bind_family(cn_ctx *c, int family, const char *fn)
 {
+    static const char *const calls[] = {"", "steepest descent (cn_sgd_update*, cn_ctx_arm_update)", "Adam (cn_adam_update*, cn_ctx_arm_adam)",
+                                        "LAMB (cn_lamb_update*, cn_ctx_arm_lamb)"};
+    static const char *const names[] = {"", "steepest descent", "Adam", "LAMB"};
     if (c->family != cn_ctx::FAMILY_NONE && c->family != family)
-        throw cn_error(CN_ERR_STATE, std::string(fn) + ": this context is bound to " +
-                       (c->family == cn_ctx::FAMILY_SGD ? "steepest descent (cn_sgd_update*, cn_ctx_arm_update)" : "Adam (cn_adam_update*, cn_ctx_arm_adam)") +
-                       " by its first update, and " + (family == cn_ctx::FAMILY_SGD ? "steepest descent" : "Adam") +
+        throw cn_error(CN_ERR_STATE, std::string(fn) + ": this context is bound to " + calls[c->family] +
+                       " by its first update, and " + names[family] +
                        " would read its weightDeltas as something they are not (momentum term / first moment)");
     c->family = family;
 }
@@ -1602,7 +1637,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart); hipFree(ctx->aug_tab); hipFree(ctx->pf.aug_tab);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault); hipFree(ctx->cx_len);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->lamb_u); hipFree(ctx->lamb_recs); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault); hipFree(ctx->cx_len);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -2866,19 +2901,26 @@ static UpdateRule adam_rule(float lr, float b1, float b2, float eps, int64_t ste
     UpdateRule r; r.adam = true; r.lr = lr; r.b1 = b1; r.b2 = b2; r.eps = eps; r.step = step;
     return r;
 }
+static UpdateRule lamb_rule(float lr, float b1, float b2, float eps, int64_t step)
+{
+    UpdateRule r = adam_rule(lr, b1, b2, eps, step); r.lamb = true;
+    return r;
+}
 // what every update call does first (fn: the ABI function, for the messages); on return the main stream is ordered behind all
 // gradient work
 static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
 {
     refuse_swapped(c, fn);
     if (r.adam) check_adam_args(fn, r);
-    bind_family(c, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
+    bind_family(c, rule_family(r), fn);
     comm_check_fast(c);
-    if (r.adam) ensure_adam_v(c); else finalize(c);
+    if (r.lamb) ensure_lamb(c); else if (r.adam) ensure_adam_v(c); else finalize(c);
     join_side(c);
 }
-[[noreturn]] static void throw_rule_mismatch(const char *fn, bool adam)
+[[noreturn]] static void throw_rule_mismatch(const char *fn, const UpdateRule &r)
 {
+    const bool adam = r.adam;
+    if (r.lamb) throw cn_error(CN_ERR_STATE, std::string(fn) + ": learning rate / betas / eps / step differ from what cn_ctx_arm_lamb armed");
     throw cn_error(CN_ERR_STATE, std::string(fn) + (adam ? ": learning rate / betas / eps / step differ from what cn_ctx_arm_adam armed and applied"
                                                           : ": learning rate / momentum differ from what cn_ctx_arm_update armed and applied"));
 }
@@ -2889,6 +2931,7 @@ static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, fl
                         const DecayRanges *decayed = nullptr)
 {
     float *w = c->arena + off, *wu = w + c->total, *wd = w + 2 * c->total;
+    if (r.lamb) throw cn_error(CN_ERR_STATE, "launch_flat: LAMB steps go by layers (launch_lamb_layers)");
     if (r.decay != 0.f) {
         if (!decayed) throw cn_error(CN_ERR_STATE, "launch_flat: weight decay needs a layer's range");
         if (r.adam) launch_adam_decay(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), decay_ld(lr, r.decay), *decayed, clip, done);
@@ -2914,7 +2957,28 @@ static const ClipRecord *clip_record(cn_ctx *c)
     return c->clip_rec;
 }
 
-// cn_ctx_arm_update / cn_ctx_arm_adam
+// LAMB (include/currennt_hip.h, section LAMB): the direction and apply launches over `layers` (all of them in groups of
+// LAMB_GROUP_MAX, not one launch pair per layer); own_rates: a layer with a rate of its own takes it (layer_lr), else r.lr is the
+// rate as it stands; done rides on the last apply launch
+static void launch_lamb_layers(cn_ctx *c, const UpdateRule &r, const std::vector<cn_layer *> &layers, bool own_rates, const ClipRecord *clip, hipEvent_t done = nullptr)
+{
+    const LambScalars a = lamb_scalars(c, r);
+    for (size_t first = 0; first < layers.size(); first += LAMB_GROUP_MAX) {
+        LambGroup grp{};
+        for (size_t k = first; k < layers.size() && k < first + LAMB_GROUP_MAX; ++k) {
+            const cn_layer *l = layers[k];
+            const DecayRanges rg = decay_ranges(l);
+            LambItem &it = grp.item[grp.n++];
+            it.off = l->woff; it.n = (unsigned)round_up(l->nw, 4);
+            it.a1 = (unsigned)rg.a1; it.b0 = (unsigned)rg.b0; it.b1 = (unsigned)rg.b1;
+            it.lr = own_rates ? layer_lr(l, r) : r.lr; it.rec = l->lamb_rec;
+        }
+        const bool last = first + LAMB_GROUP_MAX >= layers.size();
+        launch_lamb(c->stream, grp, c->arena, c->total, c->adam_v, c->lamb_u, a, c->lamb_recs, clip, last ? done : nullptr);
+    }
+}
+
+// cn_ctx_arm_update / cn_ctx_arm_adam / cn_ctx_arm_lamb
 static void arm(cn_ctx *ctx, UpdateRule r, const char *fn)
 {
     enter(ctx);
@@ -2923,11 +2987,13 @@ static void arm(cn_ctx *ctx, UpdateRule r, const char *fn)
     if (r.adam) check_adam_args(fn, r);
     for (cn_layer *l : ctx->layers)
         if (l->updated) throw cn_error(CN_ERR_STATE, std::string(fn) + ": the previous armed update has not been completed (" +
-                                       (r.adam ? "cn_adam_update_all" : "cn_sgd_update_all") + ")");
-    bind_family(ctx, r.adam ? cn_ctx::FAMILY_ADAM : cn_ctx::FAMILY_SGD, fn);
-    if (r.adam) ensure_adam_v(ctx);
+                                       (r.lamb ? "cn_lamb_update_all" : r.adam ? "cn_adam_update_all" : "cn_sgd_update_all") + ")");
+    bind_family(ctx, rule_family(r), fn);
+    if (r.lamb) ensure_lamb(ctx); else if (r.adam) ensure_adam_v(ctx);
     ctx->arm = r;
-    if (ctx->clip_max != 0.f) {      // clipping on: accepted and checked, applied by the completing call (a global norm needs every layer's gradient)
+    // clipping on: accepted and checked, applied by the completing call (a global norm needs every layer's gradient); LAMB: the
+    // same deferral, always (its direction pass writes a layer's moments before the layer's ratio is known)
+    if (ctx->clip_max != 0.f || r.lamb) {
         ctx->arm_deferred = true;
         for (cn_layer *l : ctx->layers) l->deferred = l->trainable;
         return;
@@ -2958,7 +3024,7 @@ static void update_layer(cn_layer *layer, UpdateRule r, const char *fn)
     if (layer->updated) {            // armed: this layer's step ran behind its gradient; nothing left but the wait above
         UpdateRule applied = c->arm;
         applied.lr = layer_lr(layer, c->arm);
-        if (!same_rule(r, applied)) throw_rule_mismatch(fn, r.adam);
+        if (!same_rule(r, applied)) throw_rule_mismatch(fn, r);
         layer->updated = false;
         bool any = false;
         for (cn_layer *o : c->layers) any = any || o->updated;
@@ -2968,7 +3034,7 @@ static void update_layer(cn_layer *layer, UpdateRule r, const char *fn)
     if (layer->deferred) {           // armed with clipping on: this is the call that applies the layer's step
         UpdateRule armed = c->arm;
         armed.lr = layer_lr(layer, c->arm);
-        if (!same_rule(r, armed)) throw_rule_mismatch(fn, r.adam);
+        if (!same_rule(r, armed)) throw_rule_mismatch(fn, r);
         layer->deferred = false;
         r.decay = c->arm.decay;
         bool any = false;
@@ -2976,6 +3042,11 @@ static void update_layer(cn_layer *layer, UpdateRule r, const char *fn)
         if (!any) c->arm_deferred = false;
     }
     Timed tm(c, KC_OTHER);
+    if (r.lamb) {
+        launch_lamb_layers(c, r, {layer}, false, clip_record(c));
+        layer->dirty = true; layer->noisy_ready = false;
+        return;
+    }
     const DecayRanges rg = decay_ranges(layer);
     launch_flat(c, r, layer->woff, (size_t)layer->nw, r.lr, clip_record(c), nullptr, &rg);
     layer->dirty = true; layer->noisy_ready = false;
@@ -3294,7 +3365,7 @@ int cn_dbg_noisy_weights(cn_layer *layer, float *host, size_t count)
     });
 }
 
-// cn_sgd_update_all / cn_adam_update_all: one sequence for both rules (r.lr: the call's learning rate)
+// cn_sgd_update_all / cn_adam_update_all / cn_lamb_update_all: one sequence for all rules (r.lr: the call's learning rate)
 // (in an unnamed namespace inside extern "C", as it has been: hipcc gives such a function an unmangled GLOBAL symbol, so the
 // library's dynamic symbol table lists "update_all" -- nobody declares it; dropping it is a change of the export list of its own)
 namespace {
@@ -3307,9 +3378,9 @@ void update_all(cn_ctx *ctx, UpdateRule r, const char *fn)
     // follows handles the rest (none, normally)
     bool any_updated = false;
     for (cn_layer *l : ctx->layers) any_updated = any_updated || l->updated;
-    if (any_updated && !same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r.adam);
+    if (any_updated && !same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r);
     if (ctx->arm_deferred) {         // armed with clipping on: the step is applied here, all layers at once
-        if (!same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r.adam);
+        if (!same_rule(r, ctx->arm)) throw_rule_mismatch(fn, r);
         ctx->arm_deferred = false;
         for (cn_layer *l : ctx->layers) l->deferred = false;
     }
@@ -3332,7 +3403,7 @@ void update_all(cn_ctx *ctx, UpdateRule r, const char *fn)
     const bool grouped = ctx->overlap && !group_off && ntrain <= PACK_GROUP_MAX;
     // grouped: the update itself rides on the pack launch (pack_fetch): one kernel instead of two behind the last gradient
     const bool fuse_off = opt().no_sgd_fuse;
-    const bool fused = grouped && !fuse_off;
+    const bool fused = grouped && !fuse_off && !r.lamb;       // (LAMB: its two launches, then the plain pack launch)
     const bool attach = ctx->overlap && !grouped && ctx->attach_forks && !ctx->timing;
     if (ctx->overlap && !grouped && !ctx->ev_sgd) HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_sgd, hipEventDisableTiming));
     if (!fused) {
@@ -3340,7 +3411,12 @@ void update_all(cn_ctx *ctx, UpdateRule r, const char *fn)
         cn_layer *last = nullptr;
         for (cn_layer *l : ctx->layers)
             if (l->trainable) { own_rates = own_rates || l->own_lr >= 0.f; last = l; }
-        if (!own_rates && r.decay == 0.f) launch_flat(ctx, r, 0, ctx->total, r.lr, clip, attach ? ctx->ev_sgd : nullptr);
+        if (r.lamb) {
+            std::vector<cn_layer *> train;
+            for (cn_layer *l : ctx->layers) if (l->trainable) train.push_back(l);
+            launch_lamb_layers(ctx, r, train, true, clip, attach ? ctx->ev_sgd : nullptr);
+        }
+        else if (!own_rates && r.decay == 0.f) launch_flat(ctx, r, 0, ctx->total, r.lr, clip, attach ? ctx->ev_sgd : nullptr);
         else            // a layer with a "learningRate" of its own, or weight decay (a layer's blocks): one launch per layer
             for (cn_layer *l : ctx->layers)
                 if (l->trainable) {
@@ -3393,6 +3469,59 @@ int cn_adam_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta
 {
     if (!ctx) { g_last_error = "cn_adam_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
     return guarded([&] { update_all(ctx, adam_rule(learning_rate, beta1, beta2, eps, step), "cn_adam_update_all"); });
+}
+
+// ---- LAMB (include/currennt_hip.h, section LAMB) ----
+int cn_lamb_update_all(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!ctx) { g_last_error = "cn_lamb_update_all: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] { update_all(ctx, lamb_rule(learning_rate, beta1, beta2, eps, step), "cn_lamb_update_all"); });
+}
+int cn_lamb_update(cn_layer *layer, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!layer) { g_last_error = "cn_lamb_update: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] { update_layer(layer, lamb_rule(learning_rate, beta1, beta2, eps, step), "cn_lamb_update"); });
+}
+int cn_ctx_arm_lamb(cn_ctx *ctx, float learning_rate, float beta1, float beta2, float eps, int64_t step)
+{
+    if (!ctx) { g_last_error = "cn_ctx_arm_lamb: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] { arm(ctx, lamb_rule(learning_rate, beta1, beta2, eps, step), "cn_ctx_arm_lamb"); });
+}
+int cn_ctx_set_trust_bounds(cn_ctx *ctx, float min_ratio, float max_ratio)
+{
+    if (!ctx) { g_last_error = "cn_ctx_set_trust_bounds: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        if (!(min_ratio >= 0.f) || !(max_ratio >= 0.f) || std::isinf(min_ratio) || std::isinf(max_ratio))
+            throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_set_trust_bounds: the bounds must be finite and >= 0 (max_ratio 0 = no upper bound)");
+        if (max_ratio != 0.f && min_ratio > max_ratio) throw cn_error(CN_ERR_BAD_ARG, "cn_ctx_set_trust_bounds: min_ratio > max_ratio");
+        bool pending = ctx->armed || ctx->arm_deferred;
+        for (cn_layer *l : ctx->layers) pending = pending || l->updated;
+        if (pending) throw cn_error(CN_ERR_STATE, "cn_ctx_set_trust_bounds: an armed update is pending (complete it with the *_update* call first)");
+        ctx->trust_min = min_ratio; ctx->trust_max = max_ratio;
+    });
+}
+int cn_ctx_get_trust_bounds(const cn_ctx *ctx, float *min_ratio, float *max_ratio)
+{
+    if (!ctx || !min_ratio || !max_ratio) { g_last_error = "cn_ctx_get_trust_bounds: ctx, min_ratio or max_ratio is NULL"; return CN_ERR_BAD_ARG; }
+    *min_ratio = ctx->trust_min; *max_ratio = ctx->trust_max;
+    return CN_OK;
+}
+int cn_layer_trust_ratio(cn_layer *layer, float *ratio, float *weight_norm, float *update_norm)
+{
+    if (!layer) { g_last_error = "cn_layer_trust_ratio: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        if (!layer->trainable) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_trust_ratio: layer has no weights");
+        LambRecord h{}; h.ratio = 1.0f;
+        if (c->lamb_recs && layer->lamb_rec >= 0) {
+            enter(c);
+            HIP_CHECK(hipMemcpyAsync(&h, c->lamb_recs + layer->lamb_rec, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+        }
+        if (ratio) *ratio = h.ratio;
+        if (weight_norm) *weight_norm = h.nw;
+        if (update_norm) *update_norm = h.nu;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -475,6 +475,28 @@ void launch_sgd_decay(hipStream_t s, float *w, const float *wu, float *wd, size_
 void launch_adam_decay(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, float ld, const DecayRanges &rg,
                        const ClipRecord *rec = nullptr, hipEvent_t done = nullptr);
 
+// ---- LAMB (include/currennt_hip.h, section LAMB; cn_lamb.hip) ----
+// The host scalars of the section, and the context's decay coefficient and trust bounds (max_ratio 0: no upper bound)
+struct LambScalars { float b1, omb1, b2, omb2, c_t, eps_t, decay, min_ratio, max_ratio; };
+// One layer of a launch: its range of the arena (off floats in, n = the padded count), the runs of it that decay ([0, a1) and
+// [b0, b1), relative to off), its effective rate and its record's index
+struct LambItem { size_t off; unsigned n, a1, b0, b1; float lr; int rec; };
+constexpr int LAMB_GROUP_MAX = 16;
+struct LambGroup { LambItem item[LAMB_GROUP_MAX]; int n; };
+// rows of CLIP_LANES entries a thread of lamb_direction_kernel loads in front of its dependent adds; the grid of lamb_apply_kernel
+constexpr int LAMB_UNROLL = 4;
+constexpr unsigned LAMB_APPLY_MAX_BLOCKS = 256;
+// A layer's device record: what its last LAMB step found (ratio 1, norms 0 before the first); part_* / arrivals belong to the
+// hand-off (arrivals is zero between launches)
+struct LambRecord {
+    float nw, nu, ratio; unsigned arrivals;
+    double part_w[CLIP_WGS], part_u[CLIP_WGS];
+};
+// One direction launch and one apply launch over the group's layers: m = arena + 2 * total, g = arena + total, v and u are [total]
+// like a part of the arena.  clip (nullable): the clipping record in front of the rule; done rides on the apply launch.
+void launch_lamb(hipStream_t s, const LambGroup &grp, float *arena, size_t total, float *v, float *u, const LambScalars &a, LambRecord *recs,
+                 const ClipRecord *clip = nullptr, hipEvent_t done = nullptr);
+
 // ---- weight averaging (include/currennt_hip.h, section Weight averaging; cn_average.hip) ----
 // avg[0 .. n) = copy ? w : avg + omd * (w - avg), every operation an fp32 operation rounded on its own (n a multiple of 4, both
 // pointers 16-byte aligned: the weights part of the arena and the context's average)

@@ -45,8 +45,10 @@ const char *Configuration::usage()
            "                      parallel_sequences is per GPU; gradients are summed with RCCL)\n"
            "  training: --train B --stochastic B (= --hybrid_online_batch) --shuffle_fractions B --shuffle_sequences B\n"
            "            --max_epochs N --max_epochs_no_best N --validate_every N --test_every N --learning_rate X\n"
-           "            --optimizer steepest_descent|adam (adam: --learning_rate is its step size, --momentum is ignored)\n"
-           "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8)\n"
+           "            --optimizer steepest_descent|adam|lamb (adam, lamb: --learning_rate is the step size, --momentum is ignored)\n"
+           "            --adam_beta1 X --adam_beta2 X --adam_epsilon X (defaults 0.9, 0.999, 1e-8; lamb uses them too)\n"
+           "            --lamb_min_trust X --lamb_max_trust X (lamb: every layer's step is scaled by |w| / |u| of that layer, kept\n"
+           "                      inside these bounds; --weight_decay enters lamb's direction u; defaults 0 and 0 = unbounded)\n"
            "            --max_grad_norm X (clip every update's gradient to this global L2 norm; a step with a non-finite gradient is\n"
            "                      skipped; default 0 = off)\n"
            "            --weight_decay X (decoupled weight decay, AdamW-style, for both optimizers: every input and recurrent weight\n"
@@ -107,7 +109,13 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "max_epochs_no_best") m_maxEpochsNoBest = atoi(v.c_str());
     else if (key == "validate_every") m_validateEvery = atoi(v.c_str());
     else if (key == "test_every") m_testEvery = atoi(v.c_str());
-    else if (key == "optimizer") { if (v == "adam" || v == "steepest_descent") m_optimizer = v; else throw std::runtime_error("Error while parsing the command line and/or options file: unknown optimizer '" + v + "'"); }
+    else if (key == "optimizer") { if (v == "adam" || v == "lamb" || v == "steepest_descent") m_optimizer = v; else throw std::runtime_error("Error while parsing the command line and/or options file: unknown optimizer '" + v + "' (steepest_descent, adam or lamb)"); }
+    else if (key == "lamb_min_trust" || key == "lamb_max_trust") {
+        real_t &bound = key == "lamb_min_trust" ? m_lambMinTrust : m_lambMaxTrust;
+        bound = (real_t)atof(v.c_str());
+        if (!(bound >= 0) || std::isinf(bound))
+            throw std::runtime_error("Error while parsing the command line and/or options file: --" + key + " must be finite and >= 0 (0 = off)");
+    }
     else if (key == "learning_rate") m_learningRate = (real_t)atof(v.c_str());
     else if (key == "momentum") m_momentum = (real_t)atof(v.c_str());
     else if (key == "adam_beta1") m_adamBeta1 = (real_t)atof(v.c_str());

@@ -34,11 +34,14 @@ public:
     unsigned randomSeed() const { return m_randomSeed; }
     real_t learningRate() const { return m_learningRate; }
     real_t momentum() const { return m_momentum; }
-    // --optimizer: "steepest_descent" (the reference's default, Configuration.cpp:152) or "adam" (no counterpart there)
+    // --optimizer: "steepest_descent" (the reference's default, Configuration.cpp:152), "adam" or "lamb" (no counterpart there)
     const std::string &optimizer() const { return m_optimizer; }
     real_t adamBeta1() const { return m_adamBeta1; }
     real_t adamBeta2() const { return m_adamBeta2; }
     real_t adamEpsilon() const { return m_adamEpsilon; }
+    // --lamb_min_trust / --lamb_max_trust: the bounds of lamb's per-layer trust ratio (include/currennt_hip.h, section LAMB); 0 = none
+    real_t lambMinTrust() const { return m_lambMinTrust; }
+    real_t lambMaxTrust() const { return m_lambMaxTrust; }
     // --max_grad_norm: bound on the global L2 norm of an update's gradient (include/currennt_hip.h, section Gradient clipping;
     // no counterpart in the reference); 0 = off
     real_t maxGradNorm() const { return m_maxGradNorm; }
@@ -133,6 +136,7 @@ private:
     real_t m_learningRate = 1e-5f, m_momentum = 0.9f, m_featurePeriod = 10, m_trainingFraction = 1, m_validationFraction = 1,
            m_testFraction = 1, m_weightsUniformMin = -0.1f, m_weightsUniformMax = 0.1f, m_weightsNormalSigma = 0.1f, m_weightsNormalMean = 0;
     real_t m_adamBeta1 = 0.9f, m_adamBeta2 = 0.999f, m_adamEpsilon = 1e-8f;
+    real_t m_lambMinTrust = 0, m_lambMaxTrust = 0;
     real_t m_maxGradNorm = 0;
     real_t m_weightDecay = 0;
     long long m_lrWarmupUpdates = 0;

@@ -371,9 +371,16 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
         if (config.trainingMode()) {
             printf("Creating the optimizer... ");
             fflush(stdout);
-            const bool adam = config.optimizer() == "adam";
+            const bool lamb = config.optimizer() == "lamb";
+            const bool adam = config.optimizer() == "adam" || lamb;            // (lamb: Adam's options and moments)
             std::unique_ptr<optimizers::Optimizer> optimizerPtr;
-            if (adam) optimizerPtr.reset(new optimizers::AdamOptimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
+            optimizers::LambOptimizer *lambPtr = nullptr;
+            if (lamb) optimizerPtr.reset(lambPtr = new optimizers::LambOptimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
+                                                                                 config.maxEpochsNoBest(), config.validateEvery(), config.testEvery(),
+                                                                                 config.learningRate(), config.adamBeta1(), config.adamBeta2(),
+                                                                                 config.adamEpsilon(), config.lambMinTrust(), config.lambMaxTrust(),
+                                                                                 config.hybridOnlineBatch()));
+            else if (adam) optimizerPtr.reset(new optimizers::AdamOptimizer(neuralNetwork, *trainingSet, *validationSet, *testSet, config.maxEpochs(),
                                                                        config.maxEpochsNoBest(), config.validateEvery(), config.testEvery(),
                                                                        config.learningRate(), config.adamBeta1(), config.adamBeta2(),
                                                                        config.adamEpsilon(), config.hybridOnlineBatch()));
@@ -382,7 +389,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                                                                              config.learningRate(), config.momentum(), config.hybridOnlineBatch()));
             optimizers::Optimizer &optimizer = *optimizerPtr;
             printf("done.\n");
-            if (adam) printf("Optimizer type: Adam\n");
+            if (lamb) printf("Optimizer type: LAMB\n");
+            else if (adam) printf("Optimizer type: Adam\n");
             else printf("Optimizer type: Steepest descent with momentum\n");                    // main.cpp:660-678
             printf("Max training epochs:       %d\n", config.maxEpochs());
             printf("Max epochs until new best: %d\n", config.maxEpochsNoBest());
@@ -392,12 +400,17 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             if (adam) {
                 printf("Adam beta1 / beta2:        %g / %g\n", (double)config.adamBeta1(), (double)config.adamBeta2());
                 printf("Adam epsilon:              %g\n", (double)config.adamEpsilon());
+                if (lamb) {
+                    if (config.lambMaxTrust() > 0) printf("Trust ratio bounds:        %g / %g\n", (double)config.lambMinTrust(), (double)config.lambMaxTrust());
+                    else printf("Trust ratio bounds:        %g / unbounded\n", (double)config.lambMinTrust());
+                }
                 printf("Momentum:                  ignored (--momentum is an option of steepest_descent)\n\n");
             } else {
                 printf("Momentum:                  %g\n\n", (double)config.momentum());
             }
             if (config.maxGradNorm() > 0) printf("Max. gradient norm:        %g\n\n", (double)config.maxGradNorm());
-            if (config.weightDecay() > 0) printf("Weight decay:              %g (decoupled; input and recurrent weights)\n\n", (double)config.weightDecay());
+            if (config.weightDecay() > 0 && lamb) printf("Weight decay:              %g (in LAMB's direction; input and recurrent weights)\n\n", (double)config.weightDecay());
+            else if (config.weightDecay() > 0) printf("Weight decay:              %g (decoupled; input and recurrent weights)\n\n", (double)config.weightDecay());
             if (config.learningRateSchedule())
                 printf("Learning rate schedule:    warm-up %lld updates, decay %g after %d epochs without a new lowest error, min %g\n\n",
                        config.learningRateWarmupUpdates(), config.learningRateDecay(), config.learningRateDecayPatience(), config.learningRateMin());
@@ -480,6 +493,11 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 if (config.maxGradNorm() > 0) {
                     const optimizers::Optimizer::ClipStats cs = optimizer.takeClipStats();
                     printf("         gradient norm: max %g, clipped %lld, skipped %lld of %lld updates\n", (double)cs.maxNormSeen, cs.clipped, cs.skipped, cs.updates);
+                }
+                // --optimizer lamb: the smallest and the largest trust ratio of the epoch's last update (one line behind the row too)
+                if (lambPtr) {
+                    const optimizers::LambOptimizer::TrustRange tr = lambPtr->trustRange();
+                    printf("         trust ratio: min %g (%s), max %g (%s)\n", (double)tr.min, tr.minLayer.c_str(), (double)tr.max, tr.maxLayer.c_str());
                 }
                 // the learning-rate schedule: the rate the next update would use (one line behind the row, like clipping's)
                 if (config.learningRateSchedule()) {

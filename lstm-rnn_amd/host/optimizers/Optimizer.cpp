@@ -431,6 +431,8 @@ void SteepestDescentOptimizer::exportState(json::Value *jsonDoc) const
 }
 void SteepestDescentOptimizer::importState(const json::Value &jsonDoc)
 {
+    if (jsonDoc.hasMember("lamb_optimizer"))
+        throw std::runtime_error("The autosave file was written by the lamb optimizer and cannot be continued with steepest_descent");
     if (jsonDoc.hasMember("adam_optimizer_step"))
         throw std::runtime_error("The autosave file was written by the adam optimizer and cannot be continued with steepest_descent");
     Optimizer::importState(jsonDoc);
@@ -511,8 +513,10 @@ void AdamOptimizer::_armUpdate()
     NeuralNetwork &nn = _neuralNetwork();
     ++m_step;
     m_armed = true;
-    hipCheck(cn_ctx_arm_adam(nn.context(), _scheduledRate(m_learningRate), m_beta1, m_beta2, m_epsilon, m_step), nn.context());
+    hipCheck(_armCall(_scheduledRate(m_learningRate)), nn.context());
 }
+int AdamOptimizer::_armCall(real_t lr) { return cn_ctx_arm_adam(_neuralNetwork().context(), lr, m_beta1, m_beta2, m_epsilon, m_step); }
+int AdamOptimizer::_layerCall(cn_layer *layer, real_t lr) { return cn_adam_update(layer, lr, m_beta1, m_beta2, m_epsilon, m_step); }
 
 void AdamOptimizer::_updateWeights()
 {
@@ -530,7 +534,7 @@ void AdamOptimizer::_updateWeights()
         real_t lr = m_learningRate;
         if (layer->learningRate() >= 0.0) lr = layer->learningRate();        // a layer's own "learningRate" is its Adam step size
         lr = _scheduledRate(lr);
-        hipCheck(cn_adam_update(layer->handle(), lr, m_beta1, m_beta2, m_epsilon, m_step), nn.context());
+        hipCheck(_layerCall(layer->handle(), lr), nn.context());
     }
 }
 
@@ -556,9 +560,13 @@ void AdamOptimizer::importState(const json::Value &jsonDoc)
 {
     if (!jsonDoc.hasMember("adam_optimizer_step")) {
         if (jsonDoc.hasMember("steepest_descent_optimizer_weight_deltas"))
-            throw std::runtime_error("The autosave file was written by the steepest_descent optimizer and cannot be continued with adam");
+            throw std::runtime_error(std::string("The autosave file was written by the steepest_descent optimizer and cannot be continued with ") + _name());
         throw std::runtime_error("Value 'adam_optimizer_step' is missing in the autosave file");
     }
+    const bool lambFile = jsonDoc.hasMember("lamb_optimizer"), lamb = std::string(_name()) == "lamb";
+    if (lambFile != lamb)
+        throw std::runtime_error(std::string("The autosave file was written by the ") + (lambFile ? "lamb" : "adam") +
+                                 " optimizer and cannot be continued with " + _name());
     Optimizer::importState(jsonDoc);
     NeuralNetwork &nn = _neuralNetwork();
     const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
@@ -576,6 +584,52 @@ void AdamOptimizer::importState(const json::Value &jsonDoc)
         hipCheck(cn_layer_upload(layer->handle(), CN_BUF_WEIGHT_DELTAS, m[i].data(), m[i].size()), nn.context());
         hipCheck(cn_layer_upload(layer->handle(), CN_BUF_ADAM_SECOND_MOMENTS, v[i].data(), v[i].size()), nn.context());
     }
+}
+
+LambOptimizer::LambOptimizer(NeuralNetwork &neuralNetwork, data_sets::DataSet &trainingSet, data_sets::DataSet &validationSet,
+                             data_sets::DataSet &testSet, int maxEpochs, int maxEpochsNoBest, int validateEvery, int testEvery,
+                             real_t learningRate, real_t beta1, real_t beta2, real_t epsilon, real_t minTrust, real_t maxTrust, bool hybridOnlineBatch)
+    : AdamOptimizer(neuralNetwork, trainingSet, validationSet, testSet, maxEpochs, maxEpochsNoBest, validateEvery, testEvery, learningRate,
+                    beta1, beta2, epsilon, hybridOnlineBatch)
+    , m_minTrust(minTrust), m_maxTrust(maxTrust)
+{
+    hipCheck(cn_ctx_set_trust_bounds(neuralNetwork.context(), m_minTrust, m_maxTrust), neuralNetwork.context());
+}
+int LambOptimizer::_armCall(real_t lr) { return cn_ctx_arm_lamb(_neuralNetwork().context(), lr, m_beta1, m_beta2, m_epsilon, m_step); }
+int LambOptimizer::_layerCall(cn_layer *layer, real_t lr) { return cn_lamb_update(layer, lr, m_beta1, m_beta2, m_epsilon, m_step); }
+
+void LambOptimizer::exportState(json::Value *jsonDoc) const
+{
+    AdamOptimizer::exportState(jsonDoc);
+    jsonDoc->addMember("lamb_optimizer", json::Value(true));
+    jsonDoc->addMember("lamb_optimizer_min_trust", json::Value((double)m_minTrust));
+    jsonDoc->addMember("lamb_optimizer_max_trust", json::Value((double)m_maxTrust));
+}
+void LambOptimizer::importState(const json::Value &jsonDoc)
+{
+    AdamOptimizer::importState(jsonDoc);
+    if (jsonDoc.hasMember("lamb_optimizer_min_trust")) m_minTrust = (real_t)jsonDoc["lamb_optimizer_min_trust"].getDouble();
+    if (jsonDoc.hasMember("lamb_optimizer_max_trust")) m_maxTrust = (real_t)jsonDoc["lamb_optimizer_max_trust"].getDouble();
+    NeuralNetwork &nn = _neuralNetwork();
+    hipCheck(cn_ctx_set_trust_bounds(nn.context(), m_minTrust, m_maxTrust), nn.context());
+}
+
+LambOptimizer::TrustRange LambOptimizer::trustRange()
+{
+    NeuralNetwork &nn = _neuralNetwork();
+    const std::vector<std::shared_ptr<layers::Layer> > &ls = nn.layers();
+    TrustRange r{0.f, 0.f, "", ""};
+    bool first = true;
+    for (size_t i = 1; i + 1 < ls.size(); ++i) {
+        layers::TrainableLayer *layer = dynamic_cast<layers::TrainableLayer *>(ls[i].get());
+        if (!layer) continue;
+        float ratio = 1.f;
+        hipCheck(cn_layer_trust_ratio(layer->handle(), &ratio, nullptr, nullptr), nn.context());
+        if (first || ratio < r.min) { r.min = ratio; r.minLayer = layer->name(); }
+        if (first || ratio > r.max) { r.max = ratio; r.maxLayer = layer->name(); }
+        first = false;
+    }
+    return r;
 }
 
 }  // namespace optimizers

@@ -1,4 +1,4 @@
-// Epoch protocol and momentum SGD (currennt_lib/src/optimizers/{Optimizer,SteepestDescentOptimizer}.*), and Adam beside it.
+// Epoch protocol and momentum SGD (currennt_lib/src/optimizers/{Optimizer,SteepestDescentOptimizer}.*), and Adam and LAMB beside it.
 // Gradient accumulation, the update and best-weight bookkeeping all stay on the device; the host only
 // sequences them.
 #pragma once
@@ -158,10 +158,36 @@ public:
 protected:
     void _updateWeights();
     void _armUpdate();
-private:
+    // the family's two calls (LambOptimizer names its own) and its name in the messages about autosave files
+    virtual int _armCall(real_t lr);
+    virtual int _layerCall(cn_layer *layer, real_t lr);
+    virtual const char *_name() const { return "adam"; }
     real_t m_learningRate, m_beta1, m_beta2, m_epsilon;
     int64_t m_step;                 // updates applied so far
+private:
     bool m_armed;                   // _armUpdate() has counted and armed the update _updateWeights() is about to complete
+};
+
+// LAMB (include/currennt_hip.h, section LAMB): Adam's state, options, seams and autosave members, the cn_lamb_* calls in place of
+// the cn_adam_* ones, and the trust bounds, which travel with the autosave beside the member "lamb_optimizer": true.
+class LambOptimizer : public AdamOptimizer {
+public:
+    LambOptimizer(NeuralNetwork &neuralNetwork, data_sets::DataSet &trainingSet, data_sets::DataSet &validationSet,
+                  data_sets::DataSet &testSet, int maxEpochs, int maxEpochsNoBest, int validateEvery, int testEvery,
+                  real_t learningRate, real_t beta1, real_t beta2, real_t epsilon, real_t minTrust, real_t maxTrust, bool hybridOnlineBatch);
+    void exportState(json::Value *jsonDoc) const;
+    void importState(const json::Value &jsonDoc);
+    real_t minTrust() const { return m_minTrust; }
+    real_t maxTrust() const { return m_maxTrust; }
+    // the smallest and the largest trust ratio of the last update, with the layers that had them (one synchronising read per layer)
+    struct TrustRange { float min, max; std::string minLayer, maxLayer; };
+    TrustRange trustRange();
+protected:
+    int _armCall(real_t lr);
+    int _layerCall(cn_layer *layer, real_t lr);
+    const char *_name() const { return "lamb"; }
+private:
+    real_t m_minTrust, m_maxTrust;
 };
 
 }  // namespace optimizers

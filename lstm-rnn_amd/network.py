@@ -153,6 +153,13 @@ class Layer:
         """Adam's second moments v (zeros before the context's first Adam call)."""
         return self._read("adamSecondMoments", self.weight_count)
 
+    def trust_ratio(self):
+        """cn_layer_trust_ratio: (ratio, weight_norm, update_norm) of the layer's last LAMB step as np.float32; (1, 0, 0) before
+        the first."""
+        f = [C.c_float() for _ in range(3)]
+        B.check(self.net.lib.cn_layer_trust_ratio(self.handle, C.byref(f[0]), C.byref(f[1]), C.byref(f[2])), self.net.ctx)
+        return tuple(np.float32(x.value) for x in f)
+
     def upload(self, which, array):
         """cn_layer_upload: overwrite a flat parameter vector ("weights", "weightUpdates", "weightDeltas",
         "adamSecondMoments") from the host."""
@@ -588,6 +595,30 @@ class NeuralNetwork:
         """cn_ctx_arm_adam: the coming backward pass applies each layer's Adam step as soon as that layer's gradient is complete;
         follow the backward pass with update_weights_adam(same values), which completes the step."""
         B.check(self.lib.cn_ctx_arm_adam(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+
+    def update_weights_lamb(self, learning_rate, beta1=0.9, beta2=0.999, eps=1e-8, step=1, per_layer=False):
+        """The LAMB step of include/currennt_hip.h (cn_lamb_update_all; per_layer: cn_lamb_update layer by layer).  `step` is the
+        caller's update count, from 1.  Layers with a JSON learningRate of their own keep it."""
+        if not per_layer:
+            B.check(self.lib.cn_lamb_update_all(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+            return
+        for lay in self.trainable_layers():
+            lr = lay.learning_rate if lay.learning_rate >= 0.0 else learning_rate
+            B.check(self.lib.cn_lamb_update(lay.handle, lr, beta1, beta2, eps, int(step)), self.ctx)
+
+    def arm_lamb(self, learning_rate, beta1=0.9, beta2=0.999, eps=1e-8, step=1):
+        """cn_ctx_arm_lamb: accepted and checked; update_weights_lamb(same values) behind the backward pass applies the step."""
+        B.check(self.lib.cn_ctx_arm_lamb(self.ctx, learning_rate, beta1, beta2, eps, int(step)), self.ctx)
+
+    def set_trust_bounds(self, min_ratio, max_ratio):
+        """cn_ctx_set_trust_bounds: the bounds of every layer's LAMB trust ratio; max_ratio 0 means no upper bound."""
+        B.check(self.lib.cn_ctx_set_trust_bounds(self.ctx, float(min_ratio), float(max_ratio)), self.ctx)
+
+    def trust_bounds(self):
+        """cn_ctx_get_trust_bounds: (min_ratio, max_ratio) as np.float32."""
+        a, b = C.c_float(), C.c_float()
+        B.check(self.lib.cn_ctx_get_trust_bounds(self.ctx, C.byref(a), C.byref(b)), self.ctx)
+        return np.float32(a.value), np.float32(b.value)
 
     def average_weights(self, decay):
         """cn_ctx_average_weights: one step avg += (1 - decay) * (w - avg) over all weights, behind the update that precedes it
