@@ -803,6 +803,58 @@ int  cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int rig
 /* The members of a context layer (any pointer may be NULL); a layer of another kind: CN_ERR_BAD_ARG. */
 int  cn_layer_context(const cn_layer *layer, int *left, int *right, int *dilation);
 
+/* ---- Strided context layers (Chan et al. 2016, "Listen, Attend and Spell": pyramidal BLSTM; Peddinti et al. 2015: subsampling TDNN;
+ * no counterpart in the reference) -------------------------------------------------------------------------------------------------
+ * A context layer has a fourth member, the stride S (1 .. 8).  Let L, R, D be its other members, B = L + R + 1, and P the preceding
+ * layer's size.  The layer reads its predecessor in the PARENT time axis -- T steps, Tmin, len_s real frames in slot s -- and
+ * writes, and every layer behind it runs in, its OWN axis:
+ *      n_s = ceil(len_s / S)     T' = ceil(T / S)     Tmin' = ceil(Tmin / S)
+ *
+ * Forward, for j < n_s, block b = c / P, unit u = c % P:
+ *      ts               = clamp(S * j + (b - L) * D, 0, len_s - 1)
+ *      out[j][s][b*P+u] = x_op[ts][s][u]
+ * Bits are copied, operand to operand, exactly as section Context layers says for S = 1.  Rows j >= n_s below T', pad slots and
+ * pad columns are zeros.
+ *
+ * Pattern types of the new axis, the rule of section Input splicing: FIRST for j = 0, LAST for j = n_s - 1 > 0, NORMAL between,
+ * NONE for j >= n_s and for pad slots; the row map is built from them with Tmin' steps of unchecked rows.
+ *
+ * Targets of the new axis, when the fraction brought any: the target class and target row of frame j are those of parent row
+ * S * j, the frame the context is centred on; everything else is -1 / zero rows.  Two strided layers compose:
+ * ceil(ceil(len / S1) / S2) = ceil(len / (S1 * S2)), centred on S1 * S2 * j.  A CTC layer reads no per-frame targets; its lengths
+ * are n_s, and a sequence with more labels plus adjacent repeats than n_s has no alignment, under the existing rule.
+ *
+ * Backward.  When the preceding layer takes errors, for every real parent frame (ts, s) and unit u
+ *      dx[ts][s][u] = sum over b = 0 .. B-1 (outer, ascending)
+ *                     sum over j = 0 .. n_s-1 (inner, ascending) with clamp(S * j + (b - L) * D, 0, len_s - 1) == ts
+ *                         e[j][s][b * P + u]
+ * single fp32 additions from +0.0f in exactly that order, without atomics: held to bits.  A parent frame that no (b, j) reads gets
+ * +0.0 (with L = R = 0 and S = 2: the odd frames).  Every other row of the parent's current fraction, and the pad columns, are
+ * written as 0.
+ *
+ * Everything behind the layer goes by its own axis: T', Tmin' and N' = T' * PSp of every launch, the derived pattern types and row
+ * map, the dispatch estimate numSeqs * ((Tmin' + T' + 1) / 2), the LDS sizing of the recurrent kernels, the frame index
+ * n = t * PS + ps of the dropout key, the rows of layer norm and residual sums, the slot lengths a later context layer clamps to,
+ * the rows of cn_layer_read / cn_layer_write_output_errors (T' * PS rows, as under cn_ctx_set_input_splice), the softmax row
+ * statistics, the loss and #correct (summed over the frames the output layer classifies), the CTC sweeps and the default label cap
+ * min(max_seq_length of that axis, 512).  Buffers of the followers are sized by ceil(parent max_seq_length / S).  A follower may
+ * drop, normalise and be residual exactly as behind a plain context layer; a post output layer directly behind one stays refused.
+ *
+ * The axis -- slot lengths, pattern types, row map, classes, and the target rows of a post output layer -- is formed once per
+ * fraction, on the context's stream, by the strided layer's first forward pass of that fraction; every cn_fraction_load* (a
+ * prefetch hit included) makes it stale.  cn_layer_forward, cn_layer_backward, cn_loss_*, cn_layer_read and
+ * cn_layer_write_output_errors in an axis that has not been formed for the current fraction fail with CN_ERR_STATE.
+ *
+ * Stride 1 is the plain context layer: the same launches and the same bits.  With no strided layer in the net the library launches
+ * exactly what it launches without this section and allocates nothing for it. */
+/* cn_layer_create_context with a stride; 1 <= stride <= 8, else CN_ERR_BAD_ARG.  cn_layer_create_context is the stride-1 call. */
+int  cn_layer_create_context_strided(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, int stride, cn_layer **out);
+/* 1 for a plain context layer; a layer of another kind: CN_ERR_BAD_ARG. */
+int  cn_layer_context_stride(const cn_layer *layer, int *stride);
+/* The steps of the current fraction as this layer sees them, and the product of the strides in front of it (any pointer may be
+ * NULL); host arithmetic, no synchronisation.  Before a load: CN_ERR_STATE. */
+int  cn_layer_time(const cn_layer *layer, int *T, int *Tmin, int *rate);
+
 /* ---- LAMB (You et al. 2020, "Large Batch Optimization for Deep Learning"; no counterpart in the reference) ---------------------
  * A third update family beside the cn_sgd_* and cn_adam_* trios, with the same three entry points and the same protocol: Adam's
  * moments give a direction u per weight, and every LAYER's step is scaled by a trust ratio |w| / |u| of its own, so that the

@@ -64,6 +64,14 @@ int cn_dbg_row_map_counts(cn_ctx *ctx, int out[3]);
 /* Loads of this context that found their fraction announced and re-laid out (cn_fraction_prefetch / _resident) and only exchanged
  * buffers. */
 int cn_dbg_prefetch_hits(cn_ctx *ctx, int *hits);
+/* The time axis a layer runs on (include/currennt_hip.h, section Strided context layers), as the device holds it for the current
+ * fraction: pat [T' * PSp] pattern types and tcls [T' * PSp] classes in the DEVICE's row order (row j * PSp + s, pad slots
+ * included), len [PSp] slot lengths; any pointer may be NULL.  rows must be T' * PSp (CN_ERR_SHAPE); an axis that has not been
+ * formed for the current fraction: CN_ERR_STATE.  [sync] */
+int cn_dbg_layer_axis(cn_layer *layer, char *pat, int *tcls, int *len, size_t rows, int *PSp);
+/* What a read-back in the reference layout cannot show: the number of elements with a non-zero bit in the pad columns and pad
+ * slots of the operand rows the layer's followers read (T' * PSp rows of the padded pitch, the current fraction).  [sync] */
+int cn_dbg_layer_pad_bits(cn_layer *layer, long long *nonzero);
 
 /* The launches of a CN_LAYER_CTC layer (csrc/cn_ctc.hip: the sweeps, then the output errors) on posteriors of the caller's choice.
  * Host arrays in the reference layout: y [T * PS][C] posteriors (blank = C - 1), pat [T * PS] pattern types, the labels as for

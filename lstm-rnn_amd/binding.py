@@ -42,7 +42,7 @@ EXPORTS = [
     "cn_layer_recurrent_kernel",
     "cn_comm_unique_id", "cn_comm_init", "cn_comm_destroy", "cn_comm_info", "cn_comm_backend", "cn_allreduce_grads", "cn_loss_read_global",
     # include/currennt_hip_debug.h
-    "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits", "cn_dbg_gemm_tn_group", "cn_dbg_fold",
+    "cn_dbg_gemm_nt", "cn_dbg_gemm_tn", "cn_dbg_row_map_counts", "cn_dbg_prefetch_hits", "cn_dbg_gemm_tn_group", "cn_dbg_fold", "cn_dbg_layer_axis", "cn_dbg_layer_pad_bits",
     # the CTC post output layer: include/currennt_hip.h and its kernel-level hook in include/currennt_hip_debug.h
     "cn_layer_set_label_sequences", "cn_dbg_ctc",
     # include/currennt_hip.h, section Dropout, and its hook in include/currennt_hip_debug.h
@@ -65,7 +65,7 @@ EXPORTS = [
     # include/currennt_hip.h, section Weight decay
     "cn_ctx_set_weight_decay", "cn_ctx_get_weight_decay",
     # include/currennt_hip.h, section Context layers
-    "cn_layer_create_context", "cn_layer_context",
+    "cn_layer_create_context", "cn_layer_context", "cn_layer_create_context_strided", "cn_layer_context_stride", "cn_layer_time",
     # include/currennt_hip.h, section LAMB
     "cn_lamb_update", "cn_lamb_update_all", "cn_ctx_arm_lamb", "cn_ctx_set_trust_bounds", "cn_ctx_get_trust_bounds", "cn_layer_trust_ratio",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
@@ -245,6 +245,11 @@ def load_library():
     L.cn_layer_upload_weight_average.argtypes = [vp, vp, C.c_size_t]
     L.cn_layer_create_context.argtypes = [vp, vp, ci, ci, ci, C.POINTER(vp)]
     L.cn_layer_context.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.cn_layer_create_context_strided.argtypes = [vp, vp, ci, ci, ci, ci, C.POINTER(vp)]
+    L.cn_layer_context_stride.argtypes = [vp, C.POINTER(ci)]
+    L.cn_layer_time.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.cn_dbg_layer_axis.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(ci)]
+    L.cn_dbg_layer_pad_bits.argtypes = [vp, C.POINTER(C.c_longlong)]
     _LIB = L
     return L
 

@@ -83,6 +83,24 @@ bool same_rule(const UpdateRule &a, const UpdateRule &b)
 // ---------------------------------------------------------------------------------------------
 // objects
 // ---------------------------------------------------------------------------------------------
+// The time axis a layer runs on (include/currennt_hip.h, section Strided context layers): the steps of the current fraction, the
+// pattern types inside an allocation with guard steps and the row map behind them (cn_ctx::pat_bytes), the estimate of the real
+// frames, the classes, and the slot lengths.  The context owns the base axis, a mirror of its own members (sync_base); every
+// strided context layer owns one more, formed on the context's stream by its first forward pass of a fraction (serial: of load
+// number cn_ctx::frac_serial).  Every layer reaches its axis through cn_layer::ax.
+struct TimeAxis {
+    int T = 0, Tmin = 0, N = 0, Next = 0, maxT = 0;
+    int rate = 1;                                     // product of the strides in front of the axis
+    char *pat = nullptr, *pat_raw = nullptr;
+    size_t pat_maxN = 0, pat_guard = 0;
+    int est_real = 0;
+    int *tcls = nullptr;
+    int *len = nullptr;                               // [PSp] real frames per slot (the base axis: cn_ctx::cx_len, formed on demand)
+    uint64_t serial = 0;
+    cn_layer *owner = nullptr;                        // the strided layer that forms the axis (nullptr: the base axis)
+    int *rowmap() const { return pat_raw ? (int *)(pat_raw + ((pat_maxN + 2 * pat_guard + 15) & ~(size_t)15)) : nullptr; }
+};
+
 struct cn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -248,6 +266,8 @@ struct cn_ctx {
     long acc_n[KC_COUNT] = {};
 
     size_t esz() const { return f32 ? 4 : 2; }
+
+    TimeAxis base;                        // the axis of the input layer and of everything in front of the first strided layer
 };
 
 struct cn_layer {
@@ -304,6 +324,17 @@ struct cn_layer {
     bool context = false;
     int cx_left = 0, cx_right = 0, cx_dil = 1;
     ContextArgs cx{};
+    // ... with a stride above 1 (section Strided context layers): the layer reads its predecessor in that layer's axis and owns
+    // the axis it writes in and its followers run in
+    int cx_stride = 1;
+    StrideArgs sx{};
+    TimeAxis own_axis;
+    // the time axis this layer's rows lie in: the context's base axis, or that of the nearest strided layer in front (or this one)
+    TimeAxis *ax = nullptr;
+    // post output layer behind a strided layer: the target rows of its axis, gathered from `targets` (which the loads fill at the
+    // base rate) by the first use in a fraction
+    float *ax_targets = nullptr;
+    uint64_t ax_targets_serial = 0;
 
     // lstm internals
     float *acts = nullptr, *cell = nullptr, *th = nullptr;
@@ -403,11 +434,26 @@ bool option_get(const Options &o, const char *name, long *value)
 
 namespace {
 
+// the base axis mirrors the context's own members: behind everything that sets or swaps them
+void sync_base(cn_ctx *c)
+{
+    TimeAxis &b = c->base;
+    b.T = c->T; b.Tmin = c->Tmin; b.N = c->N; b.Next = c->Next; b.maxT = c->maxT; b.rate = 1;
+    b.pat = c->d_pat; b.pat_raw = c->d_pat_raw; b.pat_maxN = c->pat_maxN; b.pat_guard = c->pat_guard;
+    b.est_real = c->est_real; b.tcls = c->d_tcls; b.len = c->cx_len; b.serial = c->frac_serial; b.owner = nullptr;
+}
+
 // every entry point that touches the device: bind it and make the context's options the ones the launch paths see
 void enter(cn_ctx *c)
 {
     HIP_CHECK(hipSetDevice(c->device));
     cn::t_opt = &c->opt;
+    // the mirror is hand-kept: whoever assigns or swaps one of the mirrored members and forgets sync_base is told at the next call
+    const TimeAxis &b = c->base;
+    if (b.T != c->T || b.Tmin != c->Tmin || b.N != c->N || b.Next != c->Next || b.maxT != c->maxT || b.pat != c->d_pat ||
+        b.pat_raw != c->d_pat_raw || b.pat_maxN != c->pat_maxN || b.pat_guard != c->pat_guard || b.est_real != c->est_real ||
+        b.tcls != c->d_tcls || b.len != c->cx_len || b.serial != c->frac_serial)
+        throw cn_error(CN_ERR_STATE, "internal: the base time axis is out of date (a member of the context changed without sync_base)");
 }
 
 void *dalloc(cn_layer *l, size_t bytes)
@@ -456,11 +502,13 @@ hipStream_t masked_stream(int device, int ncu, int total)
 // ---- row map -------------------------------------------------------------------------------
 // The N-wide products of a fraction may skip its dummy frames (GemmNT::rowmap): the map was built behind the re-layout of the
 // fraction that is current now (launch_fraction_load / launch_rowmap)
-static void use_rowmap(cn_ctx *c, GemmNT &g)
+// (of the axis the layer's rows lie in)
+static void use_rowmap(const cn_layer *l, GemmNT &g)
 {
-    if (opt().no_nt_rowmap || !c->d_pat_raw || !c->loaded) return;
-    int *rm = c->rowmap_of(c->d_pat_raw);
-    g.rowcnt = rm; g.rowmap = rm + 4; g.dummymap = rm + 4 + c->pat_maxN; g.m_est = c->est_real;
+    const TimeAxis *ax = l->ax;
+    if (opt().no_nt_rowmap || !ax->pat_raw || !l->ctx->loaded) return;
+    int *rm = ax->rowmap();
+    g.rowcnt = rm; g.rowmap = rm + 4; g.dummymap = rm + 4 + ax->pat_maxN; g.m_est = ax->est_real;
 }
 
 // ---- timing ---------------------------------------------------------------------------------
@@ -493,7 +541,7 @@ float *posteriors(cn_layer *o)
     cn_ctx *c = o->ctx;
     o->sm_read = true;
     if (o->sm_lazy) {
-        launch_softmax_normalise(c->stream, softmax_fast(c), o->out_f32, c->d_pat, c->N, o->size, o->Lp, o->sm_stat);
+        launch_softmax_normalise(c->stream, softmax_fast(c), o->out_f32, o->ax->pat, o->ax->N, o->size, o->Lp, o->sm_stat);
         o->sm_lazy = false;
     }
     return o->out_f32;
@@ -728,18 +776,19 @@ template <typename F> void on_side(cn_layer *l, F &&f, bool fork_attached = fals
     bool slow = c->side_slow && l->prev && l->prev->lstm;
     const bool side_rule = !opt().no_side_rule;
     // ~1.5 TFLOP/s per CU on the 64 x 64 tiles; the 256 x 256 kernel of the wide layers (cn_gemm_tn_big.hip) runs at ~3
-    const bool big = c->prec == P_BF16 && c->N >= 4096 && (l->lstm ? l->Hp >= 256 && l->Pp >= 192 : l->Lp >= 512 && l->Pp >= 192);
+    const TimeAxis *ax = l->ax;
+    const bool big = c->prec == P_BF16 && ax->N >= 4096 && (l->lstm ? l->Hp >= 256 && l->Pp >= 192 : l->Lp >= 512 && l->Pp >= 192);
     // CUs the recurrent kernel that follows on the main stream will occupy when it is a cluster launch (0: one-CU kernels)
     int rec_cus = 0;
     if (l->prev && l->prev->lstm) {
         LstmRec r{};
-        r.Hp = l->prev->Hp; r.dirs = l->prev->dirs; r.PS = c->PSp; r.T = c->T; r.rpl = c->rpl; r.num_cus = r.cluster_cus = c->num_cus;
+        r.Hp = l->prev->Hp; r.dirs = l->prev->dirs; r.PS = c->PSp; r.T = ax->T; r.rpl = c->rpl; r.num_cus = r.cluster_cus = c->num_cus;
         rec_cus = c->d_xch ? lstm_cluster_bwd_cus(c->prec, r) : 0;
     }
     if (slow && side_rule) {
-        const double flops = 2.0 * c->N * (l->lstm ? (double)l->dirs * 4 * l->Hp * (l->Pp + l->Hp) : (double)l->Lp * l->Pp);
+        const double flops = 2.0 * ax->N * (l->lstm ? (double)l->dirs * 4 * l->Hp * (l->Pp + l->Hp) : (double)l->Lp * l->Pp);
         const double t_side = flops / (c->side_cus * (big ? 3.0e12 : 1.5e12));
-        const double t_rec = c->T * (l->prev->Hp > 192 ? 1.2e-6 : 0.5e-6);                           // cluster / single-CU step
+        const double t_rec = ax->T * (l->prev->Hp > 192 ? 1.2e-6 : 0.5e-6);                           // cluster / single-CU step
         if (t_side > 0.8 * t_rec) slow = false;
         // a cluster grid that covers a large part of the chip (two sequences per two-CU cluster: 112-128 CUs, each claiming its
         // CU's whole LDS) lands on the masked CUs too and leaves the masked stream a fraction of them: no slow lane then
@@ -982,15 +1031,15 @@ void flush_loss(cn_ctx *c)
     if (!c->loss_deferred) return;
     c->loss_deferred = false;
     Timed tm(c, KC_OTHER);
-    launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, c->d_loss_acc, false);
+    launch_rowstat_reduce(c->stream, c->d_rowstat, c->rowstat_of ? c->rowstat_of->ax->N : c->N, c->d_loss_acc, false);
 }
 
 // ---- forward / backward sequences -----------------------------------------------------------
 void lstm_rec_args(cn_layer *l, LstmRec &r)
 {
     cn_ctx *c = l->ctx;
-    r.H = l->H; r.Hp = l->Hp; r.dirs = l->dirs; r.PS = c->PSp; r.T = c->T; r.Tmin = c->Tmin;
-    r.pat = c->d_pat;
+    r.H = l->H; r.Hp = l->Hp; r.dirs = l->dirs; r.PS = c->PSp; r.T = l->ax->T; r.Tmin = l->ax->Tmin;
+    r.pat = l->ax->pat;
     r.acts = l->acts; r.cell = l->cell; r.th = l->th; r.y_op = l->out_op; r.Wrec = l->Wrec; r.peep = l->peep_p;
     r.pre16 = nullptr;
     r.err = l->err; r.delta_op = l->delta_op; r.WrecT = l->WrecT; r.dbias = l->dbias; r.dpeep = l->dpeep;
@@ -1040,9 +1089,9 @@ void ensure_det(cn_layer *l)
 void check_rec_lds(const cn_layer *l, bool bwd)
 {
     const cn_ctx *c = l->ctx;
-    const size_t need = lstm_rec_lds_bytes(c->prec, bwd, l->Hp, c->rpl, c->T);
+    const size_t need = lstm_rec_lds_bytes(c->prec, bwd, l->Hp, c->rpl, l->ax->T);
     if (need > 160 * 1024)
-        throw cn_error(CN_ERR_SHAPE, "LSTM layer with " + std::to_string(l->H) + " units per direction, " + std::to_string(c->T) +
+        throw cn_error(CN_ERR_SHAPE, "LSTM layer with " + std::to_string(l->H) + " units per direction, " + std::to_string(l->ax->T) +
                        " time steps: the recurrent " + (bwd ? "backward" : "forward") + " kernel needs " + std::to_string(need / 1024) +
                        " KB of LDS per workgroup (160 KB available)" + (c->prec == P_F32 ? "; use CN_PREC_BF16 or CN_PREC_BF16X3 for layers this wide" : "") +
                        " or shorter fractions (truncate_seq)");
@@ -1106,10 +1155,10 @@ void residual_sum(cn_layer *l)
     if (!l->residual) return;
     const cn_layer *p = l->prev;
     ResArgs &a = l->res;
-    a.N = c->N; a.own = unit_map(l); a.prev = unit_map(p);
+    a.N = l->ax->N; a.own = unit_map(l); a.prev = unit_map(p);
     a.same_map = same_columns(a.own, a.prev);
     Timed tm(c, KC_OTHER);
-    launch_residual_fwd(c->stream, c->f32, a, c->d_pat, l->out_op, follower_operand(p), l->res_sum);
+    launch_residual_fwd(c->stream, c->f32, a, l->ax->pat, l->out_op, follower_operand(p), l->res_sum);
     l->summed = true;
 }
 // behind K8 and mask_handed_back_error on the main stream: the skip path's term of the preceding layer's outputErrors.  `e`: this
@@ -1118,7 +1167,7 @@ void residual_add_error(cn_layer *l, const float *e)
 {
     if (!l->summed || !takes_err(l->prev)) return;
     Timed tm(l->ctx, KC_OTHER);
-    launch_residual_bwd(l->ctx->stream, l->res, l->ctx->d_pat, e, l->prev->err);
+    launch_residual_bwd(l->ctx->stream, l->res, l->ax->pat, e, l->prev->err);
 }
 
 // ---- layer normalization of a layer's input (include/currennt_hip.h, section Layer normalization) ----
@@ -1130,9 +1179,9 @@ const void *normalized_input(cn_layer *l, const void *x)
     l->normed = l->layer_norm;
     if (!l->normed) return x;
     LnArgs &a = l->ln;
-    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev); a.eps = l->ln_eps;
+    a.N = l->ax->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev); a.eps = l->ln_eps;
     Timed tm(c, KC_OTHER);
-    launch_layernorm_fwd(c->stream, c->f32, a, c->d_pat, x, l->in_norm, l->ln_rstd);
+    launch_layernorm_fwd(c->stream, c->f32, a, l->ax->pat, x, l->in_norm, l->ln_rstd);
     return l->in_norm;
 }
 // behind K8 and mask_handed_back_error on the main stream, in front of residual_add_error: what K8 wrote is dL/d(normalised
@@ -1142,7 +1191,7 @@ void normalize_handed_back_error(cn_layer *l)
 {
     if (!l->normed || !takes_err(l->prev)) return;
     Timed tm(l->ctx, KC_OTHER);
-    launch_layernorm_bwd(l->ctx->stream, l->ctx->f32, l->ln, l->ctx->d_pat, l->in_norm, l->ln_rstd, l->prev->err);
+    launch_layernorm_bwd(l->ctx->stream, l->ctx->f32, l->ln, l->ax->pat, l->in_norm, l->ln_rstd, l->prev->err);
 }
 
 // ---- dropout on a layer's input (include/currennt_hip.h, section Dropout) ----
@@ -1157,7 +1206,7 @@ const void *forward_input(cn_layer *l)
     l->dropped = c->drop_enable && l->drop_rate > 0.f;
     if (!l->dropped) return x;
     DropArgs &a = l->drop;
-    a.N = c->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev);
+    a.N = l->ax->N; a.PS = c->PS; a.PSp = c->PSp; a.prev = unit_map(l->prev);
     a.k0 = (uint32_t)c->drop_seed + (uint32_t)l->ordinal; a.k1 = (uint32_t)(c->drop_seed >> 32);
     a.pass_lo = (uint32_t)c->drop_pass; a.pass_hi = (uint32_t)(c->drop_pass >> 32);
     a.thr = (uint32_t)std::floor((double)l->drop_rate * 4294967296.0);
@@ -1256,16 +1305,69 @@ void context_lengths(cn_ctx *c)
     launch_context_lengths(c->stream, c->d_pat, c->T, c->PSp, c->cx_len);
     c->cx_serial = c->frac_serial;
 }
+// ---- the time axis of a layer (include/currennt_hip.h, section Strided context layers) ----
+// A call in an axis that its strided layer has not formed for the current fraction has no steps, pattern types or classes to go by
+void require_axis(const cn_layer *l, const char *fn)
+{
+    const TimeAxis *ax = l->ax;
+    if (ax->owner && ax->serial != l->ctx->frac_serial)
+        throw cn_error(CN_ERR_STATE, std::string(fn) + ": the strided context layer in front of this layer has no forward pass of the current fraction");
+}
+// the slot lengths of the axis a context layer READS (its predecessor's): the base axis forms them on demand
+const int *parent_lengths(cn_layer *l, const char *fn)
+{
+    cn_ctx *c = l->ctx;
+    require_axis(l->prev, fn);
+    if (!l->prev->ax->owner) { context_lengths(c); return c->cx_len; }
+    return l->prev->ax->len;
+}
+// A strided layer's own axis, once per fraction, in front of its gather: steps by host arithmetic; lengths, pattern types and
+// classes by one kernel over all T' * PSp rows; then the row map with Tmin' steps of unchecked rows
+void form_axis(cn_layer *l, const int *plen)
+{
+    cn_ctx *c = l->ctx;
+    TimeAxis &ax = l->own_axis;
+    if (ax.serial == c->frac_serial) return;
+    const TimeAxis &pa = *l->prev->ax;
+    const int S = l->cx_stride;
+    ax.T = ceil_div(pa.T, S); ax.Tmin = ceil_div(pa.Tmin, S); ax.N = ax.T * c->PSp; ax.Next = ax.T * c->PS;
+    ax.est_real = c->numSeqs * ((ax.Tmin + ax.T + 1) / 2);
+    launch_stride_axis(c->stream, S, ax.T, c->PSp, plen, pa.tcls, ax.len, ax.pat, ax.tcls);
+    launch_rowmap(c->stream, ax.pat, ax.N, ax.rowmap(), (int)ax.pat_maxN, ax.Tmin * c->PSp);
+    ax.serial = c->frac_serial;
+}
+// the target rows a post output layer compares with: the loads' own, or behind a strided layer the rows of its axis
+// (every caller -- the post layer's backward pass, cn_loss_eval, cn_loss_accumulate -- holds a Timed scope of KC_OTHER around it)
+const float *post_targets(cn_layer *post)
+{
+    cn_ctx *c = post->ctx;
+    const TimeAxis *ax = post->ax;
+    if (!ax->owner || !post->targets) return post->targets;
+    if (post->ax_targets_serial != c->frac_serial) {
+        launch_stride_targets(c->stream, ax->rate, ax->T, c->PSp, post->size, ax->len, post->targets, post->ax_targets);
+        post->ax_targets_serial = c->frac_serial;
+    }
+    return post->ax_targets;
+}
 void context_forward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     const cn_layer *p = l->prev;
-    ContextArgs &a = l->cx;
-    a.T = c->T; a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
-    a.prev = unit_map(p);
     Timed tm(c, KC_OTHER);
-    context_lengths(c);
-    launch_context_fwd(c->stream, c->f32, a, c->cx_len, follower_operand(p), l->out_op);
+    const int *len = parent_lengths(l, "cn_layer_forward");
+    if (l->cx_stride > 1) {
+        StrideArgs &a = l->sx;
+        a.Tin = p->ax->T; a.Tout = ceil_div(p->ax->T, l->cx_stride); a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1;
+        a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp; a.S = l->cx_stride;
+        a.prev = unit_map(p);
+        form_axis(l, len);
+        launch_stride_fwd(c->stream, c->f32, a, len, follower_operand(p), l->out_op);
+        return;
+    }
+    ContextArgs &a = l->cx;
+    a.T = l->ax->T; a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
+    a.prev = unit_map(p);
+    launch_context_fwd(c->stream, c->f32, a, len, follower_operand(p), l->out_op);
 }
 // behind the follower's K8 (and its mask / normalisation / skip term) on the main stream: the preceding layer's outputErrors.
 // Nothing to do when that layer takes none -- the follower then had no K8 either.
@@ -1273,10 +1375,16 @@ void context_backward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     if (!takes_err(l->prev)) return;
-    if (l->cx.T != c->T || l->cx.PSp != c->PSp) throw cn_error(CN_ERR_STATE, "cn_layer_backward: the context layer has no forward pass of the current fraction");
+    const char *stale = "cn_layer_backward: the context layer has no forward pass of the current fraction";
+    if (l->cx_stride > 1) {
+        if (l->sx.Tin != l->prev->ax->T || l->sx.PSp != c->PSp || l->own_axis.serial != c->frac_serial) throw cn_error(CN_ERR_STATE, stale);
+        Timed tm(c, KC_OTHER);
+        launch_stride_bwd(c->stream, l->sx, parent_lengths(l, "cn_layer_backward"), l->err, l->prev->err);
+        return;
+    }
+    if (l->cx.T != l->ax->T || l->cx.PSp != c->PSp) throw cn_error(CN_ERR_STATE, stale);
     Timed tm(c, KC_OTHER);
-    context_lengths(c);
-    launch_context_bwd(c->stream, l->cx, c->cx_len, l->err, l->prev->err);
+    launch_context_bwd(c->stream, l->cx, parent_lengths(l, "cn_layer_backward"), l->err, l->prev->err);
 }
 
 void lstm_forward(cn_layer *l)
@@ -1298,8 +1406,8 @@ void lstm_forward(cn_layer *l)
         g.A = x; g.lda = l->Pp; g.B = l->Win; g.ldb = l->Pp;
         g.C = l->acts; g.ldc = R; g.C2 = nullptr; g.ldc2 = 0; g.bias = l->bias_p; g.act = ACT_IDENTITY;
         if (pre16) { g.C = nullptr; g.C2 = l->pre16; g.ldc2 = R; }
-        g.M = c->N; g.N = R; g.K = l->Pp;
-        if (l->prev->lstm) use_rowmap(c, g);          // (y = 0 on dummy frames; what the caller's inputs hold there is the caller's business)
+        g.M = l->ax->N; g.N = R; g.K = l->Pp;
+        if (l->prev->lstm) use_rowmap(l, g);          // (y = 0 on dummy frames; what the caller's inputs hold there is the caller's business)
         launch_gemm_nt(c->stream, c->prec, g);
     }
     {   // K2+K3+K4: the whole time loop
@@ -1315,7 +1423,7 @@ void lstm_forward(cn_layer *l)
 void lstm_backward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
-    const int R = l->dirs * 4 * l->Hp, Hp = l->Hp, PS = c->PSp, N = c->N;
+    const int R = l->dirs * 4 * l->Hp, Hp = l->Hp, PS = c->PSp, N = l->ax->N;
     const size_t e = c->esz();
     repack(l);
     const bool noisy = backward_noise(l);   // every backward product with a weight in it then reads the noisy set: WrecT, peep, WinT
@@ -1344,7 +1452,7 @@ void lstm_backward(cn_layer *l)
         g.A = l->delta_op; g.lda = R; g.B = noisy ? l->nWinT : l->WinT; g.ldb = R;
         g.C = l->prev->err; g.ldc = l->prev->Lp; g.bias = nullptr; g.act = ACT_IDENTITY;
         g.M = N; g.N = l->Pp; g.K = R;
-        use_rowmap(c, g);
+        use_rowmap(l, g);
         hipEvent_t fork = c->timing ? nullptr : fork_event(l);     // (timing mode records its own events around the kernel)
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
@@ -1417,8 +1525,8 @@ void ff_forward(cn_layer *l)
         g.C = l->out_f32; g.ldc = l->Lp;
         g.C2 = (!c->f32 && !softmax) ? l->out_op : nullptr; g.ldc2 = l->Lp;
         g.bias = l->bias_p; g.act = ff_act(l->kind);
-        g.M = c->N; g.N = l->Lp; g.K = l->Pp;
-        if (l->prev->lstm) use_rowmap(c, g);          // (y = 0 on dummy frames, ComputeBlockOutputFn; a feed-forward layer's output is act(bias) there)
+        g.M = l->ax->N; g.N = l->Lp; g.K = l->Pp;
+        if (l->prev->lstm) use_rowmap(l, g);          // (y = 0 on dummy frames, ComputeBlockOutputFn; a feed-forward layer's output is act(bias) there)
         launch_gemm_nt(c->stream, c->prec, g);
     }
     if (softmax) {
@@ -1435,10 +1543,10 @@ void ff_forward(cn_layer *l)
         const bool lazy_force = opt().lazy_softmax;                              // the exact lazy kernels
         l->sm_lazy = stat && l->sm_stat && l->sm_lazy_next && !l->has_follower && !lazy_off && (softmax_fast(c) || lazy_force);
         l->sm_read = false;
-        launch_softmax_fwd(c->stream, l->out_f32, c->d_pat, c->N, l->size, l->Lp, stat ? c->d_tcls : nullptr, stat ? c->d_rowstat : nullptr,
+        launch_softmax_fwd(c->stream, l->out_f32, l->ax->pat, l->ax->N, l->size, l->Lp, stat ? l->ax->tcls : nullptr, stat ? c->d_rowstat : nullptr,
                            softmax_fast(c), l->sm_lazy ? l->sm_stat : nullptr);
         c->rowstat_of = stat ? l : nullptr;
-        if (!c->f32 && l->has_follower) launch_pad_convert(c->stream, false, l->out_f32, c->N, l->Lp, l->out_op, l->Lp);
+        if (!c->f32 && l->has_follower) launch_pad_convert(c->stream, false, l->out_f32, l->ax->N, l->Lp, l->out_op, l->Lp);
     }
     residual_sum(l);
 }
@@ -1446,7 +1554,7 @@ void ff_forward(cn_layer *l)
 void ff_backward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
-    const int N = c->N;
+    const int N = l->ax->N;
     repack(l);
     const bool noisy = backward_noise(l);
     if (c->det) ensure_det(l);
@@ -1458,7 +1566,7 @@ void ff_backward(cn_layer *l)
             dummy_deltas_zero = true;             // softmax_mcc_bwd_kernel stores zeros for every pattern that is not real
             // bf16 mode: the fp32 outputErrors stay unwritten (read back from the bf16 operand copy if anyone asks)
             const bool with_loss = c->loss_deferred && c->rowstat_of == l && softmax_mcc_bwd_takes_loss(l->Lp);
-            launch_softmax_mcc_bwd(c->stream, c->f32, l->out_f32, c->d_tcls, c->d_pat, N, l->size, l->Lp, c->f32 ? l->err : nullptr, l->delta_op, l->dbias,
+            launch_softmax_mcc_bwd(c->stream, c->f32, l->out_f32, l->ax->tcls, l->ax->pat, N, l->size, l->Lp, c->f32 ? l->err : nullptr, l->delta_op, l->dbias,
                                    with_loss ? c->d_rowstat : nullptr, with_loss ? c->d_loss_acc : nullptr, c->d_loss + 6, l->sm_lazy ? l->sm_stat : nullptr,
                                    softmax_fast(c), c->d_colpart, c->det ? l->det_colpart : nullptr, &colfold);
             l->sm_lazy_next = !l->sm_read;
@@ -1471,8 +1579,8 @@ void ff_backward(cn_layer *l)
             // a marked layer hands its outputErrors on as they came in: launch_ff_delta below overwrites them in place
             if (l->summed && takes_err(l->prev))
                 HIP_CHECK(hipMemcpyAsync(l->res_e, l->err, (size_t)N * l->Lp * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            if (l->mcc_pending) launch_mcc_backward(c->stream, y, c->d_tcls, N, l->size, l->Lp, l->err);
-            if (l->kind == CN_LAYER_SOFTMAX) launch_softmax_bwd(c->stream, y, l->err, c->d_pat, N, l->size, l->Lp);
+            if (l->mcc_pending) launch_mcc_backward(c->stream, y, l->ax->tcls, N, l->size, l->Lp, l->err);
+            if (l->kind == CN_LAYER_SOFTMAX) launch_softmax_bwd(c->stream, y, l->err, l->ax->pat, N, l->size, l->Lp);
             launch_ff_delta(c->stream, c->f32, ff_act(l->kind), y, l->err, l->delta_op, N, l->size, l->Lp);
             launch_colsum(c->stream, l->err, N, l->Lp, l->dbias, c->det ? l->det_colpart : nullptr, &colfold);
         }
@@ -1485,7 +1593,7 @@ void ff_backward(cn_layer *l)
         g.A = l->delta_op; g.lda = l->Lp; g.B = noisy ? l->nWinT : l->WinT; g.ldb = l->Lp;
         g.C = l->prev->err; g.ldc = l->prev->Lp; g.bias = nullptr; g.act = ACT_IDENTITY;
         g.M = N; g.N = l->Pp; g.K = l->Lp;
-        if (dummy_deltas_zero) use_rowmap(c, g);
+        if (dummy_deltas_zero) use_rowmap(l, g);
         hipEvent_t fork = c->timing ? nullptr : fork_event(l);
         launch_gemm_nt(c->stream, c->prec, g, fork);
         fork_attached = fork != nullptr;
@@ -1900,6 +2008,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
         l->ordinal = ctx->next_ordinal;
         l->PS = preceding ? preceding->PS : parallel_sequences;
         l->maxT = preceding ? preceding->maxT : max_seq_length;
+        l->ax = preceding ? preceding->ax : &ctx->base;
         if (!preceding) {
             // sequences per workgroup of the recurrent kernels: the fewest (4, 8, 16) that still give at most
             // one workgroup per CU for a bidirectional layer; PS is padded to a whole number of groups
@@ -1928,6 +2037,7 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
             }
             HIP_CHECK(hipMalloc((void **)&ctx->d_tcls, maxN * sizeof(int)));
             HIP_CHECK(hipMemsetAsync(ctx->d_tcls, 0xFF, maxN * sizeof(int), ctx->stream));     // pad slots: target class -1
+            sync_base(ctx);
             break; }
         case CN_LAYER_LSTM:
         case CN_LAYER_BLSTM: {
@@ -2020,7 +2130,9 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
             if (kind == CN_LAYER_MULTICLASS_CLASSIFICATION && !ctx->d_rowstat)
                 HIP_CHECK(hipMalloc((void **)&ctx->d_rowstat, maxN * 2 * sizeof(float)));
             if (kind != CN_LAYER_MULTICLASS_CLASSIFICATION) {
-                l->targets = (float *)dalloc(l, maxN * size * sizeof(float));
+                // (the loads fill `targets` at the base rate; behind a strided layer the rows of the layer's axis are gathered from them)
+                l->targets = (float *)dalloc(l, (size_t)ctx->PSp * ctx->maxT * size * sizeof(float));
+                if (l->ax->owner) l->ax_targets = (float *)dalloc(l, maxN * size * sizeof(float));
                 if (!ctx->d_rowstat) HIP_CHECK(hipMalloc((void **)&ctx->d_rowstat, maxN * 2 * sizeof(float)));
             }
             break; }
@@ -2057,6 +2169,11 @@ int cn_layer_create(cn_ctx *ctx, cn_layer_kind kind, cn_layer *preceding, int si
 
 int cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, cn_layer **out)
 {
+    return cn_layer_create_context_strided(ctx, preceding, left, right, dilation, 1, out);
+}
+
+int cn_layer_create_context_strided(cn_ctx *ctx, cn_layer *preceding, int left, int right, int dilation, int stride, cn_layer **out)
+{
     if (!ctx || !out) { g_last_error = "cn_layer_create_context: NULL argument"; return CN_ERR_BAD_ARG; }
     *out = nullptr;
     cn_layer *l = nullptr;
@@ -2069,11 +2186,15 @@ int cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int righ
             throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: left and right must lie in 0..32 (" + std::to_string(left) + ", " + std::to_string(right) + ")");
         if (dilation < 1 || dilation > 16)
             throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context: dilation must lie in 1..16 (" + std::to_string(dilation) + ")");
+        if (stride < 1 || stride > 8)
+            throw cn_error(CN_ERR_BAD_ARG, "cn_layer_create_context_strided: stride must lie in 1..8 (" + std::to_string(stride) + ")");
         l = new cn_layer;
         l->ctx = ctx; l->kind = CN_LAYER_CONTEXT; l->prev = preceding; l->context = true;
         l->cx_left = left; l->cx_right = right; l->cx_dil = dilation;
         l->ordinal = ctx->next_ordinal;
-        l->PS = preceding->PS; l->maxT = preceding->maxT; l->PSp = ctx->PSp;
+        l->cx_stride = stride;
+        l->PS = preceding->PS; l->maxT = ceil_div(preceding->maxT, stride); l->PSp = ctx->PSp;
+        l->ax = preceding->ax;
         l->P = preceding->size; l->Pp = preceding->Lp;
         l->size = (left + right + 1) * l->P;
         l->Lp = round_up(l->size, 32);                    // dense rows, whatever padding the preceding layer's have
@@ -2084,6 +2205,21 @@ int cn_layer_create_context(cn_ctx *ctx, cn_layer *preceding, int left, int righ
             HIP_CHECK(hipMalloc((void **)&ctx->cx_len, (size_t)l->PSp * sizeof(int)));
             HIP_CHECK(hipMemsetAsync(ctx->cx_len, 0, (size_t)l->PSp * sizeof(int), ctx->stream));
         }
+        if (stride > 1) {
+            // the layer's own axis: pattern types between CN_GUARD_STEPS of NONE on both sides with the row map behind them, as the
+            // context's (cn_layer_create's input case; the recurrent loops of a follower prefetch outside [0, T')), classes, lengths
+            TimeAxis &ax = l->own_axis;
+            const size_t guard = (size_t)CN_GUARD_STEPS * ctx->PSp;
+            ax.maxT = l->maxT; ax.rate = preceding->ax->rate * stride; ax.owner = l;
+            ax.pat_maxN = maxN; ax.pat_guard = guard;
+            ax.pat_raw = (char *)dalloc(l, cn_ctx::pat_bytes(maxN, guard));
+            ax.pat = ax.pat_raw + guard;
+            ax.tcls = (int *)dalloc(l, maxN * sizeof(int));
+            HIP_CHECK(hipMemsetAsync(ax.tcls, 0xFF, maxN * sizeof(int), ctx->stream));
+            ax.len = (int *)dalloc(l, (size_t)l->PSp * sizeof(int));
+            l->ax = &ax;
+        }
+        sync_base(ctx);                                   // (the base axis names cx_len)
         preceding->has_follower = true;                   // (a feed-forward or softmax predecessor keeps its operand copy for the gather)
         ctx->layers.push_back(l);
         ++ctx->next_ordinal;
@@ -2099,6 +2235,25 @@ int cn_layer_context(const cn_layer *layer, int *left, int *right, int *dilation
     if (left) *left = layer->cx_left;
     if (right) *right = layer->cx_right;
     if (dilation) *dilation = layer->cx_dil;
+    return CN_OK;
+}
+
+int cn_layer_context_stride(const cn_layer *layer, int *stride)
+{
+    if (!layer || !layer->context) { g_last_error = "cn_layer_context_stride: not a context layer"; return CN_ERR_BAD_ARG; }
+    if (stride) *stride = layer->cx_stride;
+    return CN_OK;
+}
+
+int cn_layer_time(const cn_layer *layer, int *T, int *Tmin, int *rate)
+{
+    if (!layer) { g_last_error = "cn_layer_time: layer is NULL"; return CN_ERR_BAD_ARG; }
+    if (!layer->ctx->loaded) { g_last_error = "cn_layer_time: no fraction loaded (call cn_fraction_load first)"; return CN_ERR_STATE; }
+    // host arithmetic from the base axis: what the strided layers in front form, whether they have run or not
+    const int r = layer->ax->rate;
+    if (T) *T = ceil_div(layer->ctx->T, r);
+    if (Tmin) *Tmin = ceil_div(layer->ctx->Tmin, r);
+    if (rate) *rate = r;
     return CN_OK;
 }
 
@@ -2233,6 +2388,7 @@ static void set_current(cn_ctx *ctx, const cn_fraction *f)
     ctx->est_real = f->num_sequences * ((f->min_seq_length + T + 1) / 2);
     ctx->loaded = true;
     ++ctx->frac_serial;
+    sync_base(ctx);
 }
 // the alternate buffers a prefetch re-laid its fraction out into become the current ones
 static void swap_in_prefetched(cn_ctx *ctx, cn_layer *input, cn_layer *post_output)
@@ -2418,7 +2574,7 @@ static CtcArgs ctc_args(cn_layer *post)
     cn_layer *o = post->prev;
     const size_t stride = post->ctc_stride;
     CtcArgs a{};
-    a.y = posteriors(o); a.pat = c->d_pat; a.T = c->T; a.PSp = c->PSp; a.C = post->size; a.Lp = o->Lp;
+    a.y = posteriors(o); a.pat = post->ax->pat; a.T = post->ax->T; a.PSp = c->PSp; a.C = post->size; a.Lp = o->Lp;
     a.labels = post->ctc_labels; a.next = a.labels + stride; a.first = a.next + stride; a.laboff = a.first + stride;
     a.maxS = post->ctc_maxS; a.alpha = post->ctc_alpha; a.beta = post->ctc_beta; a.Sp = round_up(post->ctc_maxS, 64);
     a.info = post->ctc_info; a.rowstat = post->ctc_rowstat; a.err = o->err;
@@ -2442,6 +2598,7 @@ int cn_layer_forward(cn_layer *layer)
         require_loaded(layer->ctx);
         finalize(layer->ctx);
         join_side(layer->ctx);
+        if (layer->cx_stride == 1) require_axis(layer, "cn_layer_forward");     // (a strided layer forms its own, from its predecessor's)
         if (layer->trainable && !takes_err(layer->prev) && opt().noise_ahead) noise_ahead(layer->ctx);
         if (layer->lstm) lstm_forward(layer);
         else if (layer->trainable) ff_forward(layer);
@@ -2459,6 +2616,7 @@ int cn_layer_backward(cn_layer *layer)
         refuse_swapped(c, "cn_layer_backward");
         require_loaded(c);
         finalize(c);
+        require_axis(layer, "cn_layer_backward");
         if (layer->trainable && layer->updated)
             throw cn_error(CN_ERR_STATE, c->arm.adam
                 ? "cn_layer_backward: the armed update of this layer's previous backward pass has not been completed (call cn_adam_update_all / cn_adam_update first)"
@@ -2475,7 +2633,7 @@ int cn_layer_backward(cn_layer *layer)
             else if (layer->kind == CN_LAYER_CTC)
                 launch_ctc_errors(c->stream, ctc_swept(layer, "cn_layer_backward"));
             else
-                launch_post_backward(c->stream, post_kind(layer), posteriors(o), layer->targets, c->d_pat, c->N, o->size, o->Lp, o->err);
+                launch_post_backward(c->stream, post_kind(layer), posteriors(o), post_targets(layer), layer->ax->pat, layer->ax->N, o->size, o->Lp, o->err);
         }
     });
 }
@@ -2485,8 +2643,10 @@ static void launch_loss(cn_layer *post, float *dst, bool per_call)
 {
     cn_ctx *c = post->ctx;
     cn_layer *o = post->prev;
+    const TimeAxis *ax = post->ax;
+    require_axis(post, per_call ? "cn_loss_eval" : "cn_loss_accumulate");
     if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION && c->rowstat_of == o) {      // the softmax forward pass left the row statistics
-        launch_rowstat_reduce(c->stream, c->d_rowstat, c->N, dst, per_call);
+        launch_rowstat_reduce(c->stream, c->d_rowstat, ax->N, dst, per_call);
         return;
     }
     if (post->kind == CN_LAYER_CTC) {                                                   // its own rows: -log p in the row of t = 0 of every slot
@@ -2496,9 +2656,9 @@ static void launch_loss(cn_layer *post, float *dst, bool per_call)
     }
     flush_loss(c);                     // (the row statistics are about to be overwritten)
     if (post->kind == CN_LAYER_MULTICLASS_CLASSIFICATION)
-        launch_mcc_eval(c->stream, posteriors(o), c->d_tcls, c->N, post->size, o->Lp, dst, per_call, c->d_rowstat);
+        launch_mcc_eval(c->stream, posteriors(o), ax->tcls, ax->N, post->size, o->Lp, dst, per_call, c->d_rowstat);
     else
-        launch_post_eval(c->stream, post_kind(post), posteriors(o), post->targets, c->d_pat, c->N, o->size, o->Lp, c->d_rowstat, dst, per_call);
+        launch_post_eval(c->stream, post_kind(post), posteriors(o), post_targets(post), ax->pat, ax->N, o->size, o->Lp, c->d_rowstat, dst, per_call);
     c->rowstat_of = nullptr;           // the row statistics now are this evaluation's terms
 }
 // {error, #correct as int bits} at `src` to the host; reset: the running sums are cleared behind the read
@@ -2540,6 +2700,7 @@ int cn_loss_accumulate(cn_layer *post)
         if (!post->post) throw cn_error(CN_ERR_BAD_ARG, "cn_loss_accumulate: not a post output layer");
         require_loaded(c);
         cn_layer *o = post->prev;
+        require_axis(post, "cn_loss_accumulate");
         flush_loss(c);
         // Training: the backward pass of the output layer follows; its launch (softmax_mcc_bwd_kernel) takes the sum along in one
         // extra workgroup, so nothing is enqueued here.  Whoever needs the sums or overwrites the rows first flushes (flush_loss).
@@ -2679,14 +2840,16 @@ int cn_layer_write_output_errors(cn_layer *layer, const float *host, size_t coun
         enter(c);
         require_loaded(c);
         if (!layer->err) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_write_output_errors: layer has no outputErrors");
-        if (count != (size_t)c->Next * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_layer_write_output_errors: count != T*PS*size");
+        require_axis(layer, "cn_layer_write_output_errors");
+        const TimeAxis *ax = layer->ax;
+        if (count != (size_t)ax->Next * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_layer_write_output_errors: count != T*PS*size");
         const Scratch scratch(count * sizeof(float));
         float *tmp = scratch.get();
         HIP_CHECK(hipMemcpyAsync(tmp, host, count * sizeof(float), hipMemcpyHostToDevice, c->stream));
         layer->mcc_pending = false;
         layer->err_in_delta = false;
-        HIP_CHECK(hipMemsetAsync(layer->err, 0, (size_t)c->N * layer->Lp * sizeof(float), c->stream));
-        launch_pad_f32(c->stream, tmp, c->Next, layer->err, unit_map(layer), c->PS, c->PSp);
+        HIP_CHECK(hipMemsetAsync(layer->err, 0, (size_t)ax->N * layer->Lp * sizeof(float), c->stream));
+        launch_pad_f32(c->stream, tmp, ax->Next, layer->err, unit_map(layer), c->PS, c->PSp);
         HIP_CHECK(hipStreamSynchronize(c->stream));
     });
 }
@@ -2716,7 +2879,8 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
             return;
         }
         require_loaded(c);
-        const int N = c->Next;                 // host layout: T*PS patterns
+        require_axis(layer, "cn_layer_read");
+        const int N = layer->ax->Next;         // host layout: T*PS patterns of the layer's own time axis
         int width = layer->size;
         if (which >= CN_BUF_LSTM_CELL_STATES) {
             if (!layer->lstm) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: not an LSTM layer");
@@ -2736,7 +2900,7 @@ int cn_layer_read(cn_layer *layer, cn_buffer which, int dir, float *host, size_t
         if (which == CN_BUF_OUTPUT_ERRORS) {
             if (!layer->err) throw cn_error(CN_ERR_BAD_ARG, "cn_layer_read: layer has no outputErrors");
             if (layer->mcc_pending) {     // the deferred multiclass error injection becomes visible here
-                launch_mcc_backward(c->stream, posteriors(layer), c->d_tcls, c->N, layer->size, layer->Lp, layer->err);
+                launch_mcc_backward(c->stream, posteriors(layer), layer->ax->tcls, layer->ax->N, layer->size, layer->Lp, layer->err);
                 layer->mcc_pending = false;
             }
             const bool in_delta = !layer->lstm && layer->err_in_delta;      // fused softmax backward in bf16 mode: only the operand copy exists
@@ -3195,7 +3359,8 @@ int cn_dbg_residual_branch(cn_layer *layer, float *host, size_t count)
         enter(c);
         require_loaded(c);
         if (!layer->summed) throw cn_error(CN_ERR_STATE, "cn_dbg_residual_branch: the layer's last forward pass did not sum");
-        const int N = c->Next;
+        require_axis(layer, "cn_dbg_residual_branch");
+        const int N = layer->ax->Next;
         if (count != (size_t)N * layer->size) throw cn_error(CN_ERR_SHAPE, "cn_dbg_residual_branch: count != T*PS*size");
         read_rows(c, layer->out_op, !c->f32, unit_map(layer), N, c->PS, c->PSp, host);
     });
@@ -3663,6 +3828,57 @@ int cn_dbg_prefetch_hits(cn_ctx *ctx, int *hits)
     if (!ctx || !hits) { g_last_error = "cn_dbg_prefetch_hits: NULL argument"; return CN_ERR_BAD_ARG; }
     *hits = ctx->pf.hits;
     return CN_OK;
+}
+
+int cn_dbg_layer_axis(cn_layer *layer, char *pat, int *tcls, int *len, size_t rows, int *PSp)
+{
+    if (!layer) { g_last_error = "cn_dbg_layer_axis: layer is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        require_loaded(c);
+        join_side(c);
+        require_axis(layer, "cn_dbg_layer_axis");
+        const TimeAxis *ax = layer->ax;
+        if (PSp) *PSp = c->PSp;
+        if ((pat || tcls) && rows != (size_t)ax->N) throw cn_error(CN_ERR_SHAPE, "cn_dbg_layer_axis: rows != T * padded parallel sequences");
+        // (refused BEFORE the length pass: without a context layer the table it would write does not exist)
+        if (len && !ax->len) throw cn_error(CN_ERR_STATE, "cn_dbg_layer_axis: the context has no context layer, so no slot lengths");
+        if (len && !ax->owner) context_lengths(c);
+        if (pat) HIP_CHECK(hipMemcpyAsync(pat, ax->pat, rows, hipMemcpyDeviceToHost, c->stream));
+        if (tcls) HIP_CHECK(hipMemcpyAsync(tcls, ax->tcls, rows * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (len) HIP_CHECK(hipMemcpyAsync(len, ax->len, (size_t)c->PSp * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int cn_dbg_layer_pad_bits(cn_layer *layer, long long *nonzero)
+{
+    if (!layer || !nonzero) { g_last_error = "cn_dbg_layer_pad_bits: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = layer->ctx;
+        enter(c);
+        require_loaded(c);
+        join_side(c);
+        require_axis(layer, "cn_dbg_layer_pad_bits");
+        if (!layer->out_op) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_layer_pad_bits: layer has no outputs");
+        const UnitMap m = unit_map(layer);
+        const size_t rows = (size_t)layer->ax->N, e = c->esz();
+        std::vector<unsigned char> h(rows * m.Lp * e);
+        HIP_CHECK(hipMemcpyAsync(h.data(), follower_operand(layer), h.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        long long n = 0;
+        for (size_t r = 0; r < rows; ++r) {
+            const bool pad_slot = (int)(r % c->PSp) >= c->PS;
+            for (int col = 0; col < m.Lp; ++col) {
+                if (!pad_slot && m.unit(col) >= 0) continue;
+                bool any = false;
+                for (size_t b = 0; b < e; ++b) any = any || h[(r * m.Lp + col) * e + b] != 0;
+                n += any;
+            }
+        }
+        *nonzero = n;
+    });
 }
 
 int cn_dbg_row_map_counts(cn_ctx *ctx, int out[3])

@@ -361,6 +361,22 @@ void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int 
 void launch_context_fwd(hipStream_t s, bool f32, const ContextArgs &a, const int *len, const void *x, void *out);
 // dx[T * PSp][xLp] (fp32), every row and column written: the fold of e[T * PSp][Lp] (fp32) in the stated order, zeros elsewhere
 void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, const float *e, float *dx);
+// ---- strided context layers (include/currennt_hip.h, section Strided context layers; cn_context_stride.hip) ----
+// The geometry of one forward pass of one strided context layer: it reads Tin steps of its predecessor's time axis and writes
+// Tout = ceil(Tin / S) steps of its own; the other members as in ContextArgs.  len[] below is always the PARENT axis's (len_s);
+// the kernels form n_s = ceil(len_s / S) from it.
+struct StrideArgs {
+    int Tin, Tout, PSp, B, left, dil, Lp, S; UnitMap prev;
+};
+// The layer's own axis from the parent's, every row of Tout * PSp written: nlen[s] = n_s, the derived pattern types npat (FIRST /
+// NORMAL / LAST / NONE) and the classes ntcls[j][s] = tcls[S * j][s] for j < n_s, -1 elsewhere
+void launch_stride_axis(hipStream_t s, int S, int Tout, int PSp, const int *len, const int *tcls, int *nlen, char *npat, int *ntcls);
+// tgt[Tout * PSp][W] = src[rate * j][s][..] for j < nlen[s], zero rows elsewhere (src at the base rate, rate = the product of the strides)
+void launch_stride_targets(hipStream_t s, int rate, int Tout, int PSp, int W, const int *nlen, const float *src, float *tgt);
+// out[Tout * PSp][Lp] (op) gathered from x[Tin * PSp][xLp] (op), bits copied; rows j >= n_s and pad columns are written as zeros
+void launch_stride_fwd(hipStream_t s, bool f32, const StrideArgs &a, const int *len, const void *x, void *out);
+// dx[Tin * PSp][xLp] (fp32), every row and column written: the fold of e[Tout * PSp][Lp] (fp32) in the stated order, zeros elsewhere
+void launch_stride_bwd(hipStream_t s, const StrideArgs &a, const int *len, const float *e, float *dx);
 // delta = act'(y) * err (in place on err, all N slots: FeedForwardLayer.cu:72-79), op copy for the GEMMs
 void launch_ff_delta(hipStream_t s, bool f32, int act, const float *y, float *err, void *delta_op, int N, int L, int Lp);
 // column sums of delta over the N slots (FeedForwardLayer.cu:82-102): colsum[j] += sum_n err[n][j]

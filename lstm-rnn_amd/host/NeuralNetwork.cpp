@@ -11,6 +11,18 @@ NeuralNetwork::NeuralNetwork(const json::Value &jsonDoc, int parallelSequences, 
                              cn_precision precision, int device, const WeightsInit *weightsInit)
     : m_ctx(0)
 {
+    // the members of the context layers are held to their ranges before a device is touched
+    if (jsonDoc.isObject() && jsonDoc.hasMember("layers") && jsonDoc["layers"].isArray()) {
+        const json::Value &layersSection = jsonDoc["layers"];
+        for (size_t i = 0; i < layersSection.size(); ++i) {
+            const json::Value &layerChild = layersSection[i];
+            if (!layerChild.isObject() || !layerChild.hasMember("type") || !layerChild.hasMember("name")) continue;      // (refused below)
+            if (!layerChild["type"].isString() || layerChild["type"].getString() != "context" || !layerChild["name"].isString()) continue;
+            int values[4];
+            try { layers::Layer::contextMemberValues(layerChild, layerChild["name"].getString(), values); }
+            catch (const std::exception &e) { throw std::runtime_error(std::string("Invalid network file: Could not create layer: ") + e.what()); }
+        }
+    }
     hipCheck(cn_ctx_create(device, precision, 0, &m_ctx));
     try {
         try {

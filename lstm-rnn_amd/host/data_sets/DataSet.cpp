@@ -23,6 +23,15 @@ std::vector<int> DataSet::truncatedPieces(int length, int trunc)
     return pieces;
 }
 
+int DataSet::totalNetworkTimesteps(int stride) const
+{
+    if (stride <= 1) return m_totalNetworkTimesteps;
+    const int K = m_augment.frameSkip;
+    long total = 0;
+    for (size_t i = 0; i < m_sequences.size(); ++i) total += ((m_sequences[i].length + K - 1) / K + stride - 1) / stride;
+    return (int)total;
+}
+
 DataSet::~DataSet()
 {
     if (m_prefetch.valid()) m_prefetch.wait();

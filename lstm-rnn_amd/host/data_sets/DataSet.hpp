@@ -88,6 +88,8 @@ public:
     // the frames the network sees: the sum of ceil(length / frameSkip) over the sequences, the pieces of --truncate_seq each on
     // its own (= totalTimesteps() at a skip of 1).  What a per-frame error rate is taken over.
     int totalNetworkTimesteps() const { return m_totalNetworkTimesteps; }
+    // ... behind context layers whose strides multiply to `stride`: the sum of ceil(ceil(length / frameSkip) / stride)
+    int totalNetworkTimesteps(int stride) const;
     int minSeqLength() const { return m_minSeqLength; }
     int maxSeqLength() const { return m_maxSeqLength; }
     int inputPatternSize() const { return m_inputPatternSize; }                        // per frame, before context splicing

@@ -17,7 +17,7 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
     , m_name(layerChild.hasMember("name") ? layerChild["name"].getString() : "")
     , m_size(layerChild.hasMember("size") ? layerChild["size"].getInt() : 0)
     , m_parallelSequences(parallelSequences), m_maxSeqLength(maxSeqLength)
-    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0), m_residual(false), m_layerNorm(false), m_layerNormEps(1e-5f)
+    , m_curMaxSeqLength(0), m_curMinSeqLength(0), m_curNumSeqs(0), m_rate(precedingLayer ? precedingLayer->rate() : 1), m_axisOwner(precedingLayer ? precedingLayer->m_axisOwner : 0), m_residual(false), m_layerNorm(false), m_layerNormEps(1e-5f)
 {
     if (!layerChild.hasMember("name")) throw std::runtime_error("Missing value 'name' in layer description");       // Layer.cpp:52-53
     if (m_name.empty()) throw std::runtime_error("Empty layer name in layer description");                           // :54-55
@@ -64,9 +64,13 @@ Layer::Layer(cn_ctx *ctx, const json::Value &layerChild, cn_layer_kind kind, Lay
                                      std::to_string(precedingLayer->size()) + " is below 2");
     }
     if (kind == CN_LAYER_CONTEXT) {        // (a kind with members of its own and an entry point of its own)
-        int left, right, dilation;
-        contextMembers(layerChild, m_name, m_size, precedingLayer, &left, &right, &dilation);
-        hipCheck(cn_layer_create_context(ctx, precedingLayer->handle(), left, right, dilation, &m_handle), ctx);
+        int left, right, dilation, stride;
+        contextMembers(layerChild, m_name, m_size, precedingLayer, &left, &right, &dilation, &stride);
+        if (stride == 1) hipCheck(cn_layer_create_context(ctx, precedingLayer->handle(), left, right, dilation, &m_handle), ctx);
+        else hipCheck(cn_layer_create_context_strided(ctx, precedingLayer->handle(), left, right, dilation, stride, &m_handle), ctx);
+        m_rate *= stride;
+        if (stride > 1) m_axisOwner = this;
+        m_maxSeqLength = (m_maxSeqLength + stride - 1) / stride;
     } else {
         hipCheck(cn_layer_create(ctx, kind, precedingLayer ? precedingLayer->handle() : 0, m_size, bias,
                                  precedingLayer ? 0 : parallelSequences, precedingLayer ? 0 : maxSeqLength, &m_handle), ctx);
@@ -91,7 +95,17 @@ void Layer::loadSequences(const data_sets::DataSetFraction &fraction)
     m_curMaxSeqLength = fraction.networkMaxSeqLength();     // (a source-rate fraction: what the device derives from it)
     m_curMinSeqLength = fraction.networkMinSeqLength();
     m_curNumSeqs = fraction.numSequences();
-    m_patTypes = fraction.networkPatTypes();
+    if (m_rate == 1) { m_patTypes = fraction.networkPatTypes(); return; }
+    // behind a strided context layer: the axis the device derives (section Strided context layers)
+    m_curMaxSeqLength = (m_curMaxSeqLength + m_rate - 1) / m_rate;
+    m_curMinSeqLength = (m_curMinSeqLength + m_rate - 1) / m_rate;
+    if (m_axisOwner != this) return;      // (the axis's owner, loaded in front of this layer, holds the pattern types)
+    m_patTypes.assign((size_t)m_curMaxSeqLength * m_parallelSequences, PATTYPE_NONE);
+    for (int i = 0; i < fraction.numSequences(); ++i) {
+        const int n = (fraction.seqInfo(i).length + m_rate - 1) / m_rate;
+        for (int j = 0; j < n; ++j)
+            m_patTypes[(size_t)j * m_parallelSequences + i] = j == 0 ? PATTYPE_FIRST : (j == n - 1 ? PATTYPE_LAST : PATTYPE_NORMAL);
+    }
 }
 void Layer::computeForwardPass() { hipCheck(cn_layer_forward(m_handle), m_ctx); }
 void Layer::computeBackwardPass() { hipCheck(cn_layer_backward(m_handle), m_ctx); }
@@ -110,30 +124,37 @@ void Layer::exportLayer(json::Value *layersArray) const
 // The refusals are the library's (include/currennt_hip.h, section Context layers), said here with the layer's name; the size
 // check uses the reference's text for a size that does not fit the preceding layer (PostOutputLayer.cpp:58-59).
 void Layer::contextMembers(const json::Value &layerChild, const std::string &name, int size, const Layer *precedingLayer,
-                           int *left, int *right, int *dilation)
+                           int *left, int *right, int *dilation, int *stride)
 {
-    struct Member { const char *key; int dflt, lo, hi; int *out; };
-    const Member members[3] = {{"left", 0, 0, 32, left}, {"right", 0, 0, 32, right}, {"dilation", 1, 1, 16, dilation}};
-    for (int k = 0; k < 3; ++k) {
-        const Member &m = members[k];
-        *m.out = m.dflt;
-        if (!layerChild.hasMember(m.key)) continue;
-        const json::Value &v = layerChild[m.key];
-        if (!v.isNumber() || v.getDouble() != std::floor(v.getDouble()) || v.getDouble() < m.lo || v.getDouble() > m.hi)
-            throw std::runtime_error(std::string("Invalid value '") + m.key + "' in layer '" + name + "': an integer in " + std::to_string(m.lo) +
-                                     ".." + std::to_string(m.hi) + " expected");
-        *m.out = v.getInt();
-    }
+    int values[4];
+    contextMemberValues(layerChild, name, values);
+    *left = values[0]; *right = values[1]; *dilation = values[2]; *stride = values[3];
     const int blocks = *left + *right + 1;
     if (size != blocks * precedingLayer->size())
         throw std::runtime_error("Size mismatch: " + std::to_string(size) + " vs. " + std::to_string(blocks * precedingLayer->size()) + " in layer '" + name +
                                  "' (" + std::to_string(blocks) + " frames of the preceding layer's " + std::to_string(precedingLayer->size()) + " units)");
 }
+void Layer::contextMemberValues(const json::Value &layerChild, const std::string &name, int values[4])
+{
+    struct Member { const char *key; int dflt, lo, hi; };
+    const Member members[4] = {{"left", 0, 0, 32}, {"right", 0, 0, 32}, {"dilation", 1, 1, 16}, {"stride", 1, 1, 8}};
+    for (int k = 0; k < 4; ++k) {
+        const Member &m = members[k];
+        values[k] = m.dflt;
+        if (!layerChild.hasMember(m.key)) continue;
+        const json::Value &v = layerChild[m.key];
+        if (!v.isNumber() || v.getDouble() != std::floor(v.getDouble()) || v.getDouble() < m.lo || v.getDouble() > m.hi)
+            throw std::runtime_error(std::string("Invalid value '") + m.key + "' in layer '" + name + "': an integer in " + std::to_string(m.lo) +
+                                     ".." + std::to_string(m.hi) + " expected");
+        values[k] = v.getInt();
+    }
+}
 ContextLayer::ContextLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer)
     : Layer(ctx, layerChild, CN_LAYER_CONTEXT, &precedingLayer, precedingLayer.parallelSequences(), precedingLayer.maxSeqLength(), 0.f)
-    , m_left(0), m_right(0), m_dilation(1)
+    , m_left(0), m_right(0), m_dilation(1), m_stride(1)
 {
     hipCheck(cn_layer_context(m_handle, &m_left, &m_right, &m_dilation), ctx);
+    hipCheck(cn_layer_context_stride(m_handle, &m_stride), ctx);
 }
 const std::string &ContextLayer::type() const { static const std::string s("context"); return s; }
 void ContextLayer::exportLayer(json::Value *layersArray) const
@@ -141,6 +162,7 @@ void ContextLayer::exportLayer(json::Value *layersArray) const
     Layer::exportLayer(layersArray);
     json::Value &o = (*layersArray)[layersArray->size() - 1];
     o.addMember("left", m_left); o.addMember("right", m_right); o.addMember("dilation", m_dilation);
+    if (m_stride != 1) o.addMember("stride", m_stride);      // (files of nets without a stride stay as they were)
 }
 
 // ---- InputLayer -----------------------------------------------------------------------------

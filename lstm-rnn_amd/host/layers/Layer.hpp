@@ -28,7 +28,11 @@ public:
     int curMaxSeqLength() const { return m_curMaxSeqLength; }
     int curMinSeqLength() const { return m_curMinSeqLength; }
     int curNumSeqs() const { return m_curNumSeqs; }
-    const Hip::pattype_vector &patTypes() const { return m_patTypes; }
+    // the product of the strides of the context layers in front of (and of) this layer: its lengths, pattern types and read-backs
+    // go by ceil(network-rate length / rate) (include/currennt_hip.h, section Strided context layers)
+    int rate() const { return m_rate; }
+    // (behind a strided context layer: that layer's vector, one per time axis)
+    const Hip::pattype_vector &patTypes() const { return m_axisOwner && m_axisOwner != this ? m_axisOwner->m_patTypes : m_patTypes; }
     virtual const std::string &type() const = 0;
     virtual bool isTrainable() const { return false; }
     virtual bool isPostOutput() const { return false; }
@@ -48,17 +52,24 @@ public:
     cn_layer *handle() const { return m_handle; }
     cn_ctx *context() const { return m_ctx; }
 
+    // "left", "right", "dilation" and "stride" of a "context" layer description, each absent or an integer in its range; a value
+    // that is not is refused with a message that names the layer.  Needs no device: a network file is held to it before one is
+    // touched.
+    static void contextMemberValues(const json::Value &layerChild, const std::string &name, int values[4]);
+
 protected:
     Hip::real_vector read(cn_buffer which, int dir, size_t count) const;
     // the members of a "context" layer description, checked: the constructor below creates such a layer from them
     static void contextMembers(const json::Value &layerChild, const std::string &name, int size, const Layer *precedingLayer,
-                               int *left, int *right, int *dilation);
+                               int *left, int *right, int *dilation, int *stride);
 
     cn_ctx *m_ctx;
     cn_layer *m_handle;
     std::string m_name;
     int m_size;
     int m_parallelSequences, m_maxSeqLength, m_curMaxSeqLength, m_curMinSeqLength, m_curNumSeqs;
+    int m_rate;
+    const Layer *m_axisOwner;         // the nearest strided context layer in front of (or this) layer: it holds the axis's pattern types; 0: none
     Hip::pattype_vector m_patTypes;
     bool m_residual;
     bool m_layerNorm;
@@ -74,7 +85,8 @@ public:
 
 // A hidden layer without weights that splices its preceding layer's neighbouring frames (include/currennt_hip.h, section Context
 // layers; no counterpart in the reference): JSON "left" / "right" (default 0) frames at steps of "dilation" (default 1), and a
-// "size" of (left + right + 1) x the preceding layer's size
+// "size" of (left + right + 1) x the preceding layer's size; "stride" (default 1) keeps every stride-th frame (section Strided
+// context layers)
 class ContextLayer : public Layer {
 public:
     ContextLayer(cn_ctx *ctx, const json::Value &layerChild, Layer &precedingLayer);
@@ -82,9 +94,10 @@ public:
     int left() const { return m_left; }
     int right() const { return m_right; }
     int dilation() const { return m_dilation; }
+    int stride() const { return m_stride; }
     void exportLayer(json::Value *layersArray) const;
 private:
-    int m_left, m_right, m_dilation;
+    int m_left, m_right, m_dilation, m_stride;
 };
 
 class TrainableLayer : public Layer {                     // layers/TrainableLayer.{hpp,cu}

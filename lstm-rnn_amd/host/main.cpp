@@ -96,7 +96,7 @@ void printLayers(const NeuralNetwork &nn)                                       
         const layers::TrainableLayer *tl = dynamic_cast<const layers::TrainableLayer *>(nn.layers()[i].get());
         if (tl) { printf(", bias: %.1lf, weights: %d", (double)tl->bias(), tl->weightCount()); weights += tl->weightCount(); }
         if (const layers::ContextLayer *cl = dynamic_cast<const layers::ContextLayer *>(nn.layers()[i].get()))
-            printf(", context -%d..+%d x%d", cl->left(), cl->right(), cl->dilation());
+            printf(cl->stride() != 1 ? ", context -%d..+%d x%d /%d" : ", context -%d..+%d x%d", cl->left(), cl->right(), cl->dilation(), cl->stride());
         if (nn.layers()[i]->residual()) printf(", residual");
         if (nn.layers()[i]->layerNorm()) printf(", layer_norm");
         printf("]\n");
@@ -218,7 +218,7 @@ void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::Data
             } else if (!outputs[psIdx].empty()) {                                                // FORMAT_HTK, main.cpp:432-480
                 std::ofstream file((dir + "/" + base + ".htk").c_str(), std::ofstream::out | std::ios::binary);
                 unsigned tmp = (unsigned)outputs[psIdx].size(); swap32(&tmp); file.write((const char *)&tmp, 4);
-                tmp = (unsigned)(config.featurePeriod() * config.inputFrameSkip() * 1e4); swap32(&tmp); file.write((const char *)&tmp, 4);     // (a row every K source frames)
+                tmp = (unsigned)(config.featurePeriod() * config.inputFrameSkip() * nn.outputLayer().rate() * 1e4); swap32(&tmp); file.write((const char *)&tmp, 4);     // (a row every K x total stride source frames)
                 unsigned short tmp2 = (unsigned short)(outputs[psIdx][0].size() * sizeof(float)); swap16(&tmp2); file.write((const char *)&tmp2, 2);
                 tmp2 = (unsigned short)config.outputFeatureKind(); swap16(&tmp2); file.write((const char *)&tmp2, 2);
                 for (size_t t = 0; t < outputs[psIdx].size(); ++t)

@@ -74,7 +74,10 @@ int ctcLabelErrors(const Hip::real_vector &out, int PS, int C, int slot, int len
 real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates, real_t *classError)
 {
     real_t error = 0;
-    *classError = (real_t)ds.totalNetworkTimesteps();      // (the frames the network classifies: --input_frame_skip)
+    // the frames the output layer classifies: --input_frame_skip, and the strides of the context layers in front of it
+    const int outRate = m_neuralNetwork.outputLayer().rate();
+    const int classified = ds.totalNetworkTimesteps(outRate);
+    *classError = (real_t)classified;
     const std::vector<std::shared_ptr<layers::Layer> > &ls = m_neuralNetwork.layers();
     const bool classification = dynamic_cast<layers::MulticlassClassificationLayer *>(&m_neuralNetwork.postOutputLayer()) != 0 ||
                                 dynamic_cast<layers::BinaryClassificationLayer *>(&m_neuralNetwork.postOutputLayer()) != 0;   // Optimizer.cu:52-55
@@ -125,7 +128,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
             const Hip::real_vector out = m_neuralNetwork.outputLayer().outputs();
             for (int i = 0; i < frac.numSequences(); ++i) {
                 labelErrors += ctcLabelErrors(out, m_neuralNetwork.outputLayer().parallelSequences(), m_neuralNetwork.outputLayer().size(), i,
-                                              frac.seqInfo(i).length, frac.labelSeqs()[i]);
+                                              (frac.seqInfo(i).length + outRate - 1) / outRate, frac.labelSeqs()[i]);
                 labelCount += (long)frac.labelSeqs()[i].size();
             }
         }
@@ -191,7 +194,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         if (classification) *classError -= (real_t)correct;
     }
     error /= ds.totalSequences();                                           // :99-101
-    *classError /= (real_t)ds.totalNetworkTimesteps();
+    *classError /= (real_t)classified;
     if (ctc) *classError = labelCount ? (real_t)labelErrors / (real_t)labelCount : 0;
     return error;
 }

@@ -47,17 +47,25 @@ class Layer:
             if prev is None:
                 raise RuntimeError("The first layer is not an input layer")
             self.left, self.right, self.dilation = self._int_member(desc, "left", 0), self._int_member(desc, "right", 0), self._int_member(desc, "dilation", 1)
+            # "stride" (default 1): the layer keeps every stride-th frame and starts a new time axis (section Strided context layers)
+            self.stride_member = self._int_member(desc, "stride", 1)
             blocks = self.left + self.right + 1
             if blocks >= 1 and self.size != blocks * prev.size:
                 raise RuntimeError("Size mismatch: %d vs. %d in layer '%s' (%d frames of the preceding layer's %d units)"
                                    % (self.size, blocks * prev.size, self.name, blocks, prev.size))
-            B.check(L.cn_layer_create_context(net.ctx, prev.handle, self.left, self.right, self.dilation, C.byref(h)), net.ctx)
+            if "stride" in desc:
+                B.check(L.cn_layer_create_context_strided(net.ctx, prev.handle, self.left, self.right, self.dilation, self.stride_member,
+                                                          C.byref(h)), net.ctx)
+            else:
+                B.check(L.cn_layer_create_context(net.ctx, prev.handle, self.left, self.right, self.dilation, C.byref(h)), net.ctx)
         else:
             B.check(L.cn_layer_create(net.ctx, B.LAYER_KINDS[self.type], prev.handle if prev else None,
                                       self.size, self.bias,
                                       net.parallel_sequences if prev is None else 0,
                                       net.max_seq_length if prev is None else 0, C.byref(h)), net.ctx)
         self.handle = h
+        # the product of the strides in front of (and of) this layer: its read-backs are sized by ceil(T / rate)
+        self.rate = (prev.rate if prev is not None else 1) * (self.stride_member if self.type == "context" else 1)
         self.weight_count = L.cn_layer_weight_count(h) if self.trainable else 0
         if self.trainable and self.learning_rate >= 0.0:       # cn_sgd_update_all honours it too (SteepestDescentOptimizer.cu:78-80)
             B.check(L.cn_layer_set_learning_rate(h, self.learning_rate), net.ctx)
@@ -118,6 +126,35 @@ class Layer:
         B.check(self.net.lib.cn_layer_context(self.handle, C.byref(l), C.byref(r), C.byref(d)), self.net.ctx)
         return l.value, r.value, d.value
 
+    def stride(self):
+        """cn_layer_context_stride: the stride of a context layer (1: a plain one)."""
+        s = C.c_int()
+        B.check(self.net.lib.cn_layer_context_stride(self.handle, C.byref(s)), self.net.ctx)
+        return s.value
+
+    def time(self):
+        """cn_layer_time: (T, Tmin, rate) -- the steps of the current fraction as this layer sees them and the product of the
+        strides in front of it."""
+        t, tmin, r = C.c_int(), C.c_int(), C.c_int()
+        B.check(self.net.lib.cn_layer_time(self.handle, C.byref(t), C.byref(tmin), C.byref(r)), self.net.ctx)
+        return t.value, tmin.value, r.value
+
+    @property
+    def T(self):
+        """Time steps of the fraction loaded last in this layer's own time axis."""
+        return -(-self.net.T // self.rate)
+
+    @property
+    def N(self):
+        return self.T * self.net.PS
+
+    def pad_bits(self):
+        """cn_dbg_layer_pad_bits: elements with a non-zero bit in the pad columns and pad slots of the rows this layer's followers
+        read (what outputs() cannot show)."""
+        n = C.c_longlong(-1)
+        B.check(self.net.lib.cn_dbg_layer_pad_bits(self.handle, C.byref(n)), self.net.ctx)
+        return n.value
+
     def forward(self):
         """cn_layer_forward of this layer alone."""
         B.check(self.net.lib.cn_layer_forward(self.handle), self.net.ctx)
@@ -134,10 +171,10 @@ class Layer:
         return out
 
     def outputs(self):
-        return self._read("outputs", self.net.N * self.size).reshape(self.net.T, self.net.PS, self.size)
+        return self._read("outputs", self.N * self.size).reshape(self.T, self.net.PS, self.size)
 
     def output_errors(self):
-        return self._read("outputErrors", self.net.N * self.size).reshape(self.net.T, self.net.PS, self.size)
+        return self._read("outputErrors", self.N * self.size).reshape(self.T, self.net.PS, self.size)
 
     def weights(self):
         return self._read("weights", self.weight_count)
@@ -188,10 +225,10 @@ class Layer:
     def dropout_input(self):
         """The masked operand copy this layer's input products read in its last forward pass, [T][PS][size of the preceding
         layer] (cn_dbg_dropout_input); CN_ERR_STATE when that pass did not drop."""
-        n = self.net.N * self.prev.size
+        n = self.N * self.prev.size
         out = np.empty(n, np.float32)
         B.check(self.net.lib.cn_dbg_dropout_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
-        return out.reshape(self.net.T, self.net.PS, self.prev.size)
+        return out.reshape(self.T, self.net.PS, self.prev.size)
 
     def set_residual(self, enable=True):
         """cn_layer_set_residual: from this layer's next forward pass on, its followers and outputs() see its own output plus
@@ -202,10 +239,10 @@ class Layer:
     def residual_branch(self):
         """This layer's own output in its last forward pass, [T][PS][size] (cn_dbg_residual_branch): outputs() minus the skip
         path; CN_ERR_STATE when that pass did not sum."""
-        n = self.net.N * self.size
+        n = self.N * self.size
         out = np.empty(n, np.float32)
         B.check(self.net.lib.cn_dbg_residual_branch(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
-        return out.reshape(self.net.T, self.net.PS, self.size)
+        return out.reshape(self.T, self.net.PS, self.size)
 
     def set_layer_norm(self, enable=True, eps=1e-5):
         """cn_layer_set_layer_norm: from this layer's next forward pass on, its input products read the normalised copy of what
@@ -216,10 +253,10 @@ class Layer:
     def normalized_input(self):
         """The normalised copy of this layer's input in its last forward pass, [T][PS][size of the preceding layer]
         (cn_dbg_layer_norm_input); CN_ERR_STATE when that pass did not normalise."""
-        n = self.net.N * self.prev.size
+        n = self.N * self.prev.size
         out = np.empty(n, np.float32)
         B.check(self.net.lib.cn_dbg_layer_norm_input(self.handle, out.ctypes.data_as(C.c_void_p), n), self.net.ctx)
-        return out.reshape(self.net.T, self.net.PS, self.prev.size)
+        return out.reshape(self.T, self.net.PS, self.prev.size)
 
     def noisy_weights(self):
         """The weights this layer's last backward pass read, flat reference layout (cn_dbg_noisy_weights): w + noise as the noisy
@@ -240,7 +277,7 @@ class Layer:
 
     def internal(self, which, direction=0):
         """LSTM per-direction internal vector by its reference name (LstmLayer.hpp:88-100)."""
-        return self._read(which, self.net.N * self.H, direction).reshape(self.net.T, self.net.PS, self.H)
+        return self._read(which, self.N * self.H, direction).reshape(self.T, self.net.PS, self.H)
 
     def set_weights(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
@@ -270,6 +307,7 @@ class NeuralNetwork:
             self.set_option(name, value)
         self.layers = []
         self.T = self.Tmin = self.N = 0
+        self._lens = self._lens_from = None
         self.frame_skip = 1                               # set_input_splice: loads take source-rate fractions, read-backs go by ceil(T / k)
         try:
             names = set()
@@ -376,15 +414,18 @@ class NeuralNetwork:
         f, keep = self._host_descriptor(frac)
         # (the library copies the host arrays into pinned staging memory before it returns: nothing to wait for)
         B.check(self.lib.cn_fraction_load(self.ctx, self.layers[0].handle, self.layers[-1].handle, C.byref(f)), self.ctx)
-        self._set_current(f)
+        self._set_current(f, (frac["patTypes"], int(frac["T"]), self.frame_skip))
         if self.layers[-1].type == "ctc" and frac.get("labels") is not None:
             self.set_label_sequences(frac["labels"])
 
-    def _set_current(self, f):
+    def _set_current(self, f, lens=None):
         """The lengths of the fraction just loaded as the layers see them: f's, or ceil(f's / frame_skip) under set_input_splice."""
         k = self.frame_skip
         self.T, self.Tmin = -(-f.max_seq_length // k), -(-f.min_seq_length // k)
         self.N = self.T * self.PS
+        # lengths(): counted on demand, from the host's pattern types (kept by reference with their T) or, after a resident load,
+        # from the device's
+        self._lens, self._lens_from = None, lens
 
     def set_label_sequences(self, labels):
         """cn_layer_set_label_sequences: one int array of labels per sequence of the fraction loaded last (a ctc net)."""
@@ -709,8 +750,33 @@ class NeuralNetwork:
         B.check(self.lib.cn_ctx_take_accumulated(self.ctx), self.ctx)
 
     def outputs(self):
-        """Output layer activations [T][PS][C] (NeuralNetwork.cpp:237-262 de-interleaves per sequence)."""
+        """Output layer activations [T][PS][C] (NeuralNetwork.cpp:237-262 de-interleaves per sequence); T of the output layer's
+        own time axis."""
         return self.output_layer().outputs()
+
+    def lengths(self, layer=None):
+        """The real frames per sequence slot of the fraction loaded last as `layer` (default: the input layer) sees them:
+        n_s = ceil(len_s / rate) (include/currennt_hip.h, section Strided context layers)."""
+        lay = self.layers[0] if layer is None else (self.layer(layer) if isinstance(layer, str) else layer)
+        if self._lens is None and self._lens_from is not None:
+            pat, T, k = self._lens_from
+            self._lens = -(-(np.asarray(pat).reshape(T, -1) != 0).sum(axis=0).astype(np.int64) // k)
+        if self._lens is None:
+            self._lens = (self.axis(self.layers[0])[0][:, :self.PS] != 0).sum(axis=0).astype(np.int64)
+        return -(-self._lens // lay.rate)
+
+    def axis(self, layer):
+        """(patTypes [T'][PSp], classes [T'][PSp], lengths [PSp]) of the time axis `layer` runs on, as the device holds them
+        (cn_dbg_layer_axis; pad slots included)."""
+        lay = self.layer(layer) if isinstance(layer, str) else layer
+        psp = C.c_int()
+        B.check(self.lib.cn_dbg_layer_axis(lay.handle, None, None, None, 0, C.byref(psp)), self.ctx)
+        rows = lay.T * psp.value
+        pat, cls, ln = np.empty(rows, np.int8), np.empty(rows, np.int32), np.empty(psp.value, np.int32)
+        has_len = any(l.type == "context" for l in self.layers)
+        B.check(self.lib.cn_dbg_layer_axis(lay.handle, pat.ctypes.data_as(C.c_void_p), cls.ctypes.data_as(C.c_void_p),
+                                           ln.ctypes.data_as(C.c_void_p) if has_len else None, rows, None), self.ctx)
+        return pat.reshape(lay.T, psp.value), cls.reshape(lay.T, psp.value), (ln if has_len else None)
 
     def torch_stream(self, torch):
         """The context's HIP stream as a torch stream.  Collectives and tensor ops that must be ordered against the
