@@ -926,6 +926,41 @@ int  cn_ctx_get_trust_bounds(const cn_ctx *ctx, float *min_ratio, float *max_rat
  * before the first.  Any pointer may be NULL.  A layer without weights: CN_ERR_BAD_ARG.                              [sync] */
 int  cn_layer_trust_ratio(cn_layer *layer, float *ratio, float *weight_norm, float *update_norm);
 
+/* ---- CTC decoding (no counterpart in the reference; Graves et al. 2006, section 3.2: best path decoding) -------------------------
+ * What a CN_LAYER_CTC layer recognises in the posteriors of the softmax layer in front of it, and how far that is from the
+ * label sequences cn_layer_set_label_sequences brought: integer work on the fp32 posteriors where they lie, nothing is copied to
+ * the host but the results.  Prefix search and language models are not part of it.
+ *
+ * The rule, for slot s of the loaded fraction, len_s its length in the ctc layer's own time axis (cn_layer_time; behind strided
+ * context layers the reduced length), C the layer's size, blank = C - 1:
+ *      k_t     = the index of the largest of the C posteriors of frame t; of equal values the LOWEST index wins (the scan
+ *                `best = 0; for k = 1 .. C-1: if (y[k] > y[best]) best = k`, which is numpy.argmax).  Pad columns, pad slots and
+ *                frames t >= len_s take no part.
+ *      decoded = k_t for t = 0 .. len_s - 1, kept when k_t != blank and (t == 0 or k_t != k_{t-1}), in order: D_s labels.
+ *                `x _ x` keeps both x; a run of x is one x however long.
+ *      dist_s  = the Levenshtein distance of decoded to the slot's U_s labels with unit costs for an insertion, a deletion and a
+ *                substitution; D_s for U_s = 0 and U_s for D_s = 0.
+ * All three are integers: two runs, and any order of summation, give the same numbers.
+ *
+ * Bounds.  No bound on the steps T.  The distance keeps three anti-diagonals of min(D_s, U_s) + 1 ints in LDS, at most 60 KB:
+ * min(T, longest label sequence of the fraction) <= 5119, else CN_ERR_SHAPE; nothing is ever truncated.  A ctc layer's label cap
+ * cannot exceed 2047 (cn_layer_set_label_sequences), so no fraction a layer accepts comes near the bound.
+ *
+ * Errors of all three calls: a layer that is not ctc: CN_ERR_BAD_ARG; before a fraction is loaded, and before the softmax layer in
+ * front has run its forward pass of the loaded fraction: CN_ERR_STATE.  The first decoding call of a layer allocates its buffers
+ * (2 * max_seq_length * padded parallel sequences ints); without one the library launches what it launches without this section. */
+/* decoded [num_sequences][T] with T the layer's own steps (cn_layer_time) -- only the first decoded_lengths[s] entries of row s are
+ * defined --, decoded_lengths [num_sequences], distances [num_sequences]; any of the three may be NULL.  distances[s] is -1 for
+ * every s when the loaded fraction has no valid label sequences (a forward pass over unlabelled data); decoding works all the
+ * same.                                                                                                              [sync] */
+int  cn_ctc_decode(cn_layer *ctc, int *decoded, int *decoded_lengths, int *distances);
+/* Beside cn_loss_accumulate: adds the sum of dist_s and the sum of U_s over the fraction's slots to two 64-bit integer sums on the
+ * device that the context keeps.  Without valid label sequences: CN_ERR_STATE.                                      [async] */
+int  cn_ctc_decode_accumulate(cn_layer *ctc);
+/* Beside cn_loss_read: the two sums (either pointer may be NULL; both 0 before the first accumulation); `reset` != 0 clears them
+ * behind the read.  Data-parallel: the sums of this rank's sequences.                                                [sync] */
+int  cn_ctc_decode_read(cn_ctx *ctx, int64_t *label_errors, int64_t *labels, int reset);
+
 #ifdef __cplusplus
 }
 #endif

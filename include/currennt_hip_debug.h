@@ -80,6 +80,14 @@ int cn_dbg_layer_pad_bits(cn_layer *layer, long long *nonzero);
  * with CN_ERR_STATE when a pad slot or pad column of it is not exactly 0.  [sync] */
 int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
                float *loss_out, float *err_out);
+/* The launches of CTC decoding (include/currennt_hip.h, section CTC decoding; csrc/cn_ctc_decode.hip) on posteriors of the caller's
+ * choice.  Host arrays as for cn_dbg_ctc; label_lengths == NULL: a fraction without labels (every distance is -1).  The pad
+ * columns of the device's rows hold +inf: they would win every row if they took part.  accumulate != 0: the context's sums take
+ * the fraction's numbers (cn_ctc_decode_read), which needs labels (CN_ERR_STATE).  out, any may be NULL: argmax_out [T * PS] the
+ * index per frame (-1 for a frame with pattern type 0), decoded [PS][T], decoded_lengths [PS], distances [PS].  The hook fails
+ * with CN_ERR_STATE when a pad slot decodes to anything.  [sync] */
+int cn_dbg_ctc_decode(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
+                      int accumulate, int *argmax_out, int *decoded, int *decoded_lengths, int *distances);
 
 /* The masked operand copy a dropping layer's input products read (include/currennt_hip.h, section Dropout), as its last forward
  * pass left it: reference layout [T * PS][P], P the preceding layer's size, widened to float; count = T * PS * P.  CN_ERR_STATE

@@ -68,6 +68,8 @@ EXPORTS = [
     "cn_layer_create_context", "cn_layer_context", "cn_layer_create_context_strided", "cn_layer_context_stride", "cn_layer_time",
     # include/currennt_hip.h, section LAMB
     "cn_lamb_update", "cn_lamb_update_all", "cn_ctx_arm_lamb", "cn_ctx_set_trust_bounds", "cn_ctx_get_trust_bounds", "cn_layer_trust_ratio",
+    # include/currennt_hip.h, section CTC decoding, and its hook in include/currennt_hip_debug.h
+    "cn_ctc_decode", "cn_ctc_decode_accumulate", "cn_ctc_decode_read", "cn_dbg_ctc_decode",
     # include/currennt_hip.h, section Adam (tests/test_adam_reference.py keeps this section last)
     "cn_adam_update", "cn_adam_update_all", "cn_ctx_arm_adam",
 ]
@@ -223,6 +225,10 @@ def load_library():
     L.cn_dbg_prefetch_hits.argtypes = [vp, C.POINTER(C.c_int)]
     L.cn_layer_set_label_sequences.argtypes = [vp, vp, vp, ci]
     L.cn_dbg_ctc.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+    L.cn_ctc_decode.argtypes = [vp, vp, vp, vp]
+    L.cn_ctc_decode_accumulate.argtypes = [vp]
+    L.cn_ctc_decode_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ci]
+    L.cn_dbg_ctc_decode.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp]
     L.cn_layer_set_dropout.argtypes = [vp, cf]
     L.cn_ctx_set_dropout_pass.argtypes = [vp, ci, C.c_uint64, C.c_uint64]
     L.cn_dbg_dropout_input.argtypes = [vp, vp, C.c_size_t]

@@ -151,6 +151,7 @@ struct cn_ctx {
     int *d_tcls = nullptr;
     float *d_loss = nullptr;      // [2] per-call (error, #correct as int bits)
     float *d_loss_acc = nullptr;  // [2] running sums for cn_loss_accumulate
+    unsigned long long *d_ctc_sums = nullptr;   // {label errors, labels} of cn_ctc_decode_accumulate, allocated by the first decoding call
     unsigned long long *d_xch = nullptr; size_t xch_bytes = 0;   // cluster kernels' exchange granules
     unsigned xch_epoch = 0;       // granule tags handed out so far (LstmRec::xch_epoch)
     int *d_fault = nullptr;       // device fault word (bounded spins)
@@ -390,6 +391,10 @@ struct cn_layer {
     // two pinned images of ctc_labels, used in turn (the host packs fraction k + 1 while the upload of fraction k may still be
     // queued); an image's last upload has read it when its event completes
     int *ctc_hbuf[2] = {nullptr, nullptr}; hipEvent_t ctc_ev[2] = {nullptr, nullptr}; unsigned ctc_uploads = 0;
+    // CTC decoding (cn_ctc_decode.hip), allocated by the layer's first decoding call: [maxN] argmax per row, then [PSp][maxT]
+    // decoded, [PSp] lengths, [PSp] distances
+    int *ctc_dec = nullptr;
+    uint64_t fwd_serial = 0;              // softmax layer: the load number (cn_ctx::frac_serial) of its last forward pass
 
     std::vector<void *> owned;            // device allocations to free
 
@@ -1531,6 +1536,7 @@ void ff_forward(cn_layer *l)
     }
     if (softmax) {
         for (cn_layer *p : c->layers) if (p->prev == l) p->ctc_swept = false;      // (a ctc layer's sweeps belonged to the old posteriors)
+        l->fwd_serial = c->frac_serial;
         flush_loss(c);                         // (the row statistics are about to be overwritten)
         Timed tm(c, KC_OTHER);
         const bool stat = c->d_rowstat != nullptr;
@@ -1745,7 +1751,7 @@ int cn_ctx_destroy(cn_ctx *ctx)
         for (int k = 0; k < KC_COUNT; ++k) for (auto &sp : ctx->spans[k]) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
         for (hipEvent_t e : ctx->free_events) hipEventDestroy(e);
         hipFree(ctx->pf.pat_raw); hipFree(ctx->pf.tcls); hipFree(ctx->d_colpart); hipFree(ctx->aug_tab); hipFree(ctx->pf.aug_tab);
-        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->lamb_u); hipFree(ctx->lamb_recs); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault); hipFree(ctx->cx_len);
+        hipFree(ctx->d_pat_raw); hipFree(ctx->d_tcls); hipFree(ctx->d_loss); hipFree(ctx->arena); hipFree(ctx->adam_v); hipFree(ctx->lamb_u); hipFree(ctx->lamb_recs); hipFree(ctx->avg); hipFree(ctx->clip_rec); hipFree(ctx->acc); hipFree(ctx->d_rowstat); hipFree(ctx->d_xch); hipFree(ctx->d_fault); hipFree(ctx->cx_len); hipFree(ctx->d_ctc_sums);
         if (ctx->own_stream) hipStreamDestroy(ctx->stream);
         if (cn::t_opt == &ctx->opt) cn::t_opt = nullptr;
         delete ctx;
@@ -2764,6 +2770,89 @@ int cn_loss_read(cn_ctx *ctx, float *error_sum, int64_t *correct_sum, int reset)
         read_loss_sums(ctx, ctx->d_loss_acc, reset != 0, &err, &cc);
         if (error_sum) *error_sum = err;
         if (correct_sum) *correct_sum = cc;
+    });
+}
+
+// ---- CTC decoding (cn_ctc_decode.hip) ------------------------------------------------------------
+static unsigned long long *ctc_sums(cn_ctx *c)
+{
+    if (!c->d_ctc_sums) {
+        HIP_CHECK(hipMalloc((void **)&c->d_ctc_sums, 2 * sizeof(unsigned long long)));
+        HIP_CHECK(hipMemsetAsync(c->d_ctc_sums, 0, 2 * sizeof(unsigned long long), c->stream));
+    }
+    return c->d_ctc_sums;
+}
+// The launches on the posteriors of the current forward pass; sums: the context's running sums take the fraction's numbers
+static CtcDecodeArgs ctc_decode_launch(cn_layer *post, const char *who, bool sums)
+{
+    cn_ctx *c = post->ctx;
+    if (post->kind != CN_LAYER_CTC) throw cn_error(CN_ERR_BAD_ARG, std::string(who) + ": not a ctc layer");
+    require_loaded(c);
+    cn_layer *o = post->prev;
+    require_axis(post, who);
+    if (o->fwd_serial != c->frac_serial)
+        throw cn_error(CN_ERR_STATE, std::string(who) + ": the softmax layer in front of the ctc layer has no forward pass of the current fraction");
+    if (sums && !post->ctc_labels_valid)
+        throw cn_error(CN_ERR_STATE, std::string(who) + ": the ctc layer has no label sequences for the loaded fraction (call cn_layer_set_label_sequences after cn_fraction_load)");
+    const TimeAxis *ax = post->ax;
+    const int maxU = post->ctc_labels_valid ? (post->ctc_maxS - 1) / 2 : 0;
+    if (!ctc_decode_fits(ax->T, maxU))
+        throw cn_error(CN_ERR_SHAPE, std::string(who) + ": min(steps, longest label sequence) = " + std::to_string(std::min(ax->T, maxU)) +
+                                     " exceeds " + std::to_string(CTC_DECODE_MAX_SHORT) + " (the distance's three diagonals in LDS)");
+    const size_t maxN = post->maxN();
+    if (!post->ctc_dec) post->ctc_dec = (int *)dalloc(post, (2 * maxN + 2 * (size_t)c->PSp) * sizeof(int));
+    CtcDecodeArgs a{};
+    a.pat = ax->pat; a.T = ax->T; a.PSp = c->PSp; a.C = post->size;
+    int *amax = post->ctc_dec;
+    a.amax = amax; a.decoded = amax + maxN; a.decoded_len = a.decoded + maxN; a.dist = a.decoded_len + c->PSp;
+    if (post->ctc_labels_valid) { a.labels = post->ctc_labels; a.laboff = post->ctc_labels + 3 * post->ctc_stride; }
+    a.maxShort = std::min(ax->T, maxU);
+    a.sums = sums ? ctc_sums(c) : nullptr;
+    Timed tm(c, KC_OTHER);
+    launch_ctc_argmax(c->stream, posteriors(o), ax->pat, ax->N, post->size, o->Lp, amax);
+    if (!opt().ctc_decode_argmax_only) launch_ctc_collapse(c->stream, a);
+    return a;
+}
+
+int cn_ctc_decode(cn_layer *ctc, int *decoded, int *decoded_lengths, int *distances)
+{
+    if (!ctc) { g_last_error = "cn_ctc_decode: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        cn_ctx *c = ctc->ctx;
+        enter(c);
+        const CtcDecodeArgs a = ctc_decode_launch(ctc, "cn_ctc_decode", false);
+        const size_t S = (size_t)c->numSeqs;
+        if (decoded && S) HIP_CHECK(hipMemcpyAsync(decoded, a.decoded, S * a.T * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (decoded_lengths && S) HIP_CHECK(hipMemcpyAsync(decoded_lengths, a.decoded_len, S * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (distances && S) HIP_CHECK(hipMemcpyAsync(distances, a.dist, S * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        check_fault(c);
+    });
+}
+
+int cn_ctc_decode_accumulate(cn_layer *ctc)
+{
+    if (!ctc) { g_last_error = "cn_ctc_decode_accumulate: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctc->ctx);
+        ctc_decode_launch(ctc, "cn_ctc_decode_accumulate", true);
+    });
+}
+
+int cn_ctc_decode_read(cn_ctx *ctx, int64_t *label_errors, int64_t *labels, int reset)
+{
+    if (!ctx) { g_last_error = "cn_ctc_decode_read: ctx is NULL"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        unsigned long long h[2] = {0, 0};
+        if (ctx->d_ctc_sums) {                 // (no decoding call yet: the sums are 0)
+            HIP_CHECK(hipMemcpyAsync(h, ctx->d_ctc_sums, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+            if (reset) HIP_CHECK(hipMemsetAsync(ctx->d_ctc_sums, 0, sizeof(h), ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            check_fault(ctx);
+        }
+        if (label_errors) *label_errors = (int64_t)h[0];
+        if (labels) *labels = (int64_t)h[1];
     });
 }
 
@@ -3820,6 +3909,69 @@ int cn_dbg_ctc(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int 
                     else if (!(v == 0.f)) throw cn_error(CN_ERR_STATE, "cn_dbg_ctc: a pad slot or pad column of the output errors is not 0");
                 }
         for (int s = 0; s < PS; ++s) loss_out[s] = hrs[2 * s];
+    });
+}
+
+int cn_dbg_ctc_decode(cn_ctx *ctx, const float *y, const char *pat, int T, int PS, int C, const int *labels, const int *label_lengths,
+                      int accumulate, int *argmax_out, int *decoded, int *decoded_lengths, int *distances)
+{
+    if (!ctx || !y || !pat) { g_last_error = "cn_dbg_ctc_decode: NULL argument"; return CN_ERR_BAD_ARG; }
+    return guarded([&] {
+        enter(ctx);
+        if (T <= 0 || PS <= 0 || C < 2) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc_decode: T, PS must be positive and C >= 2");
+        if (accumulate && !label_lengths) throw cn_error(CN_ERR_STATE, "cn_dbg_ctc_decode: no label sequences to accumulate against");
+        int maxU = 0; size_t total = 0;
+        for (int s = 0; label_lengths && s < PS; ++s) {
+            if (label_lengths[s] < 0) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc_decode: negative label sequence length");
+            maxU = std::max(maxU, label_lengths[s]); total += (size_t)label_lengths[s];
+        }
+        if (total && !labels) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc_decode: labels missing");
+        for (size_t i = 0; i < total; ++i)
+            if (labels[i] < 0 || labels[i] > C - 2) throw cn_error(CN_ERR_BAD_ARG, "cn_dbg_ctc_decode: label outside [0, C - 2]");
+        if (!ctc_decode_fits(T, maxU)) throw cn_error(CN_ERR_SHAPE, "cn_dbg_ctc_decode: min(T, longest label sequence) exceeds the distance's LDS bound");
+        const int PSp = round_up(PS, 4), Lp = round_up(C, 32), N = T * PSp;
+        const size_t stride = std::max<size_t>(total, 1);
+        std::vector<int> packed(3 * stride + PSp + 1, 0);
+        if (label_lengths) ctc_pack_labels(packed.data(), labels, label_lengths, PS, PSp, stride, C);
+        // the caller's [T][PS] rows in the device's [T][PSp] pitch: pad slots are PATTYPE_NONE; pad columns hold +inf, which would win
+        // every row if they took part
+        std::vector<float> hy((size_t)N * Lp, INFINITY); std::vector<char> hpat(N, 0);
+        for (int t = 0; t < T; ++t)
+            for (int s = 0; s < PS; ++s) {
+                hpat[(size_t)t * PSp + s] = pat[(size_t)t * PS + s];
+                memcpy(&hy[((size_t)t * PSp + s) * Lp], y + ((size_t)t * PS + s) * C, C * sizeof(float));
+            }
+        const size_t ints = 2 * (size_t)N + 2 * (size_t)PSp;
+        Scratch dy(hy.size() * sizeof(float)), dpat(N), dlab(packed.size() * sizeof(int)), dout(ints * sizeof(int));
+        hipStream_t st = ctx->stream;
+        HIP_CHECK(hipMemcpyAsync(dy.p, hy.data(), hy.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dpat.p, hpat.data(), N, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(dlab.p, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(dout.p, 0xFF, ints * sizeof(int), st));
+        CtcDecodeArgs a{};
+        a.pat = dpat.get<char>(); a.T = T; a.PSp = PSp; a.C = C;
+        int *amax = dout.get<int>();
+        a.amax = amax; a.decoded = amax + N; a.decoded_len = a.decoded + N; a.dist = a.decoded_len + PSp;
+        if (label_lengths) { a.labels = dlab.get<int>(); a.laboff = a.labels + 3 * stride; }
+        a.maxShort = std::min(T, maxU);
+        a.sums = accumulate ? ctc_sums(ctx) : nullptr;
+        launch_ctc_argmax(st, dy.get(), a.pat, N, C, Lp, amax);
+        launch_ctc_collapse(st, a);
+        std::vector<int> h(ints);
+        HIP_CHECK(hipMemcpyAsync(h.data(), dout.p, ints * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipGetLastError());
+        const int *hdec = h.data() + N, *hlen = hdec + N, *hdist = hlen + PSp;
+        for (int s = PS; s < PSp; ++s)       // pad slots are not part of the caller's layout: the hook itself holds them to the contract
+            if (hlen[s] != 0) throw cn_error(CN_ERR_STATE, "cn_dbg_ctc_decode: a pad slot decoded to something");
+        for (int t = 0; t < T; ++t)
+            for (int s = 0; s < PS; ++s)
+                if (argmax_out) argmax_out[(size_t)t * PS + s] = h[(size_t)t * PSp + s];
+        for (int s = 0; s < PS; ++s) {
+            if (decoded) memcpy(decoded + (size_t)s * T, hdec + (size_t)s * T, (size_t)T * sizeof(int));
+            if (decoded_lengths) decoded_lengths[s] = hlen[s];
+            if (distances) distances[s] = hdist[s];
+        }
     });
 }
 

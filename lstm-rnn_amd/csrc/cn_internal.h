@@ -50,6 +50,8 @@ enum Prec { P_BF16 = 0, P_F32 = 1, P_X3 = 2 };
     /* CTC: label cap per sequence of a CTC layer created afterwards (0: min(max_seq_length, 512)); A/B: the beta sweep as a     \
        launch of its own behind the alpha sweep instead of beside it */                                                          \
     NUM(ctc_max_labels, 0) FLAG(ctc_serial_sweeps)                                                                                \
+    /* CTC decoding, measurement only (tools/ctc_decode_cost.py): the argmax launch alone, nothing is collapsed or counted */    \
+    FLAG(ctc_decode_argmax_only)                                                                                                  \
     /* weight noise: generate the noisy operand copies on the side stream beside the forward pass (the key is known before it) \
        instead of on the main stream in front of the first backward kernel */                                                    \
     FLAG(noise_ahead)
@@ -543,6 +545,23 @@ bool ctc_shape_fits(int max_labels, int Lp);
 void launch_ctc_sweeps(hipStream_t s, const CtcArgs &a);
 // behind the sweeps: every row and column of err
 void launch_ctc_errors(hipStream_t s, const CtcArgs &a);
+
+// ---- CTC decoding (cn_ctc_decode.hip; the rule is stated in that file's header) --------------------------------------------------
+struct CtcDecodeArgs {
+    const char *pat; int T, PSp, C;       // pattern types [T * PSp] of the ctc layer's own time axis
+    const int *amax;                      // [T * PSp] launch_ctc_argmax's result
+    const int *labels, *laboff;           // as CtcArgs; laboff == nullptr: the fraction has no labels, every distance is -1
+    int maxShort;                         // >= min(D, U) of every slot: min(T, longest label sequence of the fraction)
+    int *decoded, *decoded_len, *dist;    // [PSp][T], [PSp], [PSp]
+    unsigned long long *sums;             // {label errors, labels}: added to, or nullptr
+};
+constexpr int CTC_ARGMAX_WAVE_C = 1024;   // up to this many units a wave takes a row, above it a workgroup
+constexpr int CTC_DECODE_MAX_SHORT = 5119;   // three diagonals of maxShort + 1 ints in 60 KB of LDS
+bool ctc_decode_fits(int T, int max_labels);
+// amax[n] = index of the largest of y[n][0 .. C), the lowest of equal ones; -1 for a row with pat[n] == 0
+void launch_ctc_argmax(hipStream_t s, const float *y, const char *pat, int N, int C, int Lp, int *amax);
+// behind it: decoded, decoded_len, dist and, if asked for, the sums
+void launch_ctc_collapse(hipStream_t s, const CtcDecodeArgs &a);
 // gather a padded row-major fp32/op matrix into the reference layout [N][L]
 // (host row n = t*PS + s maps to device row t*PSp + s)
 void launch_unpad(hipStream_t s, bool src_is_bf16, const void *src, long ld, int col0, int cstride, int N, int L, float *dst, long ldd, int dcol0, int PS, int PSp);

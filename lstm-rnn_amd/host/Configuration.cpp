@@ -78,7 +78,11 @@ const char *Configuration::usage()
            "            --train_fraction X --val_fraction X --test_fraction X\n"
            "            --weights_dist uniform|normal --weights_uniform_min X --weights_uniform_max X\n"
            "            --weights_normal_sigma X --weights_normal_mean X\n"
-           "  forward:  --ff_input_file F --ff_output_file F --ff_output_format single_csv|csv|htk\n"
+           "            --ctc_train_label_errors B (ctc nets: the training column shows the label error rate of best-path decoding of\n"
+           "                      the training pass's own posteriors, dropout and all, counted on the device; default false: '-')\n"
+           "  forward:  --ff_input_file F --ff_output_file F --ff_output_format single_csv|csv|htk|ctc_labels\n"
+           "                      (ctc_labels, ctc nets only: --ff_output_file is one text file with a line `<seqTag>;<l0> <l1> ...`\n"
+           "                      per sequence, the best-path decoding; labels by name when the input file has a `labels` variable)\n"
            "            --ff_output_kind N --feature_period X --revert_std B\n";
 }
 
@@ -94,6 +98,7 @@ void Configuration::apply(const std::string &key, const std::string &v)
         if (v == "single_csv") m_feedForwardFormat = FORMAT_SINGLE_CSV;
         else if (v == "csv") m_feedForwardFormat = FORMAT_CSV;
         else if (v == "htk") m_feedForwardFormat = FORMAT_HTK;
+        else if (v == "ctc_labels") m_feedForwardFormat = FORMAT_CTC_LABELS;
         else throw std::runtime_error("Error while parsing the command line and/or options file: unknown output format '" + v + "'");
     }
     else if (key == "ff_output_file") m_feedForwardOutputFile = v;
@@ -183,6 +188,7 @@ void Configuration::apply(const std::string &key, const std::string &v)
     else if (key == "dp_world") m_dpWorld = atoi(v.c_str());
     else if (key == "dump_fractions") m_dumpFractions = toBool(key, v);
     else if (key == "dump_labels") m_dumpLabels = toBool(key, v);
+    else if (key == "ctc_train_label_errors") m_ctcTrainLabelErrors = toBool(key, v);
     else if (key == "dump_epochs") m_dumpEpochs = std::max(1, atoi(v.c_str()));
     else if (key == "input_noise_sigma") m_inputNoiseSigma = (real_t)atof(v.c_str());
     else if (key == "weight_noise_sigma") m_weightNoiseSigma = (real_t)atof(v.c_str());

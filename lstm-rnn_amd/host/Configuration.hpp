@@ -14,7 +14,7 @@ namespace currennt_hip {
 
 class Configuration {
 public:
-    enum feedforwardformat_type_t { FORMAT_SINGLE_CSV, FORMAT_CSV, FORMAT_HTK };
+    enum feedforwardformat_type_t { FORMAT_SINGLE_CSV, FORMAT_CSV, FORMAT_HTK, FORMAT_CTC_LABELS };
 
     Configuration(int argc, const char *argv[]);
 
@@ -85,6 +85,7 @@ public:
     bool help() const { return m_help; }
     bool dumpFractions() const { return m_dumpFractions; }
     bool dumpLabels() const { return m_dumpLabels; }          // --dump_fractions rows also print the label sequences' counts
+    bool ctcTrainLabelErrors() const { return m_ctcTrainLabelErrors; }   // ctc: the training column shows the training pass's label error rate
     int dumpEpochs() const { return m_dumpEpochs; }
     // data/noise options of Configuration.cpp:139-146,171-176
     real_t inputNoiseSigma() const { return m_inputNoiseSigma; }
@@ -120,7 +121,7 @@ public:
 
 private:
     int m_dumpEpochs = 1;
-    bool m_dumpFractions = false, m_dumpLabels = false, m_autosave = false, m_autosaveBest = false;
+    bool m_dumpFractions = false, m_dumpLabels = false, m_ctcTrainLabelErrors = false, m_autosave = false, m_autosaveBest = false;
     real_t m_inputNoiseSigma = 0, m_weightNoiseSigma = 0;
     bool m_weightNoiseOnDevice = false, m_inputNoiseOnDevice = false;
     int m_specFreqMasks = 0, m_specFreqWidth = 0, m_specTimeMasks = 0, m_specTimeWidth = 0;

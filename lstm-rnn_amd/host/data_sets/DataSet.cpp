@@ -51,6 +51,10 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
     for (size_t fi = 0; fi < ncfiles.size(); ++fi) {
         NetCdf3File nc(ncfiles[fi]);
         const int maxSeqTagLength = nc.dimension("maxSeqTagLength");
+        // transcription data: `targetStrings` beside the alphabet `labels`; `targetClasses` may be missing
+        const bool transcripts = nc.hasVariable("targetStrings");
+        if (transcripts && !(nc.hasDimension("numLabels") && nc.hasVariable("labels")))
+            throw std::runtime_error("'" + ncfiles[fi] + "' has the variable 'targetStrings' but not the dimension 'numLabels' and the variable 'labels' its label names come from");
         if (firstFile) {                                                                       // :489-500
             m_isClassificationData = nc.hasDimension("numLabels");
             m_inputPatternSize = nc.dimension("inputPattSize");
@@ -64,6 +68,29 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
             } else if (m_outputPatternSize != nc.dimension("targetPattSize")) throw std::runtime_error("Number of targets mismatch in NC files");
             if (m_inputPatternSize != nc.dimension("inputPattSize")) throw std::runtime_error("Number of inputs mismatch in NC files");
         }
+        if (firstFile) {
+            m_hasTranscripts = transcripts;
+            m_hasTargetClasses = nc.hasVariable("targetClasses");
+        } else if (transcripts != m_hasTranscripts || (m_isClassificationData && nc.hasVariable("targetClasses") != m_hasTargetClasses))
+            throw std::runtime_error("Cannot combine NC files with and without 'targetStrings' / 'targetClasses'");
+        // --truncate_seq: a transcript cannot be cut with its frames.  Refused here when the transcripts are all the file has; a file
+        // with targetClasses as well stays usable for every layer that reads those (transcriptsCut(): not for a ctc layer)
+        if (transcripts && truncSeqLength > 0) {
+            if (!nc.hasVariable("targetClasses"))
+                throw std::runtime_error("--truncate_seq cannot be used with transcription data ('targetStrings' without 'targetClasses'): a transcript cannot be cut with its frames");
+            m_transcriptsCut = true;
+        }
+        std::vector<std::string> names;
+        if (nc.hasVariable("labels") && nc.hasDimension("numLabels") && (transcripts || nc.hasDimension("maxLabelLength"))) {
+            const int maxLabelLength = nc.dimension("maxLabelLength");
+            for (int k = 0; k < nc.dimension("numLabels"); ++k) {
+                std::string name = nc.readString("labels", k, maxLabelLength);
+                name.erase(name.find_last_not_of(" \t") + 1);                                   // (NUL- or space-padded)
+                names.push_back(name);
+            }
+            if (firstFile) m_labelNames = names;
+        }
+        const int maxTargStringLength = transcripts ? nc.dimension("maxTargStringLength") : 0;
         int nSeq = nc.dimension("numSeqs");
         nSeq = std::max((int)((real_t)nSeq * fraction), 1);                                    // :518-520
         std::vector<int> lengths = nc.readInts("seqLengths", 0, nSeq);
@@ -72,11 +99,27 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
             m_totalTimesteps += lengths[i];
             std::string seqTag = nc.readString("seqTags", i, maxSeqTagLength);
             const std::vector<int> pieces = truncatedPieces(lengths[i], truncSeqLength);
+            const size_t labelsBegin = m_transcriptData.size();
+            if (transcripts) {                                                                  // label names separated by runs of blanks
+                const std::string text = nc.readString("targetStrings", i, maxTargStringLength);
+                for (size_t p = 0; p < text.size();) {
+                    const size_t b = text.find_first_not_of(" \t\n", p);
+                    if (b == std::string::npos) break;
+                    const size_t e = std::min(text.find_first_of(" \t\n", b), text.size());
+                    const std::string token = text.substr(b, e - b);
+                    const size_t k = std::find(names.begin(), names.end(), token) - names.begin();
+                    if (k == names.size())
+                        throw std::runtime_error("Unknown label '" + token + "' in the target string of sequence '" + seqTag + "' ('" + ncfiles[fi] + "')");
+                    m_transcriptData.push_back((int)k);
+                    p = e;
+                }
+            }
             for (size_t k = 0; k < pieces.size(); ++k) {
                 sequence_t seq;
                 seq.originalSeqIdx = (int)k; seq.length = pieces[k]; seq.seqTag = seqTag;
                 m_totalNetworkTimesteps += (pieces[k] + augment.frameSkip - 1) / augment.frameSkip;
                 seq.inputsBegin = 0; seq.targetsBegin = 0;
+                seq.labelsBegin = labelsBegin; seq.labelCount = (int)(m_transcriptData.size() - labelsBegin);
                 sequences.push_back(seq);
             }
         }
@@ -88,7 +131,8 @@ DataSet::DataSet(const std::vector<std::string> &ncfiles, int parSeq, real_t fra
         size_t tgBase;
         if (m_isClassificationData) {
             tgBase = m_classData.size();
-            std::vector<int> t = nc.readInts("targetClasses", 0, frames); m_classData.insert(m_classData.end(), t.begin(), t.end());
+            if (m_hasTargetClasses) { std::vector<int> t = nc.readInts("targetClasses", 0, frames); m_classData.insert(m_classData.end(), t.begin(), t.end()); }
+            else if (!transcripts) nc.readInts("targetClasses", 0, frames);                     // (says that the variable is missing, as ever)
         } else {
             tgBase = m_targetData.size();
             std::vector<float> t = nc.readFloats("targetPatterns", 0, frames * m_outputPatternSize); m_targetData.insert(m_targetData.end(), t.begin(), t.end());
@@ -188,7 +232,9 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
         if (globalIdx(i) >= (int)m_sequences.size()) continue;
         const sequence_t &seq = m_sequences[globalIdx(i)];
         const float *src = m_inputData.data() + seq.inputsBegin;
-        if (m_isClassificationData) {                                                          // the label sequence: runs collapsed
+        if (m_hasTranscripts)                                                                  // the label sequence: the transcript
+            frac->m_labelSeqs.push_back(std::vector<int>(m_transcriptData.begin() + seq.labelsBegin, m_transcriptData.begin() + seq.labelsBegin + seq.labelCount));
+        else if (m_isClassificationData) {                                                     // ... or the target classes, runs collapsed
             std::vector<int> labels;
             for (int t = 0; t < seq.length; ++t) {
                 const int k = m_classData[seq.targetsBegin + t];
@@ -212,8 +258,9 @@ void DataSet::makeFraction(int firstSeqIdx, DataSetFraction *frac)
                 const int ts = std::min(std::max(t + off, 0), seq.length - 1);
                 std::copy(src + (size_t)ts * P, src + (size_t)(ts + 1) * P, frac->m_inputs.begin() + slot * Pf + (size_t)k * P);
             }
-            if (m_isClassificationData)                                                        // :372-380, class 0 before the lag
-                frac->m_targetClasses[slot] = t >= lag ? m_classData[seq.targetsBegin + (t - lag)] : 0;
+            if (m_isClassificationData) {                                                      // :372-380, class 0 before the lag
+                if (m_hasTargetClasses) frac->m_targetClasses[slot] = t >= lag ? m_classData[seq.targetsBegin + (t - lag)] : 0;
+            }                                                                                  // (transcripts alone: every class stays -1)
             else if (t >= lag)                                                                 // :383-397, 1.0 before the lag
                 std::copy(m_targetData.begin() + seq.targetsBegin + (size_t)(t - lag) * m_outputPatternSize,
                           m_targetData.begin() + seq.targetsBegin + (size_t)(t - lag + 1) * m_outputPatternSize,

@@ -36,9 +36,10 @@ public:
     const Hip::real_vector &inputs() const { return m_inputs; }
     const Hip::real_vector &outputs() const { return m_outputs; }
     const Hip::int_vector &targetClasses() const { return m_targetClasses; }
-    // classification data: the label sequence of each sequence of the fraction, slot by slot -- its per-frame target classes
-    // with every run collapsed (a a a b b a -> a b a); what a ctc post output layer trains against (no counterpart in the
-    // reference).  A label that repeats without another one in between cannot be expressed this way.
+    // classification data: the label sequence of each sequence of the fraction, slot by slot; what a ctc post output layer trains
+    // against (no counterpart in the reference).  Transcription data (DataSet::hasTranscripts): the sequence's transcript from
+    // `targetStrings`, repeats and the empty sequence included.  Otherwise its per-frame target classes with every run collapsed
+    // (a a a b b a -> a b a), where a label that repeats without another one in between cannot be expressed.
     const std::vector<std::vector<int> > &labelSeqs() const { return m_labelSeqs; }
 
 private:
@@ -62,7 +63,8 @@ struct Augment { real_t noiseDeviation = 0; int contextLeft = 0, contextRight = 
 class DataSet {
 public:
     typedef data_sets::Augment Augment;
-    struct sequence_t { int originalSeqIdx; int length; std::string seqTag; size_t inputsBegin; size_t targetsBegin; };
+    // labelsBegin / labelCount: the sequence's transcript in m_transcriptData (transcription data only)
+    struct sequence_t { int originalSeqIdx; int length; std::string seqTag; size_t inputsBegin; size_t targetsBegin; size_t labelsBegin; int labelCount; };
 
     DataSet();                                              // empty set (DataSet.cpp:429-442)
     // DataSet.cpp:443-606; `sortByLength` = Configuration::trainingMode() there (:603-605)
@@ -96,6 +98,17 @@ public:
     int fractionInputPatternSize() const { return m_inputPatternSize * (m_augment.contextLeft + m_augment.contextRight + 1); }
     int outputPatternSize() const { return m_outputPatternSize; }
     int numLabels() const { return m_numLabels; }                                     // classification data: the numLabels dimension
+    // Transcription data (the layout of RNNLIB's CTC corpora): the files have `targetStrings(numSeqs, maxTargStringLength)`, one
+    // string of label names per sequence, and the alphabet `labels(numLabels, maxLabelLength)`; the label sequences of the fractions
+    // are the transcripts.  Such files need no `targetClasses`: hasTargetClasses() says whether they have them (the fractions'
+    // targetClasses are all -1 when not, and only a ctc post output layer can train on the set).
+    bool hasTranscripts() const { return m_hasTranscripts; }
+    bool hasTargetClasses() const { return m_hasTargetClasses; }
+    // --truncate_seq cut the sequences of a set with transcripts into pieces: labelSeqs() of its fractions mean nothing (every piece
+    // carries the whole transcript), so the driver refuses a ctc net and --dump_labels on it
+    bool transcriptsCut() const { return m_transcriptsCut; }
+    // the `labels` variable of the first file, row k the name of label k; empty when the file has none
+    const std::vector<std::string> &labelNames() const { return m_labelNames; }
     const Hip::real_vector &outputMeans() const { return m_outputMeans; }
     const Hip::real_vector &outputStdevs() const { return m_outputStdevs; }
     // what the loader thread has spent packing fractions so far (noise and splicing included) and how many it packed: read
@@ -106,7 +119,9 @@ public:
 private:
     double m_loaderSeconds = 0;
     long m_loaderFractions = 0;
-    bool m_fractionShuffling = false, m_sequenceShuffling = false, m_isClassificationData = false;
+    bool m_fractionShuffling = false, m_sequenceShuffling = false, m_isClassificationData = false, m_hasTranscripts = false, m_hasTargetClasses = false, m_transcriptsCut = false;
+    std::vector<std::string> m_labelNames;
+    Hip::int_vector m_transcriptData;
     int m_parallelSequences = 0, m_totalSequences = 0, m_totalTimesteps = 0, m_totalNetworkTimesteps = 0, m_minSeqLength = 0, m_maxSeqLength = 0,
         m_inputPatternSize = 0, m_outputPatternSize = 0, m_numLabels = 0, m_curFirstSeqIdx = -1, m_rank = 0, m_world = 1;
     unsigned m_rngState = 0;

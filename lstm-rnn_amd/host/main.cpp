@@ -79,6 +79,7 @@ std::shared_ptr<data_sets::DataSet> loadDataSet(const Configuration &config, dat
                                             (ds->maxSeqLength() + config.inputFrameSkip() - 1) / config.inputFrameSkip(), ds->totalNetworkTimesteps());
     if (config.inputSpliceOnDevice()) printf("Input splicing:   on the device (context %d + %d frames, uploaded unspliced)\n", config.inputLeftContext(), config.inputRightContext());
     if (deviceNoise) printf("Input noise:      sigma %g, generated on the device\n", (double)deviceSigma);
+    if (ds->hasTranscripts()) printf("Label sequences:  from targetStrings (%d label names%s)\n", ds->numLabels(), ds->hasTargetClasses() ? "" : "; the file has no targetClasses");
     if (dsType == DATA_SET_TRAINING && config.specAugment())
         printf("SpecAugment:      %d frequency masks of up to %d features, %d time masks of up to %d frames (at most %g of a sequence), on the device\n",
                config.specAugmentFreqMasks(), config.specAugmentFreqWidth(), config.specAugmentTimeMasks(), config.specAugmentTimeWidth(),
@@ -177,7 +178,10 @@ void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::Data
     const bool unstandardize = config.revertStd();
     if (unstandardize) printf("Outputs will be scaled by mean and standard deviation specified in NC file.\n");
     std::ofstream single;
-    if (config.feedForwardFormat() == Configuration::FORMAT_SINGLE_CSV) single.open(config.feedForwardOutputFile().c_str());
+    const bool ctcLabels = config.feedForwardFormat() == Configuration::FORMAT_CTC_LABELS;
+    if (config.feedForwardFormat() == Configuration::FORMAT_SINGLE_CSV || ctcLabels) single.open(config.feedForwardOutputFile().c_str());
+    const std::vector<std::string> &labelNames = set.labelNames();
+    std::vector<int> decoded, decodedLengths;
     data_sets::DataSetFraction frac;
     int fracIdx = 0;
     while (set.getNextFraction(&frac)) {
@@ -189,6 +193,23 @@ void feedForward(const Configuration &config, NeuralNetwork &nn, data_sets::Data
         }
         nn.loadSequences(frac);
         nn.computeForwardPass();
+        if (ctcLabels) {          // <seqTag>;<l0> <l1> ... per sequence: the best path, decoded on the device (no posteriors are copied)
+            int T = 0;
+            hipCheck(cn_layer_time(nn.postOutputLayer().handle(), &T, nullptr, nullptr), nn.context());
+            decoded.assign((size_t)frac.numSequences() * T, 0); decodedLengths.assign(frac.numSequences(), 0);
+            hipCheck(cn_ctc_decode(nn.postOutputLayer().handle(), decoded.data(), decodedLengths.data(), nullptr), nn.context());
+            for (int psIdx = 0; psIdx < frac.numSequences(); ++psIdx) {
+                single << frac.seqInfo(psIdx).seqTag << ';';
+                for (int k = 0; k < decodedLengths[psIdx]; ++k) {
+                    const int label = decoded[(size_t)psIdx * T + k];
+                    if (k) single << ' ';
+                    if (label < (int)labelNames.size()) single << labelNames[label]; else single << label;
+                }
+                single << '\n';
+            }
+            printf(" done.\n");
+            continue;
+        }
         std::vector<std::vector<std::vector<real_t> > > outputs = nn.getOutputs();
         for (int psIdx = 0; psIdx < (int)outputs.size(); ++psIdx) {
             const std::string &tag = frac.seqInfo(psIdx).seqTag;
@@ -257,6 +278,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
 
         if (config.dumpFractions()) {     // host-only check of reader + packer (no GPU needed)
             data_sets::DataSet &ds = config.trainingMode() ? *trainingSet : *feedForwardSet;
+            if (config.dumpLabels() && ds.transcriptsCut())
+                throw std::runtime_error("--truncate_seq cannot be used with the label sequences of transcription data ('targetStrings'): a transcript cannot be cut with its frames");
             data_sets::DataSetFraction frac;
             // --dump_epochs N: N passes over the set (the shuffles of --shuffle_sequences / --shuffle_fractions run at the start
             // of every pass, DataSet.cpp:416-427)
@@ -312,7 +335,19 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             };
             checkSet(*trainingSet, "training", false); checkSet(*validationSet, "validation", false); checkSet(*testSet, "test", false);
             checkSet(*feedForwardSet, "feed forward input", true);
+            // transcripts without per-frame classes: nothing but a ctc layer can train on or score them
+            auto needsClasses = [&](const data_sets::DataSet &set, const char *which) {
+                if (!ctcTask && !set.empty() && set.hasTranscripts() && !set.hasTargetClasses())
+                    throw std::runtime_error(std::string("The ") + which + " set has 'targetStrings' but no 'targetClasses': only a network whose post output layer is 'ctc' can use it, this one's is '" +
+                                             (last.isObject() && last.hasMember("type") ? last["type"].getString() : std::string("?")) + "'");
+            };
+            needsClasses(*trainingSet, "training"); needsClasses(*validationSet, "validation"); needsClasses(*testSet, "test");
+            if (ctcTask && trainingSet->transcriptsCut())
+                throw std::runtime_error("--truncate_seq cannot be used with a ctc network on transcription data ('targetStrings'): a transcript cannot be cut with its frames");
+            needsClasses(*feedForwardSet, "feed forward input");
         }
+        if (!config.trainingMode() && config.feedForwardFormat() == Configuration::FORMAT_CTC_LABELS && !ctcTask)
+            throw std::runtime_error("--ff_output_format ctc_labels needs a network whose last layer is of type 'ctc'");
 
         printf("Creating the neural network... ");
         fflush(stdout);
@@ -364,7 +399,7 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
         printLayers(neuralNetwork);
         printf("\n");
 
-        // (ctc: the percentage column is the label error rate of best-path decoding, on the validation and test sets only)
+        // (ctc: the percentage column is the label error rate of best-path decoding; of the training set with --ctc_train_label_errors)
         const bool classificationTask = dynamic_cast<layers::MulticlassClassificationLayer *>(&neuralNetwork.postOutputLayer()) != 0 ||
                                         dynamic_cast<layers::BinaryClassificationLayer *>(&neuralNetwork.postOutputLayer()) != 0 || ctcTask;   // main.cpp:165-166
 
@@ -426,6 +461,7 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
             optimizer.setWeightNoise(config.weightNoiseSigma(), config.randomSeed());
             // --weight_noise_on_device: seed = --random_seed on every rank (no rank offset: the replicas stay identical)
             optimizer.setWeightNoiseOnDevice(config.weightNoiseOnDevice(), (uint64_t)config.randomSeed());
+            optimizer.setCtcTrainLabelErrors(ctcTask && config.ctcTrainLabelErrors());
             // every rank its own masks: seed = --random_seed + rank * 0x9E3779B97F4A7C15 (mod 2^64)
             optimizer.setDropoutSeed((uint64_t)config.randomSeed() + (uint64_t)(dp.active ? dp.rank : 0) * 0x9E3779B97F4A7C15ull);
             // --input_noise_on_device, --spec_augment_*: every rank its own stream, like the dropout masks (a rank holds other sequences)
@@ -460,7 +496,8 @@ int trainerMain(const Configuration &config, const DataParallel &dp = DataParall
                 // CN_DRIVER_TIMING=1: the epoch's wall time with microsecond resolution on stderr (the table above keeps the
                 // reference's format, one decimal); bench.py's driver leg reads it
                 if (getenv("CN_DRIVER_TIMING")) fprintf(stderr, "TIMING epoch %d %.6f s %d frames\n", optimizer.currentEpoch(), duration, trainingSet->totalTimesteps());
-                if (ctcTask) infoRows += printfRow("      -%10.3lf |", (double)optimizer.curTrainingError());     // (decoding every training fraction would put a D2H copy on the hot path)
+                // (ctc: the training pass counts label errors only with --ctc_train_label_errors, two more launches per fraction)
+                if (ctcTask && !config.ctcTrainLabelErrors()) infoRows += printfRow("      -%10.3lf |", (double)optimizer.curTrainingError());
                 else if (classificationTask) infoRows += printfRow(errFormat, (double)optimizer.curTrainingClassError() * 100.0, (double)optimizer.curTrainingError());
                 else infoRows += printfRow(errFormat, (double)optimizer.curTrainingError());
                 const bool validated = !validationSet->empty() && optimizer.currentEpoch() % config.validateEvery() == 0;

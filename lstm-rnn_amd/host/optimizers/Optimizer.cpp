@@ -42,35 +42,6 @@ void Optimizer::_restoreWeights()
     }
 }
 
-namespace {
-// Best-path decoding of one sequence (argmax per frame, repeats collapsed, blanks dropped) and its Levenshtein distance to the
-// label sequence.  out: [T][PS][C] posteriors as the output layer holds them; slot: the sequence's parallel-sequence index.
-int ctcLabelErrors(const Hip::real_vector &out, int PS, int C, int slot, int length, const std::vector<int> &labels)
-{
-    std::vector<int> decoded;
-    int prev = -1;
-    for (int t = 0; t < length; ++t) {
-        const real_t *y = out.data() + ((size_t)t * PS + slot) * C;
-        int best = 0;
-        for (int k = 1; k < C; ++k) if (y[k] > y[best]) best = k;
-        if (best != prev && best != C - 1) decoded.push_back(best);
-        prev = best;
-    }
-    std::vector<int> row(labels.size() + 1);
-    for (size_t j = 0; j <= labels.size(); ++j) row[j] = (int)j;
-    for (size_t i = 1; i <= decoded.size(); ++i) {
-        int diag = row[0];
-        row[0] = (int)i;
-        for (size_t j = 1; j <= labels.size(); ++j) {
-            const int subst = diag + (decoded[i - 1] != labels[j - 1]);
-            diag = row[j];
-            row[j] = std::min(subst, std::min(row[j], row[j - 1]) + 1);
-        }
-    }
-    return row[labels.size()];
-}
-}  // namespace
-
 real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates, real_t *classError)
 {
     real_t error = 0;
@@ -87,10 +58,12 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
     // added up on the device, in the same order and in float like the reference's `error += ...`, and read back once
     // per pass over the data set: the host keeps enqueueing fractions while the device works.
     hipCheck(cn_loss_read(m_neuralNetwork.context(), nullptr, nullptr, 1), m_neuralNetwork.context());     // clear the sums
-    // ctc: the class error of an evaluation pass is the LABEL ERROR RATE of best-path decoding, computed here from the posteriors
-    // (one D2H copy per fraction: not on the training pass, whose class error stays unset).  Data-parallel: of this rank's sequences.
+    // ctc: the class error of an evaluation pass is the LABEL ERROR RATE of best-path decoding, counted on the device beside the error
+    // (include/currennt_hip.h, section CTC decoding) and read once per pass like it; of a training pass only with
+    // --ctc_train_label_errors, else its class error stays unset.  Data-parallel: of this rank's sequences.
     const bool ctc = dynamic_cast<layers::CtcPostOutputLayer *>(&m_neuralNetwork.postOutputLayer()) != 0;
-    long labelErrors = 0, labelCount = 0;
+    const bool ctcDecode = ctc && (!calcWeightUpdates || m_ctcTrainLabelErrors);
+    if (ctcDecode) hipCheck(cn_ctc_decode_read(m_neuralNetwork.context(), nullptr, nullptr, 1), m_neuralNetwork.context());     // clear the sums
     // dropout: only training passes drop; the calls are skipped altogether when no layer has a rate
     bool anyDropout = false;
     for (size_t i = 1; i + 1 < ls.size(); ++i) {
@@ -124,14 +97,7 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
         m_neuralNetwork.loadSequences(frac);
         m_neuralNetwork.computeForwardPass();
         hipCheck(cn_loss_accumulate(m_neuralNetwork.postOutputLayer().handle()), m_neuralNetwork.context());
-        if (ctc && !calcWeightUpdates) {
-            const Hip::real_vector out = m_neuralNetwork.outputLayer().outputs();
-            for (int i = 0; i < frac.numSequences(); ++i) {
-                labelErrors += ctcLabelErrors(out, m_neuralNetwork.outputLayer().parallelSequences(), m_neuralNetwork.outputLayer().size(), i,
-                                              (frac.seqInfo(i).length + outRate - 1) / outRate, frac.labelSeqs()[i]);
-                labelCount += (long)frac.labelSeqs()[i].size();
-            }
-        }
+        if (ctcDecode) hipCheck(cn_ctc_decode_accumulate(m_neuralNetwork.postOutputLayer().handle()), m_neuralNetwork.context());
         // The data set's worker has the next fraction ready one ahead (DataSet.cpp:202-240,632-668); in training it goes on
         // across PCIe and through the re-layout beside this fraction's backward pass (cn_fraction_prefetch), and the load at
         // the top of the next iteration only exchanges buffers.  (`next` keeps its vectors' storage when it becomes `frac`:
@@ -195,7 +161,11 @@ real_t Optimizer::_processDataSet(data_sets::DataSet &ds, bool calcWeightUpdates
     }
     error /= ds.totalSequences();                                           // :99-101
     *classError /= (real_t)classified;
-    if (ctc) *classError = labelCount ? (real_t)labelErrors / (real_t)labelCount : 0;
+    if (ctcDecode) {
+        int64_t labelErrors = 0, labelCount = 0;
+        hipCheck(cn_ctc_decode_read(m_neuralNetwork.context(), &labelErrors, &labelCount, 1), m_neuralNetwork.context());
+        *classError = labelCount ? (real_t)labelErrors / (real_t)labelCount : 0;
+    } else if (ctc) *classError = 0;
     return error;
 }
 

@@ -33,6 +33,9 @@ public:
     // fraction in the epoch, derived like dropout's -- set in front of each fraction's prefetch announcement and again in front
     // of its load, so the load stays a hit; validation and test passes load without augmentation
     void setInputAugment(const cn_input_augment &settings) { m_inputAugment = settings; m_inputAugmentOn = true; }
+    // ctc nets (--ctc_train_label_errors): training passes count label errors too, on the posteriors their own forward pass produced
+    // (include/currennt_hip.h, section CTC decoding); curTrainingClassError() is then the training pass's label error rate
+    void setCtcTrainLabelErrors(bool on) { m_ctcTrainLabelErrors = on; }
     // Dropout (layers with a JSON "dropout"; include/currennt_hip.h, section Dropout): training passes drop with this seed and
     // pass = (epoch << 32) | index of the fraction in the epoch -- derived, not stored, so --continue resumes the same masks;
     // validation and test passes do not drop
@@ -117,6 +120,7 @@ private:
     uint64_t m_dropoutSeed = 0;
     cn_input_augment m_inputAugment{};
     bool m_inputAugmentOn = false;
+    bool m_ctcTrainLabelErrors = false;
     real_t m_avgDecay = 0;
     bool m_avgWarmup = true, m_avgStartsFresh = false;
     int64_t m_avgSteps = 0;             // averaging steps taken so far

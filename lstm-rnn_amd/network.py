@@ -423,6 +423,7 @@ class NeuralNetwork:
         k = self.frame_skip
         self.T, self.Tmin = -(-f.max_seq_length // k), -(-f.min_seq_length // k)
         self.N = self.T * self.PS
+        self._num_seqs = int(f.num_sequences)
         # lengths(): counted on demand, from the host's pattern types (kept by reference with their T) or, after a resident load,
         # from the device's
         self._lens, self._lens_from = None, lens
@@ -474,6 +475,29 @@ class NeuralNetwork:
         err, cor = C.c_float(), C.c_int64()
         B.check(self.lib.cn_loss_read(self.ctx, C.byref(err), C.byref(cor), 1 if reset else 0), self.ctx)
         return float(err.value), int(cor.value)
+
+    def ctc_decode(self):
+        """cn_ctc_decode: best-path decoding of the current forward pass of a ctc net.  Returns (one int array of labels per sequence
+        of the fraction, distances): the Levenshtein distance of each to its label sequence, or None when the fraction has no
+        labels."""
+        post = self.layers[-1]
+        S = getattr(self, "_num_seqs", self.PS)
+        T = post.time()[0] if self.T else 1                             # (before a load the call itself says what is wrong)
+        dec, lens, dist = np.zeros((S, T), np.int32), np.zeros(S, np.int32), np.zeros(S, np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        B.check(self.lib.cn_ctc_decode(post.handle, vp(dec), vp(lens), vp(dist)), self.ctx)
+        seqs = [dec[s, :lens[s]].copy() for s in range(S)]
+        return seqs, (None if S and (dist < 0).all() else dist)
+
+    def ctc_decode_accumulate(self):
+        """cn_ctc_decode_accumulate: add this fraction's label errors and label count to the device-side sums (no host sync)."""
+        B.check(self.lib.cn_ctc_decode_accumulate(self.layers[-1].handle), self.ctx)
+
+    def ctc_decode_stats(self, reset=True):
+        """cn_ctc_decode_read: (label_errors, labels) accumulated so far."""
+        e, n = C.c_int64(), C.c_int64()
+        B.check(self.lib.cn_ctc_decode_read(self.ctx, C.byref(e), C.byref(n), 1 if reset else 0), self.ctx)
+        return int(e.value), int(n.value)
 
     def compute_forward_pass(self):                                                    # NeuralNetwork.cpp:168-173
         for lay in self.layers:
