@@ -612,6 +612,10 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_bwd_kernel(LstmR
         f32x4 a_[UG][RPL];
         float cp_[UG][RPL];
         [[maybe_unused]] float th_[UG][RPL];
+        // fp32 mode: err stays out of the product and is added behind it.  As the C operand it made every one of the 4 Hp / 4
+        // chained MFMAs round at |err|, where the reference rounds four times (one product per gate, Matrix.cu:64-85): with errors
+        // far above the recurrent sum (a clipped pass) the deltas sat 7 - 16 D_ref from fp64 instead of within the reference's noise
+        [[maybe_unused]] float es_[UG][RPL];
         unsigned char dmy[RPL];                      // dummy-slot flags of this step (LDS table, see the forward kernel)
 #pragma unroll
         for (int r = 0; r < RPL; ++r) dmy[r] = dtab[t * (4 * RPL) + 4 * r + q];
@@ -630,7 +634,8 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_bwd_kernel(LstmR
 #pragma unroll
                 for (int g = 0; g < 4; ++g) asm volatile("v_mov_b32 %0, %1" : "=&v"(a_[u][r][g]) : "v"(pre.a[u][r][g]));
                 if constexpr (CN_TH_STORE) asm volatile("v_mov_b32 %0, %1" : "=&v"(th_[u][r]) : "v"(pre.th[u][r]));
-                acc[u][r] = e_;                                                             // err enters as the MFMA C operand
+                if constexpr (F32) { es_[u][r] = e_; acc[u][r] = 0.f; }
+                else acc[u][r] = e_;                                                        // err enters as the MFMA C operand
                 cp_[u][r] = hasprev_ ? c_ : 0.f;
             }
 #pragma unroll
@@ -762,7 +767,8 @@ __global__ __launch_bounds__(HP ? HP * 4 / UG : 1024) void lstm_bwd_kernel(LstmR
             for (int r = 0; r < RPL; ++r) {
                 const bool dummy = dmy[r] != 0;
                 // ComputeBlockErrorsFn, LstmLayer.cu:236-285
-                const float e = acc[u][r];
+                float e = acc[u][r];
+                if constexpr (F32) e += es_[u][r];
                 const float ni = a_[u][r][0], ig = a_[u][r][1], fg = a_[u][r][2], og = a_[u][r][3];
                 const float cs = ccur[u][r], cp = cp_[u][r];
                 const float th = CN_TH_STORE ? th_[u][r] : tanh_ref<ACC>(cs);      // (the forward pass's value, same function of the same cs)

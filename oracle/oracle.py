@@ -345,21 +345,28 @@ class OracleNetwork:
             L.orc_post_backward(POST[post.type], out.size, self.N, self.patTypes, self.targets,
                                 out.outputs, out.outputErrors)
         for lay in reversed(self.layers[1:-1]):
-            P, x = lay.prev.size, lay.prev.outputs
-            # only a trainable preceding layer receives errors (LstmLayer.cu:991-992)
-            prev_err = lay.prev.outputErrors if lay.prev.trainable else None
-            if lay.type in ("lstm", "blstm"):
-                L.orc_lstm_backward(P, lay.size, int(lay.bidir), lay.bias, self.PS, self.maxT,
-                                    self.T, self.Tmin, self.patTypes, lay.weights, x,
-                                    lay.outputErrors, _ptr(prev_err), lay.weightUpdates, lay.bufs)
-            elif lay.type == "softmax":
-                L.orc_softmax_backward(P, lay.size, lay.bias, self.N, self.patTypes, lay.weights,
-                                       x, lay.outputs, lay.outputErrors, _ptr(prev_err),
-                                       lay.weightUpdates, lay.patTmp)
-            else:
-                L.orc_ff_backward(ACT[lay.type], P, lay.size, lay.bias, self.N, lay.weights,
-                                  x, lay.outputs, lay.outputErrors, _ptr(prev_err),
-                                  lay.weightUpdates)
+            self.backward_layer(lay)
+
+    def backward_layer(self, lay):
+        """computeBackwardPass of ONE layer: reads lay.outputErrors (whatever wrote them: the layer above, the post output layer,
+        or a test that injects errors), writes the layer's weightUpdates, its internals and the preceding trainable layer's
+        outputErrors.  compute_backward_pass is this call per layer in reverse order."""
+        L = self._L
+        P, x = lay.prev.size, lay.prev.outputs
+        # only a trainable preceding layer receives errors (LstmLayer.cu:991-992)
+        prev_err = lay.prev.outputErrors if lay.prev.trainable else None
+        if lay.type in ("lstm", "blstm"):
+            L.orc_lstm_backward(P, lay.size, int(lay.bidir), lay.bias, self.PS, self.maxT,
+                                self.T, self.Tmin, self.patTypes, lay.weights, x,
+                                lay.outputErrors, _ptr(prev_err), lay.weightUpdates, lay.bufs)
+        elif lay.type == "softmax":
+            L.orc_softmax_backward(P, lay.size, lay.bias, self.N, self.patTypes, lay.weights,
+                                   x, lay.outputs, lay.outputErrors, _ptr(prev_err),
+                                   lay.weightUpdates, lay.patTmp)
+        else:
+            L.orc_ff_backward(ACT[lay.type], P, lay.size, lay.bias, self.N, lay.weights,
+                              x, lay.outputs, lay.outputErrors, _ptr(prev_err),
+                              lay.weightUpdates)
 
     # -- SteepestDescentOptimizer::_updateWeights (SteepestDescentOptimizer.cu:67-94)
     def update_weights(self, learning_rate, momentum, deltas=None):
