@@ -328,7 +328,6 @@ struct cn_layer {
     // ... with a stride above 1 (section Strided context layers): the layer reads its predecessor in that layer's axis and owns
     // the axis it writes in and its followers run in
     int cx_stride = 1;
-    StrideArgs sx{};
     TimeAxis own_axis;
     // the time axis this layer's rows lie in: the context's base axis, or that of the nearest strided layer in front (or this one)
     TimeAxis *ax = nullptr;
@@ -1360,18 +1359,11 @@ void context_forward(cn_layer *l)
     const cn_layer *p = l->prev;
     Timed tm(c, KC_OTHER);
     const int *len = parent_lengths(l, "cn_layer_forward");
-    if (l->cx_stride > 1) {
-        StrideArgs &a = l->sx;
-        a.Tin = p->ax->T; a.Tout = ceil_div(p->ax->T, l->cx_stride); a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1;
-        a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp; a.S = l->cx_stride;
-        a.prev = unit_map(p);
-        form_axis(l, len);
-        launch_stride_fwd(c->stream, c->f32, a, len, follower_operand(p), l->out_op);
-        return;
-    }
     ContextArgs &a = l->cx;
-    a.T = l->ax->T; a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1; a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp;
+    a.Tin = p->ax->T; a.Tout = ceil_div(p->ax->T, l->cx_stride); a.PSp = c->PSp; a.B = l->cx_left + l->cx_right + 1;
+    a.left = l->cx_left; a.dil = l->cx_dil; a.Lp = l->Lp; a.S = l->cx_stride;
     a.prev = unit_map(p);
+    if (l->cx_stride > 1) form_axis(l, len);
     launch_context_fwd(c->stream, c->f32, a, len, follower_operand(p), l->out_op);
 }
 // behind the follower's K8 (and its mask / normalisation / skip term) on the main stream: the preceding layer's outputErrors.
@@ -1380,14 +1372,9 @@ void context_backward(cn_layer *l)
 {
     cn_ctx *c = l->ctx;
     if (!takes_err(l->prev)) return;
-    const char *stale = "cn_layer_backward: the context layer has no forward pass of the current fraction";
-    if (l->cx_stride > 1) {
-        if (l->sx.Tin != l->prev->ax->T || l->sx.PSp != c->PSp || l->own_axis.serial != c->frac_serial) throw cn_error(CN_ERR_STATE, stale);
-        Timed tm(c, KC_OTHER);
-        launch_stride_bwd(c->stream, l->sx, parent_lengths(l, "cn_layer_backward"), l->err, l->prev->err);
-        return;
-    }
-    if (l->cx.T != l->ax->T || l->cx.PSp != c->PSp) throw cn_error(CN_ERR_STATE, stale);
+    // (a plain layer lies in its predecessor's axis: l->ax->T == l->prev->ax->T there)
+    if (l->cx.Tin != l->prev->ax->T || l->cx.PSp != c->PSp || (l->cx_stride > 1 && l->own_axis.serial != c->frac_serial))
+        throw cn_error(CN_ERR_STATE, "cn_layer_backward: the context layer has no forward pass of the current fraction");
     Timed tm(c, KC_OTHER);
     launch_context_bwd(c->stream, l->cx, parent_lengths(l, "cn_layer_backward"), l->err, l->prev->err);
 }

@@ -351,34 +351,26 @@ struct ResArgs {
 void launch_residual_fwd(hipStream_t s, bool f32, const ResArgs &a, const char *pat, const void *branch, const void *x, void *sum);
 // prev_err[N][xLp] (fp32) += e[N][Lp] (fp32) on the rows with pat[row] != 0, unit by unit
 void launch_residual_bwd(hipStream_t s, const ResArgs &a, const char *pat, const float *e, float *prev_err);
-// ---- context layers (include/currennt_hip.h, section Context layers; cn_context.hip) ----
-// The geometry of one forward pass of one context layer: T time steps of PSp slots; B = left + right + 1 blocks of the preceding
-// layer's P = prev.L units in rows Lp = round_up(B * P, 32) wide, block b at columns [b * P, (b + 1) * P); xLp = prev.Lp below.
+// ---- context layers (include/currennt_hip.h, sections Context layers and Strided context layers; cn_context.hip) ----
+// The geometry of one forward pass of one context layer: it reads Tin steps of its predecessor's (the PARENT's) time axis and
+// writes Tout = ceil(Tin / S) steps of PSp slots; a plain layer has S = 1 and lies in the parent's axis (Tout == Tin), a layer
+// with S > 1 owns the axis it writes in.  B = left + right + 1 blocks of the preceding layer's P = prev.L units in rows
+// Lp = round_up(B * P, 32) wide, block b at columns [b * P, (b + 1) * P); xLp = prev.Lp below.  len[] below is always the parent
+// axis's (len_s); the kernels form n_s = ceil(len_s / S), the real frames of a slot in the layer's own axis, from it.
 struct ContextArgs {
-    int T, PSp, B, left, dil, Lp; UnitMap prev;
+    int Tin, Tout, PSp, B, left, dil, Lp, S; UnitMap prev;
 };
 // len[PSp]: the frames of every slot whose pattern type is not NONE, from pat[t * PSp + s], t < T (one wave per slot)
 void launch_context_lengths(hipStream_t s, const char *pat, int T, int PSp, int *len);
-// out[T * PSp][Lp] (op) gathered from x[T * PSp][xLp] (op), bits copied; rows t >= len[s] and pad columns are written as zeros
-void launch_context_fwd(hipStream_t s, bool f32, const ContextArgs &a, const int *len, const void *x, void *out);
-// dx[T * PSp][xLp] (fp32), every row and column written: the fold of e[T * PSp][Lp] (fp32) in the stated order, zeros elsewhere
-void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, const float *e, float *dx);
-// ---- strided context layers (include/currennt_hip.h, section Strided context layers; cn_context_stride.hip) ----
-// The geometry of one forward pass of one strided context layer: it reads Tin steps of its predecessor's time axis and writes
-// Tout = ceil(Tin / S) steps of its own; the other members as in ContextArgs.  len[] below is always the PARENT axis's (len_s);
-// the kernels form n_s = ceil(len_s / S) from it.
-struct StrideArgs {
-    int Tin, Tout, PSp, B, left, dil, Lp, S; UnitMap prev;
-};
-// The layer's own axis from the parent's, every row of Tout * PSp written: nlen[s] = n_s, the derived pattern types npat (FIRST /
-// NORMAL / LAST / NONE) and the classes ntcls[j][s] = tcls[S * j][s] for j < n_s, -1 elsewhere
+// S > 1: the layer's own axis from the parent's, every row of Tout * PSp written: nlen[s] = n_s, the derived pattern types npat
+// (FIRST / NORMAL / LAST / NONE) and the classes ntcls[j][s] = tcls[S * j][s] for j < n_s, -1 elsewhere
 void launch_stride_axis(hipStream_t s, int S, int Tout, int PSp, const int *len, const int *tcls, int *nlen, char *npat, int *ntcls);
 // tgt[Tout * PSp][W] = src[rate * j][s][..] for j < nlen[s], zero rows elsewhere (src at the base rate, rate = the product of the strides)
 void launch_stride_targets(hipStream_t s, int rate, int Tout, int PSp, int W, const int *nlen, const float *src, float *tgt);
 // out[Tout * PSp][Lp] (op) gathered from x[Tin * PSp][xLp] (op), bits copied; rows j >= n_s and pad columns are written as zeros
-void launch_stride_fwd(hipStream_t s, bool f32, const StrideArgs &a, const int *len, const void *x, void *out);
+void launch_context_fwd(hipStream_t s, bool f32, const ContextArgs &a, const int *len, const void *x, void *out);
 // dx[Tin * PSp][xLp] (fp32), every row and column written: the fold of e[Tout * PSp][Lp] (fp32) in the stated order, zeros elsewhere
-void launch_stride_bwd(hipStream_t s, const StrideArgs &a, const int *len, const float *e, float *dx);
+void launch_context_bwd(hipStream_t s, const ContextArgs &a, const int *len, const float *e, float *dx);
 // delta = act'(y) * err (in place on err, all N slots: FeedForwardLayer.cu:72-79), op copy for the GEMMs
 void launch_ff_delta(hipStream_t s, bool f32, int act, const float *y, float *err, void *delta_op, int N, int L, int Lp);
 // column sums of delta over the N slots (FeedForwardLayer.cu:82-102): colsum[j] += sum_n err[n][j]
