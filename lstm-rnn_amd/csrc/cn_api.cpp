@@ -1122,14 +1122,14 @@ void set_pack_update(PackGroup &grp, PackAdam &ad, PackDecayArgs &dk, int mode, 
     dk.ld[grp.n - 1] = decay_ld(it.lr, r.decay);
     if (r.adam) {
         const AdamScalars a = adam_scalars(r, it.lr);
-        it.optimizer = PACK_OPT_ADAM; it.lr = a.alpha_t; it.mom = a.b1;
+        it.lr = a.alpha_t; it.mom = a.b1;
         ad.v[grp.n - 1] = l->ctx->adam_v + l->woff; ad.b2 = a.b2; ad.omb1 = a.omb1; ad.omb2 = a.omb2; ad.eps_t = a.eps_t;
     }
 }
 // One layer's weight update + operand copies as one launch of the grouped pack kernel on `st`.
 // mode 1: gradient from the flat weightUpdates; mode 2: from the packed accumulators (unpack fused in, cn_elementwise.hip)
 // folds (mode 2, deterministic mode; nullable): f_in, f_rec[0], f_rec[1], f_bias -- the partial sums the launch adds itself
-// r: the optimizer's rule (the armed one, or the completing call's): its kind selects the instantiation (PackItem::optimizer)
+// r: the optimizer's rule (the armed one, or the completing call's): its kind and its decay select the instantiation
 void launch_layer_update(hipStream_t st, cn_layer *l, int mode, const UpdateRule &r, hipEvent_t done, const PackFold *folds = nullptr)
 {
     cn_ctx *c = l->ctx;
@@ -3165,24 +3165,20 @@ static void begin_update(cn_ctx *c, const UpdateRule &r, const char *fn)
                                                           : ": learning rate / momentum differ from what cn_ctx_arm_update armed and applied"));
 }
 // the flat forms: momentum SGD or Adam over a range of the arena that starts `off` floats in, at rate lr
-// clip: the record of the step's norm (clip_record below), or null with clipping off -- then the launches are the ones they were
+// clip: the record of the step's norm (clip_record below), or null with clipping off
 // decayed (with r.decay on; then the range is ONE layer's): the runs of the range that decay (decay_ranges)
 static void launch_flat(cn_ctx *c, const UpdateRule &r, size_t off, size_t n, float lr, const ClipRecord *clip, hipEvent_t done = nullptr,
                         const DecayRanges *decayed = nullptr)
 {
-    float *w = c->arena + off, *wu = w + c->total, *wd = w + 2 * c->total;
     if (r.lamb) throw cn_error(CN_ERR_STATE, "launch_flat: LAMB steps go by layers (launch_lamb_layers)");
-    if (r.decay != 0.f) {
-        if (!decayed) throw cn_error(CN_ERR_STATE, "launch_flat: weight decay needs a layer's range");
-        if (r.adam) launch_adam_decay(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), decay_ld(lr, r.decay), *decayed, clip, done);
-        else        launch_sgd_decay(c->stream, w, wu, wd, n, lr, r.mom, decay_ld(lr, r.decay), *decayed, clip, done);
-    }
-    else if (clip) {
-        if (r.adam) launch_adam_clip(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), clip, done);
-        else        launch_sgd_clip(c->stream, w, wu, wd, n, lr, r.mom, clip, done);
-    }
-    else if (r.adam) launch_adam(c->stream, w, wu, wd, c->adam_v + off, n, adam_scalars(r, lr), done);
-    else             launch_sgd(c->stream, w, wu, wd, n, lr, r.mom, done);
+    if (r.decay != 0.f && !decayed) throw cn_error(CN_ERR_STATE, "launch_flat: weight decay needs a layer's range");
+    float *w = c->arena + off;
+    const FlatUpdate u{w, w + c->total, w + 2 * c->total, n, lr, r.mom};
+    FlatAdam ad{};
+    FlatDecay dk{};
+    if (r.adam) ad = FlatAdam{c->adam_v + off, adam_scalars(r, lr)};
+    if (r.decay != 0.f) dk = FlatDecay{decay_ld(lr, r.decay), *decayed};
+    launch_flat_update(c->stream, u, r.adam ? &ad : nullptr, clip, r.decay != 0.f ? &dk : nullptr, done);
 }
 // Behind begin_update (the main stream is ordered behind the side streams' gradient work and the reductions): the record the
 // update launches of this step read, or null with clipping off.  The norm is formed once per gradient: by the first update call

@@ -8,15 +8,18 @@
 //   layers/SoftmaxLayer.cu:162-219     error offset / errors     -> softmax_bwd_kernel (one pass)
 //   layers/MulticlassClassificationLayer.cu:48-135               -> mcc_rows_kernel, mcc_backward_kernel
 //   layers/SsePostOutputLayer.cu:39-88 and the other post output layers -> post_rows_kernel, post_backward_kernel
-//   optimizers/SteepestDescentOptimizer.cu:39-59 UpdateWeightFn  -> sgd_kernel
-//   (no counterpart in the reference) the Adam step of include/currennt_hip.h -> adam_kernel, pack_group_adam_kernel
+//   optimizers/SteepestDescentOptimizer.cu:39-59 UpdateWeightFn  -> sgd_step, in flat_update_kernel and pack_group_kernel
+//   (no counterpart in the reference) the Adam step, gradient clipping and weight decay of include/currennt_hip.h
+//                                                                -> adam_step, clip_scaled, decayed, in the same two kernels
 //   (no counterpart in the reference) dropout on a layer's input, include/currennt_hip.h -> dropout_fwd_kernel, dropout_bwd_kernel
 //   optimizers/Optimizer.cu:58-84 weight noise, drawn on the device (include/currennt_hip.h, section Weight noise) -> pack_group_noise_kernel
 #include "cn_internal.h"
 #include "cn_philox_device.h"
 
 #include <float.h>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 namespace cn {
 
@@ -31,37 +34,95 @@ template <bool F32> __device__ __forceinline__ void st_op(void *base, long idx, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// LSTM weight packing (flat layout: LstmLayer.hpp:36-55, LstmLayer.cu:535-541,583-596)
+// the weight update, stated once
 // ---------------------------------------------------------------------------------------------
-// The weight at flat index fi as the operand copies should see it: as stored, or (upd) after the momentum-SGD step, which this
-// thread then also writes back (same arithmetic as sgd_kernel: separate multiplies and adds, no contraction).
-// UPD = 2: the gradient of this weight is still in its PACKED accumulator `gp` (scaled by gscale: the bias gradient of a
-// feed-forward layer is bias * column sum, FeedForwardLayer.cu:94-100): it is read, cleared for the next backward pass and
-// written to the flat weightUpdates on the way (what lstm_unpack_kernel / ff_unpack_kernel do in the unfused sequence).
-struct PackUpd { float *w_rw; const float *wu; float *wd; float lr, mom; float *wu_rw; };
-// The Adam forms (a type of their own: pack_fetch and the pack bodies are instantiated a second time for it and the SGD
-// instantiations keep their code): wd holds the first moments, lr alpha_t, mom beta1
-struct PackUpdAdam : PackUpd { float *v; float b2, omb1, omb2, eps_t; };
-// One weight's update from its gradient g.  Adam as stated in include/currennt_hip.h (cn_adam_update), every operation rounded
-// on its own like the SGD step's: m = b1*m + omb1*g; v = b2*v + omb2*(g*g); w = w - (alpha_t*m) / (sqrt(v) + eps_t)
-__device__ __forceinline__ float adam_step(float w, float g, float *m, float *v, float b1, float omb1, float b2, float omb2, float alpha_t, float eps_t)
+// Every kernel of this file that changes a weight -- flat_update_kernel and pack_group_kernel, every
+// instantiation -- does it through these four statements; each operation is an fp32 operation rounded on its own, so that equal
+// gradients give bit-equal weights on every path (cn_lamb.hip's direction is LAMB's own rule, stated there the same way).
+// What keeps the operations apart is "#pragma clang fp contract(off)".  hipcc's __fmul_rn / __fadd_rn / __fsub_rn are the plain
+// operators and promise nothing: under the compiler's default (-ffp-contract=fast-honor-pragmas) the backend may fuse a product
+// into the sum that reads it, and it did make one v_fma_f32 of w - ld * w when decayed() was written with them.  In the gfx950
+// assembly of these statements the SGD step is v_pk_mul_f32 (or two v_mul_f32), v_sub_f32, v_add_f32 and the Adam step has
+// separate multiplies and adds; the only v_fma / v_fmac are inside the square root and division sequences (and the index
+// divisions of the pack bodies).  The pragma is what guarantees that; the observation only confirms it.
+// g' = scale * g of a CLIP_SCALE step (include/currennt_hip.h, section Gradient clipping)
+__device__ __forceinline__ float clip_scaled(float scale, float g)
 {
-    const float mn = __fadd_rn(__fmul_rn(b1, *m), __fmul_rn(omb1, g));
-    const float vn = __fadd_rn(__fmul_rn(b2, *v), __fmul_rn(omb2, __fmul_rn(g, g)));
+#pragma clang fp contract(off)
+    return scale * g;
+}
+// w0 = w - ld * w (include/currennt_hip.h, section Weight decay); the rule's step then starts from w0 (StepFrom)
+__device__ __forceinline__ float decayed(float w, float ld)
+{
+#pragma clang fp contract(off)
+    const float p = ld * w;
+    return w - p;
+}
+// Where a step starts: the weight at *w, or (dec) decayed() of it
+struct StepFrom { const float *w; bool dec; float ld; };
+__device__ __forceinline__ float start_weight(const StepFrom &s)
+{
+    const float w = *s.w;
+    return s.dec ? decayed(w, s.ld) : w;
+}
+// momentum SGD (SteepestDescentOptimizer.cu:39-59 UpdateWeightFn): d = mom * d - lr * g (:51); w = w0 + d (:55)
+// (the weight is read behind the store of d, as the functor reads it: the loop of the plain flat kernel holds one value less)
+__device__ __forceinline__ float sgd_step(const StepFrom &w0, float g, float *d, float lr, float mom)
+{
+#pragma clang fp contract(off)
+    const float a = mom * *d, b = lr * g;
+    const float dl = a - b;
+    *d = dl;
+    return start_weight(w0) + dl;
+}
+// Adam as stated in include/currennt_hip.h (cn_adam_update): m = b1*m + omb1*g; v = b2*v + omb2*(g*g); w = w0 - (alpha_t*m) / (sqrt(v) + eps_t)
+__device__ __forceinline__ float adam_step(const StepFrom &w0, float g, float *m, float *v, float b1, float omb1, float b2, float omb2, float alpha_t, float eps_t)
+{
+#pragma clang fp contract(off)
+    const float w = start_weight(w0);
+    const float m1 = b1 * *m, m2 = omb1 * g;
+    const float mn = m1 + m2;
+    const float gg = g * g;
+    const float v1 = b2 * *v, v2 = omb2 * gg;
+    const float vn = v1 + v2;
     *m = mn; *v = vn;
+    const float num = alpha_t * mn;
     // (sqrtf, not __fsqrt_rn: hipcc's __fsqrt_rn is the NATIVE square root, v_sqrt_f32 alone, 1 ulp; sqrtf compiles to the correctly
     // rounded sequence -- v_sqrt_f32 and a residual step -- as long as no fast-math flag is given, and csrc/Makefile gives none)
-    return __fsub_rn(w, __fdiv_rn(__fmul_rn(alpha_t, mn), __fadd_rn(sqrtf(vn), eps_t)));
+    const float den = sqrtf(vn) + eps_t;
+    const float q = __fdiv_rn(num, den);
+    return w - q;
 }
-__device__ __forceinline__ float apply_update(const PackUpd &u, long fi, float g)
+// A feature of an update kernel that is off is an argument (or a base) of an empty type: no bytes to speak of in the kernel
+// argument, and with `if constexpr` on the same flag no code -- the plain SGD instantiations carry nothing of Adam, clipping or decay.
+template <class T> struct Off {};
+template <bool ON, class T> using Opt = typename std::conditional<ON, T, Off<T>>::type;
+template <bool ON, class T> static Opt<ON, T> opt_arg(const T *p)
 {
-    const float dl = __fsub_rn(__fmul_rn(u.mom, u.wd[fi]), __fmul_rn(u.lr, g));          // SteepestDescentOptimizer.cu:51
-    u.wd[fi] = dl;
-    return __fadd_rn(u.w_rw[fi], dl);                                                     // :55
+    if constexpr (ON) return *p; else return {};
 }
-__device__ __forceinline__ float apply_update(const PackUpdAdam &u, long fi, float g)
+
+// ---------------------------------------------------------------------------------------------
+// LSTM weight packing (flat layout: LstmLayer.hpp:36-55, LstmLayer.cu:535-541,583-596)
+// ---------------------------------------------------------------------------------------------
+// The rule of a grouped launch as the pack bodies see it: where the step reads and writes (wu_rw: the flat weightUpdates an
+// armed update writes on the way), momentum SGD's scalars, and a part per feature that is on.  Adam: wd holds the first moments,
+// lr alpha_t, mom beta1, and PackAdamPart the rest; clipping: the record of grad_norm_kernel; decay: the layer's ld = lr * decay.
+struct PackUpd { float *w_rw; const float *wu; float *wd; float lr, mom; float *wu_rw; };
+struct PackAdamPart { float *v; float b2, omb1, omb2, eps_t; };
+struct PackClipPart { float scale; int state; };
+struct PackDecayPart { float ld; };
+template <bool ADAM, bool CLIP, bool DECAY>
+struct PackRule : PackUpd, Opt<ADAM, PackAdamPart>, Opt<CLIP, PackClipPart>, Opt<DECAY, PackDecayPart> {};
+// One weight's step from its gradient g.  DEC: the index lies in a block that decays -- the input and recurrent weights do, the
+// bias and peephole weights do not (known where the pack bodies fetch it)
+template <bool DEC, bool ADAM, bool CLIP, bool DECAY>
+__device__ __forceinline__ float pack_apply(const PackRule<ADAM, CLIP, DECAY> &u, long fi, float g)
 {
-    return adam_step(u.w_rw[fi], g, u.wd + fi, u.v + fi, u.mom, u.omb1, u.b2, u.omb2, u.lr, u.eps_t);
+    StepFrom w{u.w_rw + fi, false, 0.f};
+    if constexpr (DEC && DECAY) { w.dec = true; w.ld = u.ld; }
+    if constexpr (ADAM) return adam_step(w, g, u.wd + fi, u.v + fi, u.mom, u.omb1, u.b2, u.omb2, u.lr, u.eps_t);
+    else return sgd_step(w, g, u.wd + fi, u.lr, u.mom);
 }
 // deterministic mode: the partial sums of this entry, added in order -- ((p0 + p1) + p2) + ..., exactly fold_kernel's sum
 // (sixteen loads in flight per batch: the bias / peephole sums have one partial per backward workgroup -- 52 on the headline --
@@ -85,72 +146,8 @@ __device__ __forceinline__ float pack_fold(const PackFold &f, long off)
     }
     return t;
 }
-// Clipping on (UPD = 4, include/currennt_hip.h, section Gradient clipping): an update rule with the record of grad_norm_kernel in
-// front of it.  Types and an UPD of their own: the forms without it are instantiated as before.
-template <class B> struct PackClip : B { float scale; int state; };
-// Weight decay on (include/currennt_hip.h, section Weight decay): an update rule with the layer's ld = lr * decay in front of it.
-// A type of its own again, around the plain rule or the clipped one: the forms without it are instantiated as before.  Which block
-// an index lies in is known where the pack bodies fetch it (DEC of pack_fetch): the input and recurrent weights decay, the bias
-// and peephole weights do not and take the plain step.
-template <class B> struct PackDecay : B { float ld; };
-template <class U> struct pack_decays { static constexpr bool value = false; };
-template <class B> struct pack_decays<PackDecay<B>> { static constexpr bool value = true; };
-// w0 = w - ld * w, two operations rounded on their own; then the family's step from w0.
-// (hipcc's __fmul_rn / __fsub_rn are the plain operators, and the compiler's default lets the backend contract a product into the
-// sum that reads it: it made one v_fma_f32 of w - ld * w.  The decay forms state their arithmetic under "contract(off)", which
-// the default -- fast-honor-pragmas -- honours; the family's step is restated here for the same reason, operation by operation
-// as apply_update and adam_step state it.)
-__device__ __forceinline__ float decayed(float w, float ld)
-{
-#pragma clang fp contract(off)
-    const float p = ld * w;
-    return w - p;
-}
-__device__ __forceinline__ float sgd_delta_exact(float mom, float d, float lr, float g)
-{
-#pragma clang fp contract(off)
-    const float a = mom * d, b = lr * g;
-    return a - b;
-}
-__device__ __forceinline__ float sum_exact(float a, float b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float adam_step_exact(float w, float g, float *m, float *v, float b1, float omb1, float b2, float omb2, float alpha_t, float eps_t)
-{
-#pragma clang fp contract(off)
-    const float m1 = b1 * *m, m2 = omb1 * g;
-    const float mn = m1 + m2;
-    const float gg = g * g;
-    const float v1 = b2 * *v, v2 = omb2 * gg;
-    const float vn = v1 + v2;
-    *m = mn; *v = vn;
-    const float num = alpha_t * mn;
-    const float den = sqrtf(vn) + eps_t;
-    const float q = __fdiv_rn(num, den);
-    return w - q;
-}
-// (DEC: the entry decays; an exempt entry takes the same restated step from w itself)
-template <bool DEC> __device__ __forceinline__ float apply_update_decay(const PackUpd &u, long fi, float g, float ld)
-{
-    const float dl = sgd_delta_exact(u.mom, u.wd[fi], u.lr, g);
-    u.wd[fi] = dl;
-    const float w = u.w_rw[fi];
-    return sum_exact(DEC ? decayed(w, ld) : w, dl);
-}
-template <bool DEC> __device__ __forceinline__ float apply_update_decay(const PackUpdAdam &u, long fi, float g, float ld)
-{
-    const float w = u.w_rw[fi];
-    return adam_step_exact(DEC ? decayed(w, ld) : w, g, u.wd + fi, u.v + fi, u.mom, u.omb1, u.b2, u.omb2, u.lr, u.eps_t);
-}
-template <bool DEC, class U> __device__ __forceinline__ float pack_apply(const U &u, long fi, float g)
-{
-    if constexpr (pack_decays<U>::value) return apply_update_decay<DEC>(u, fi, g, u.ld);
-    else return apply_update(u, fi, g);
-}
 // Weight noise (UPD = 5, include/currennt_hip.h, section Weight noise): the fetch returns w + n(fi), and the bodies write the
-// copies a backward pass reads only.  A type and an UPD of their own again.
+// copies a backward pass reads only.
 // (philox4x32_10 and the Box-Muller step gauss_noise: cn_philox_device.h)
 struct PackNoiseKey { uint32_t k0, k1, pass_lo, pass_hi; float sigma; };
 __device__ __forceinline__ float weight_noise(const PackNoiseKey &u, long k)
@@ -158,24 +155,32 @@ __device__ __forceinline__ float weight_noise(const PackNoiseKey &u, long k)
     const uint4 w = philox4x32_10(make_uint4((uint32_t)(k >> 2), 0u, u.pass_lo, u.pass_hi), u.k0, u.k1);
     return gauss_noise(w, k, u.sigma);
 }
-// (DEC: the index lies in a block that decays -- it matters to the PackDecay forms only)
+// The weight at flat index fi as the operand copies should see it: as stored (UPD = 0), with noise (UPD = 5), or after the rule's
+// step, which this thread then also writes back.  Where the step's gradient comes from:
+// UPD = 1: the flat weightUpdates.
+// UPD = 2: the gradient of this weight is still in its PACKED accumulator `gp` (scaled by gscale: the bias gradient of a
+// feed-forward layer is bias * column sum, FeedForwardLayer.cu:94-100): it is read, cleared for the next backward pass and
+// written to the flat weightUpdates on the way (what lstm_unpack_kernel / ff_unpack_kernel do in the unfused sequence).
+// UPD = 3: deterministic mode: this launch adds the stored partial sums itself (a variant of its own: with the loop inside the
+// UPD = 2 code every launch of the default mode paid ~11 us for it); the packed accumulator itself was never written.
+// UPD = 4: as UPD = 1 behind the clipping record: scaled, or the step skipped (the operand copies are still written, from the
+// unchanged weight).
+// (DEC: the index lies in a block that decays -- it matters to the rules with decay on only)
 template <int UPD, bool DEC = true, class U>
 __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi, float *gp = nullptr, float gscale = 1.0f,
                                             const PackFold *fold = nullptr, long foff = 0)
 {
     if constexpr (UPD == 5) return __fadd_rn(w[fi], weight_noise(u, fi));
-    else if constexpr (UPD == 4) {         // the gradient from the flat weightUpdates (as UPD = 1), scaled or the step skipped
-        if (u.state == CLIP_SKIP) return u.w_rw[fi];          // (the operand copies are still written, from the unchanged weight)
-        float g = u.wu[fi];
-        if (u.state == CLIP_SCALE) g = __fmul_rn(u.scale, g);
-        const float v = pack_apply<DEC>(u, fi, g);
-        u.w_rw[fi] = v;
-        return v;
-    } else if constexpr (UPD != 0) {
+    else if constexpr (UPD == 0) return w[fi];
+    else {
         float g;
-        if constexpr (UPD == 3) {          // deterministic mode: this launch adds the stored partial sums itself (a variant of its own:
-            if (fold->nparts) g = pack_fold(*fold, foff);        // with the loop inside the UPD = 2 code every launch of the default mode
-            else { g = *gp; *gp = 0.f; }                          // paid ~11 us for it); the packed accumulator itself was never written
+        if constexpr (UPD == 4) {
+            if (u.state == CLIP_SKIP) return u.w_rw[fi];
+            g = u.wu[fi];
+            if (u.state == CLIP_SCALE) g = clip_scaled(u.scale, g);
+        } else if constexpr (UPD == 3) {
+            if (fold->nparts) g = pack_fold(*fold, foff);
+            else { g = *gp; *gp = 0.f; }
             if (gscale != 1.0f) g = __fmul_rn(gscale, g);
             u.wu_rw[fi] = g;
         } else if constexpr (UPD == 2) { g = *gp; *gp = 0.f; if (gscale != 1.0f) g = __fmul_rn(gscale, g); u.wu_rw[fi] = g; }
@@ -183,7 +188,7 @@ __device__ __forceinline__ float pack_fetch(const float *w, const U &u, long fi,
         const float v = pack_apply<DEC>(u, fi, g);
         u.w_rw[fi] = v;
         return v;
-    } else return w[fi];
+    }
 }
 struct PackGrad { float *g_in, *g_rec, *g_bias, *g_peep; PackFold f_in, f_rec[2], f_bias; };
 
@@ -322,127 +327,53 @@ __global__ void ff_pack_kernel(FfGeom g, float bias, const float *w, void *W, vo
 
 // Every trainable layer's operand copies in ONE launch (after cn_sgd_update_all): four launches of 4-9 us each were
 // either on the critical path (the first layer's) or cost a fork event, a side stream and a wait (the others').
-template <bool F32>
-__global__ void pack_group_kernel(PackGroup grp)
+// The item that owns this workgroup, and the workgroups [first, first + count) of the launch that work on it
+struct PackWork { int i, first, count; };
+__device__ __forceinline__ PackWork pack_work(const PackGroup &grp)
 {
     int i = 0;
 #pragma unroll
     for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) i = k;
-    const PackItem it = grp.item[i];     // (a copy: through a reference into the argument struct hipcc re-loads fields inside the loops)
-    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
-    if (it.update) {      // cn_sgd_update_all: the weight update rides on the pack (one launch instead of two on the critical tail)
-        const PackUpd upd{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
-        if (it.update == 2) {   // armed update: ... and so does the unpacking of the gradient
-            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}};
-            if (it.lstm) lstm_pack_body<F32, 2>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-            else         ff_pack_body<F32, 2>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-            return;
-        }
-        if (it.update == 3) {   // ... in deterministic mode, from the partial sums the producers stored (PackFold)
-            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias};
-            if (it.lstm) lstm_pack_body<F32, 3>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-            else         ff_pack_body<F32, 3>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-            return;
-        }
-        if (it.lstm) lstm_pack_body<F32, 1>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-        else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-        return;
-    }
-    if (it.lstm) lstm_pack_body<F32>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count);
-    else         ff_pack_body<F32>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count);
+    return {i, grp.first[i], (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i]};
 }
-// The Adam forms of the three update modes: the same bodies instantiated for PackUpdAdam.  A kernel of its own, so that
-// pack_group_kernel -- the tail of the SGD step -- does not carry their registers or their code.
-template <bool F32>
-__global__ void pack_group_adam_kernel(PackGroup grp, PackAdam ad)
+// ... and item i's entry of a per-item array of a feature's argument (no dynamic index into the argument: it would go through scratch)
+template <class T> __device__ __forceinline__ T pack_pick(const T (&a)[PACK_GROUP_MAX], int i)
 {
-    int i = 0;
+    T x = a[0];
 #pragma unroll
-    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) i = k;
-    const PackItem it = grp.item[i];
-    float *v = ad.v[0];
-#pragma unroll
-    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k == i) v = ad.v[k];           // (no dynamic index into the argument: it would go through scratch)
-    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
-    const PackUpdAdam upd{{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw}, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t};
-    if (it.update == 2) {
-        const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}};
-        if (it.lstm) lstm_pack_body<F32, 2>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-        else         ff_pack_body<F32, 2>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-    } else if (it.update == 3) {
-        const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias};
-        if (it.lstm) lstm_pack_body<F32, 3>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-        else         ff_pack_body<F32, 3>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-    } else {
-        if (it.lstm) lstm_pack_body<F32, 1>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-        else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-    }
+    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k == i) x = a[k];
+    return x;
 }
-// ... and of update mode 1 with clipping on: the record is read once per workgroup (the norm launch is in front on the stream)
-template <bool F32, bool ADAM>
-__global__ void pack_group_clip_kernel(PackGroup grp, PackAdam ad, const ClipRecord *rec)
+// One item's pack body for fetch mode UPD under rule upd: the layer kind picks the body
+template <bool F32, int UPD, class U>
+__device__ __forceinline__ void run_item(const PackItem &it, const PackWork &wk, const U &upd, const PackGrad &pg = PackGrad{})
 {
-    int i = 0;
-#pragma unroll
-    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) i = k;
-    const PackItem it = grp.item[i];
-    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
-    const float scale = rec->scale; const int state = rec->state;
-    const PackUpd base{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
-    if constexpr (ADAM) {
-        float *v = ad.v[0];
-#pragma unroll
-        for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k == i) v = ad.v[k];
-        const PackClip<PackUpdAdam> upd{{base, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t}, scale, state};
-        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-    } else {
-        const PackClip<PackUpd> upd{base, scale, state};
-        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-    }
+    if (it.lstm) lstm_pack_body<F32, UPD>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, wk.first, wk.count, upd, pg);
+    else         ff_pack_body<F32, UPD>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, wk.first, wk.count, upd, pg);
 }
-// ... and of every update mode with weight decay on (CLIP: mode 1 behind the record, as pack_group_clip_kernel): item i's
-// ld = lr_layer * decay comes in an argument of its own, so that PackItem and the instantiations above stay as they are
-template <bool F32, bool ADAM, bool CLIP>
-__global__ void pack_group_decay_kernel(PackGroup grp, PackAdam ad, PackDecayArgs dk, const ClipRecord *rec)
+// The weight update rides on the pack (cn_sgd_update_all: one launch instead of two on the critical tail), under momentum SGD or
+// Adam, behind the clipping record (CLIP: update mode 1 only; the record is read once per workgroup, the norm launch is in front
+// on the stream) and with weight decay.  The flags are compile-time: <F32, false, false, false> -- the tail of the SGD step -- does
+// not carry the other forms' registers or code, and it alone also takes the items without an update.
+template <bool F32, bool ADAM, bool CLIP, bool DECAY>
+__global__ void pack_group_kernel(PackGroup grp, Opt<ADAM, PackAdam> ad, Opt<CLIP, const ClipRecord *> rec, Opt<DECAY, PackDecayArgs> dk)
 {
-    int i = 0;
-    float ld = dk.ld[0];
-    float *v = ad.v[0];
-#pragma unroll
-    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) { i = k; ld = dk.ld[k]; v = ad.v[k]; }
-    const PackItem it = grp.item[i];
-    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
-    const PackUpd base{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
-    using Rule = typename std::conditional<ADAM, PackUpdAdam, PackUpd>::type;
-    Rule rule;
-    if constexpr (ADAM) rule = PackUpdAdam{base, v, ad.b2, ad.omb1, ad.omb2, ad.eps_t}; else rule = base;
-    if constexpr (CLIP) {
-        const PackDecay<PackClip<Rule>> upd{{rule, rec->scale, rec->state}, ld};
-        if (it.lstm) lstm_pack_body<F32, 4>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-        else         ff_pack_body<F32, 4>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-    } else {
-        const PackDecay<Rule> upd{rule, ld};
-        if (it.update == 2) {
-            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}};
-            if (it.lstm) lstm_pack_body<F32, 2>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-            else         ff_pack_body<F32, 2>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-        } else if (it.update == 3) {
-            const PackGrad pg{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias};
-            if (it.lstm) lstm_pack_body<F32, 3>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd, pg);
-            else         ff_pack_body<F32, 3>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd, pg);
-        } else {
-            if (it.lstm) lstm_pack_body<F32, 1>(it.lg, it.bias, it.w, it.Win, it.WinT, it.Wrec, it.WrecT, it.bias_p, it.peep_p, grp.first[i], count, upd);
-            else         ff_pack_body<F32, 1>(it.fg, it.bias, it.w, it.Win, it.WinT, it.bias_p, grp.first[i], count, upd);
-        }
+    const PackWork wk = pack_work(grp);
+    const PackItem it = grp.item[wk.i];  // (a copy: through a reference into the argument struct hipcc re-loads fields inside the loops)
+    if constexpr (!ADAM && !CLIP && !DECAY) {
+        if (!it.update) { run_item<F32, 0>(it, wk, PackUpd{}); return; }
     }
-}
-template <bool F32, bool ADAM>
-static void launch_pack_group_decay(hipStream_t s, int blocks, hipEvent_t done, const PackGroup &grp, const PackAdam &a, const PackDecayArgs &dk, const ClipRecord *clip)
-{
-    if (clip) hipExtLaunchKernelGGL((pack_group_decay_kernel<F32, ADAM, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, dk, clip);
-    else      hipExtLaunchKernelGGL((pack_group_decay_kernel<F32, ADAM, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, dk, clip);
+    PackRule<ADAM, CLIP, DECAY> upd;
+    static_cast<PackUpd &>(upd) = PackUpd{it.w_rw, it.wu, it.wd, it.lr, it.mom, it.wu_rw};
+    if constexpr (ADAM) static_cast<PackAdamPart &>(upd) = PackAdamPart{pack_pick(ad.v, wk.i), ad.b2, ad.omb1, ad.omb2, ad.eps_t};
+    if constexpr (CLIP) { upd.scale = rec->scale; upd.state = rec->state; }
+    if constexpr (DECAY) upd.ld = pack_pick(dk.ld, wk.i);
+    if constexpr (CLIP) run_item<F32, 4>(it, wk, upd);
+    else if (it.update == 2)    // armed update: ... and so does the unpacking of the gradient
+        run_item<F32, 2>(it, wk, upd, PackGrad{it.g_in, it.g_rec, it.g_bias, it.g_peep, {}, {{}, {}}, {}});
+    else if (it.update == 3)    // ... in deterministic mode, from the partial sums the producers stored (PackFold)
+        run_item<F32, 3>(it, wk, upd, PackGrad{it.g_in, it.g_rec, it.g_bias, it.g_peep, it.f_in, {it.f_rec[0], it.f_rec[1]}, it.f_bias});
+    else run_item<F32, 1>(it, wk, upd);
 }
 // the grid of a grouped launch: item i's workgroups are [grp.first[i], grp.first[i + 1]), one thread per packed entry up to 1024 groups
 static int pack_group_blocks(PackGroup &grp)
@@ -457,51 +388,33 @@ static int pack_group_blocks(PackGroup &grp)
     }
     return blocks;
 }
+typedef void (*PackGroupLaunch)(hipStream_t, int, hipEvent_t, const PackGroup &, const PackAdam *, const ClipRecord *, const PackDecayArgs *);
+template <bool F32, bool ADAM, bool CLIP, bool DECAY>
+static void launch_pack_group_as(hipStream_t s, int blocks, hipEvent_t done, const PackGroup &grp, const PackAdam *adam, const ClipRecord *clip, const PackDecayArgs *decay)
+{
+    hipExtLaunchKernelGGL((pack_group_kernel<F32, ADAM, CLIP, DECAY>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp,
+                          opt_arg<ADAM>(adam), opt_arg<CLIP>(&clip), opt_arg<DECAY>(decay));
+}
+// entry 8 * f32 + 4 * adam + 2 * clip + decay
+template <size_t... I> static constexpr std::array<PackGroupLaunch, sizeof...(I)> pack_group_table(std::index_sequence<I...>)
+{
+    return {{&launch_pack_group_as<(I >> 3 & 1) != 0, (I >> 2 & 1) != 0, (I >> 1 & 1) != 0, (I & 1) != 0>...}};
+}
 void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done, const PackAdam *adam, const ClipRecord *clip, const PackDecayArgs *decay)
 {
+    static constexpr auto table = pack_group_table(std::make_index_sequence<16>{});
     const int blocks = pack_group_blocks(grp);
     if (blocks == 0) return;
-    if (decay) {
-        const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
-        const PackAdam a = ad ? *adam : PackAdam{};
-        if (ad) { if (f32) launch_pack_group_decay<true, true>(s, blocks, done, grp, a, *decay, clip); else launch_pack_group_decay<false, true>(s, blocks, done, grp, a, *decay, clip); }
-        else    { if (f32) launch_pack_group_decay<true, false>(s, blocks, done, grp, a, *decay, clip); else launch_pack_group_decay<false, false>(s, blocks, done, grp, a, *decay, clip); }
-        return;
-    }
-    if (clip) {
-        const bool ad = grp.item[0].optimizer == PACK_OPT_ADAM;
-        const PackAdam a = ad ? *adam : PackAdam{};
-        if (ad) {
-            if (f32) hipExtLaunchKernelGGL((pack_group_clip_kernel<true, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
-            else     hipExtLaunchKernelGGL((pack_group_clip_kernel<false, true>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
-        } else {
-            if (f32) hipExtLaunchKernelGGL((pack_group_clip_kernel<true, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
-            else     hipExtLaunchKernelGGL((pack_group_clip_kernel<false, false>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, a, clip);
-        }
-        return;
-    }
-    if (grp.item[0].optimizer == PACK_OPT_ADAM) {
-        if (f32) hipExtLaunchKernelGGL(pack_group_adam_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
-        else     hipExtLaunchKernelGGL(pack_group_adam_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp, *adam);
-        return;
-    }
-    if (f32) hipExtLaunchKernelGGL(pack_group_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
-    else     hipExtLaunchKernelGGL(pack_group_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, grp);
+    table[8 * f32 + 4 * (adam != nullptr) + 2 * (clip != nullptr) + (decay != nullptr)](s, blocks, done, grp, adam, clip, decay);
 }
-// Weight noise: the NOISY set of the copies a backward pass reads (items' WinT / WrecT / peep_p point there; Win, Wrec and bias_p
-// are not written), every layer of the group in one launch, each with its own key word 0 (seed + ordinal).
+// Weight noise: the NOISY set of the copies a backward pass reads (items' WinT / WrecT / peep_p point there; with UPD = 5 the
+// bodies write nothing else), every layer of the group in one launch, each with its own key word 0 (seed + ordinal).
 template <bool F32>
 __global__ void pack_group_noise_kernel(PackGroup grp, PackNoise nz)
 {
-    int i = 0;
-    uint32_t k0 = nz.k0[0];
-#pragma unroll
-    for (int k = 1; k < PACK_GROUP_MAX; ++k) if (k < grp.n && (int)blockIdx.x >= grp.first[k]) { i = k; k0 = nz.k0[k]; }
-    const PackItem it = grp.item[i];
-    const int count = (i + 1 < grp.n ? grp.first[i + 1] : (int)gridDim.x) - grp.first[i];
-    const PackNoiseKey key{k0, nz.k1, nz.pass_lo, nz.pass_hi, nz.sigma};
-    if (it.lstm) lstm_pack_body<F32, 5>(it.lg, it.bias, it.w, nullptr, it.WinT, nullptr, it.WrecT, nullptr, it.peep_p, grp.first[i], count, key);
-    else         ff_pack_body<F32, 5>(it.fg, it.bias, it.w, nullptr, it.WinT, nullptr, grp.first[i], count, key);
+    const PackWork wk = pack_work(grp);
+    const PackItem it = grp.item[wk.i];
+    run_item<F32, 5>(it, wk, PackNoiseKey{pack_pick(nz.k0, wk.i), nz.k1, nz.pass_lo, nz.pass_hi, nz.sigma});
 }
 void launch_pack_group_noise(hipStream_t s, bool f32, PackGroup &grp, const PackNoise &nz)
 {
@@ -1694,7 +1607,7 @@ void launch_classes_to_targets(hipStream_t s, const int *tcls, float *tgt, int N
 }
 
 // ---------------------------------------------------------------------------------------------
-// optimizer step
+// gradient exchange test doubles, batch-learning sum (the optimizer step itself: flat_update_kernel at the end of the file)
 // ---------------------------------------------------------------------------------------------
 // x *= a (test double of the gradient exchange, cn_allreduce_grads with CN_COMM_TEST_DOUBLE: what a two-rank all-reduce of
 // equal shards does to a gradient)
@@ -1732,34 +1645,6 @@ void launch_accumulate(hipStream_t s, float *acc, const float *wu, size_t n, boo
     if (n == 0) return;
     int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(accumulate_kernel, dim3(blocks), dim3(256), 0, s, acc, wu, n, first ? 1 : 0);
-}
-
-__global__ void sgd_kernel(float *w, const float *wu, float *wd, size_t n, float lr, float mom)
-{
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        // separate multiplies and adds (no FMA contraction) so that equal gradients give bit-equal weights
-        const float dl = __fsub_rn(__fmul_rn(mom, wd[i]), __fmul_rn(lr, wu[i]));   // SteepestDescentOptimizer.cu:51
-        wd[i] = dl;
-        w[i] = __fadd_rn(w[i], dl);                               // :55
-    }
-}
-void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, hipEvent_t done)
-{
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipExtLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom);
-}
-
-__global__ void adam_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a)
-{
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        w[i] = adam_step(w[i], wu[i], m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
-}
-void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done)
-{
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipExtLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1835,88 +1720,44 @@ void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, C
     hipLaunchKernelGGL(grad_norm_kernel, dim3(CLIP_WGS), dim3(256), 0, s, g, n, max_norm, rec);
 }
 
-// sgd_kernel / adam_kernel behind the record (kernels of their own: the plain ones keep their code)
-__global__ void sgd_clip_kernel(float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec)
-{
-    const int state = rec->state; const float scale = rec->scale;
-    if (state == CLIP_SKIP) return;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float g = wu[i];
-        if (state == CLIP_SCALE) g = __fmul_rn(scale, g);
-        const float dl = __fsub_rn(__fmul_rn(mom, wd[i]), __fmul_rn(lr, g));
-        wd[i] = dl;
-        w[i] = __fadd_rn(w[i], dl);
-    }
-}
-void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done)
-{
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipExtLaunchKernelGGL(sgd_clip_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, rec);
-}
-__global__ void adam_clip_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a, const ClipRecord *rec)
-{
-    const int state = rec->state; const float scale = rec->scale;
-    if (state == CLIP_SKIP) return;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float g = wu[i];
-        if (state == CLIP_SCALE) g = __fmul_rn(scale, g);
-        w[i] = adam_step(w[i], g, m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
-    }
-}
-void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done)
-{
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipExtLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, rec);
-}
-
-// sgd_kernel / adam_kernel with weight decay on (include/currennt_hip.h, section Weight decay; CLIP: behind the record too) over
-// ONE layer's flat range: rg names the two runs of it that decay, relative to its start.  Kernels of their own once more.
+// ---------------------------------------------------------------------------------------------
+// the flat update: momentum SGD (SteepestDescentOptimizer.cu:39-59 UpdateWeightFn) or Adam over a range of the arena
+// ---------------------------------------------------------------------------------------------
+// CLIP: behind the record of grad_norm_kernel -- g' = scale * g on CLIP_SCALE, nothing touched on CLIP_SKIP.  DECAY: the range is
+// ONE layer's, and the entries of dk.rg's two runs start their step from w0 = w - ld * w.  Compile-time flags, as pack_group_kernel's.
 __device__ __forceinline__ bool decays(const DecayRanges &rg, size_t i) { return i < rg.a1 || (i >= rg.b0 && i < rg.b1); }
-template <bool CLIP>
-__global__ void sgd_decay_kernel(float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, DecayRanges rg, const ClipRecord *rec)
+template <bool ADAM, bool CLIP, bool DECAY>
+__global__ void flat_update_kernel(FlatUpdate u, Opt<ADAM, FlatAdam> ad, Opt<CLIP, const ClipRecord *> rec, Opt<DECAY, FlatDecay> dk)
 {
     int state = CLIP_NONE; float scale = 1.0f;
     if constexpr (CLIP) { state = rec->state; scale = rec->scale; if (state == CLIP_SKIP) return; }
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float g = wu[i];
-        if constexpr (CLIP) { if (state == CLIP_SCALE) g = __fmul_rn(scale, g); }
-        const float dl = sgd_delta_exact(mom, wd[i], lr, g);
-        wd[i] = dl;
-        float w0 = w[i];
-        if (decays(rg, i)) w0 = decayed(w0, ld);
-        w[i] = sum_exact(w0, dl);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < u.n; i += (size_t)gridDim.x * blockDim.x) {
+        float g = u.wu[i];
+        if constexpr (CLIP) { if (state == CLIP_SCALE) g = clip_scaled(scale, g); }
+        StepFrom w{u.w + i, false, 0.f};
+        if constexpr (DECAY) { w.dec = decays(dk.rg, i); w.ld = dk.ld; }
+        if constexpr (ADAM) u.w[i] = adam_step(w, g, u.wd + i, ad.v + i, ad.a.b1, ad.a.omb1, ad.a.b2, ad.a.omb2, ad.a.alpha_t, ad.a.eps_t);
+        else u.w[i] = sgd_step(w, g, u.wd + i, u.lr, u.mom);
     }
 }
-template <bool CLIP>
-__global__ void adam_decay_kernel(float *w, const float *wu, float *m, float *v, size_t n, AdamScalars a, float ld, DecayRanges rg, const ClipRecord *rec)
+typedef void (*FlatUpdateLaunch)(hipStream_t, int, hipEvent_t, const FlatUpdate &, const FlatAdam *, const ClipRecord *, const FlatDecay *);
+template <bool ADAM, bool CLIP, bool DECAY>
+static void launch_flat_update_as(hipStream_t s, int blocks, hipEvent_t done, const FlatUpdate &u, const FlatAdam *adam, const ClipRecord *clip, const FlatDecay *decay)
 {
-    int state = CLIP_NONE; float scale = 1.0f;
-    if constexpr (CLIP) { state = rec->state; scale = rec->scale; if (state == CLIP_SKIP) return; }
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float g = wu[i];
-        if constexpr (CLIP) { if (state == CLIP_SCALE) g = __fmul_rn(scale, g); }
-        float w0 = w[i];
-        if (decays(rg, i)) w0 = decayed(w0, ld);
-        w[i] = adam_step_exact(w0, g, m + i, v + i, a.b1, a.omb1, a.b2, a.omb2, a.alpha_t, a.eps_t);
-    }
+    hipExtLaunchKernelGGL((flat_update_kernel<ADAM, CLIP, DECAY>), dim3(blocks), dim3(256), 0, s, nullptr, done, 0, u,
+                          opt_arg<ADAM>(adam), opt_arg<CLIP>(&clip), opt_arg<DECAY>(decay));
 }
-void launch_sgd_decay(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, const DecayRanges &rg,
-                      const ClipRecord *rec, hipEvent_t done)
+// entry 4 * adam + 2 * clip + decay
+template <size_t... I> static constexpr std::array<FlatUpdateLaunch, sizeof...(I)> flat_update_table(std::index_sequence<I...>)
 {
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    if (rec) hipExtLaunchKernelGGL(sgd_decay_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, ld, rg, rec);
-    else     hipExtLaunchKernelGGL(sgd_decay_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, wd, n, lr, mom, ld, rg, rec);
+    return {{&launch_flat_update_as<(I >> 2 & 1) != 0, (I >> 1 & 1) != 0, (I & 1) != 0>...}};
 }
-void launch_adam_decay(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, float ld, const DecayRanges &rg,
-                       const ClipRecord *rec, hipEvent_t done)
+void launch_flat_update(hipStream_t s, const FlatUpdate &u, const FlatAdam *adam, const ClipRecord *clip, const FlatDecay *decay, hipEvent_t done)
 {
-    if (n == 0) return;
-    int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048;
-    if (rec) hipExtLaunchKernelGGL(adam_decay_kernel<true>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, ld, rg, rec);
-    else     hipExtLaunchKernelGGL(adam_decay_kernel<false>, dim3(blocks), dim3(256), 0, s, nullptr, done, 0, w, wu, m, v, n, a, ld, rg, rec);
+    static constexpr auto table = flat_update_table(std::make_index_sequence<8>{});
+    if (u.n == 0) return;
+    int blocks = (int)((u.n + 255) / 256); if (blocks > 2048) blocks = 2048;
+    table[4 * (adam != nullptr) + 2 * (clip != nullptr) + (decay != nullptr)](s, blocks, done, u, adam, clip, decay);
 }
 
 }  // namespace cn

@@ -243,10 +243,8 @@ struct PackItem {
     void *Win, *WinT, *Wrec, *WrecT; float *bias_p, *peep_p;
     // update == 1: the momentum-SGD step of SteepestDescentOptimizer.cu:39-59 is applied on the way (every flat weight is read by
     // exactly one packed position, so the thread that packs it also updates it): wd = mom*wd - lr*wu; w += wd
-    // optimizer (beside `update`, in what was padding: the layout of the SGD forms is unchanged): PACK_OPT_SGD, or PACK_OPT_ADAM --
-    // launch_pack_group then launches pack_group_adam_kernel, instantiations of their own, with the group's PackAdam; lr holds the
-    // layer's alpha_t and mom holds beta1, wd is the first moment
-    int update; int optimizer; float *w_rw; const float *wu; float *wd; float lr, mom;
+    // Under Adam (a launch with a PackAdam) lr holds the layer's alpha_t, mom holds beta1 and wd is the first moment.
+    int update; float *w_rw; const float *wu; float *wd; float lr, mom;
     // update == 2 (cn_ctx_arm_update, no communicator): the gradient is taken straight from the PACKED accumulators the gradient
     // GEMMs / recurrent kernel summed into (every packed position is visited by exactly one thread, which also clears it and
     // writes the flat weightUpdates entry): unpack + update + operand copies in ONE launch behind the layer's gradient GEMMs
@@ -256,15 +254,15 @@ struct PackItem {
     PackFold f_in, f_rec[2], f_bias;
 };
 struct PackGroup { PackItem item[PACK_GROUP_MAX]; int first[PACK_GROUP_MAX]; int n; };
-enum { PACK_OPT_SGD = 0, PACK_OPT_ADAM = 1 };
-// What an Adam launch needs beyond PackItem (a kernel argument of its own: PackItem, and with it the SGD instantiations, stay as
-// they are): item i's second moments, and the scalars every layer shares (include/currennt_hip.h, cn_adam_update)
-struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
-// adam: required when the group's items say PACK_OPT_ADAM (all items of a group name the same optimizer)
-// clip (nullable; update == 1 items only): the record of grad_norm_kernel -- kernels of their own again (pack_group_clip_kernel),
-// the instantiations without it keep their code
+// The features of an update launch, grouped (launch_pack_group) or flat (launch_flat_update): each is a nullable argument of the
+// launcher and a compile-time flag of the one kernel template behind it -- an instantiation holds the code and the kernel
+// arguments of the features it was launched with and of no other.
+// adam (nullable; items with an update): the rule is Adam, not momentum SGD, for every item -- item i's second moments and the
+// scalars every layer shares beyond PackItem's lr and mom (include/currennt_hip.h, cn_adam_update)
+// clip (nullable; update == 1 items only): the record of grad_norm_kernel in front of the rule
 // decay (nullable; items with an update): weight decay is on (include/currennt_hip.h, section Weight decay) and item i's
-// ld = (float)(lr_layer * decay) -- kernels of their own once more (pack_group_decay_kernel), for every update mode and for clip
+// ld = (float)(lr_layer * decay), for every update mode and behind clip
+struct PackAdam { float *v[PACK_GROUP_MAX]; float b2, omb1, omb2, eps_t; };
 struct ClipRecord;
 struct PackDecayArgs { float ld[PACK_GROUP_MAX]; };
 void launch_pack_group(hipStream_t s, bool f32, PackGroup &grp, hipEvent_t done = nullptr, const PackAdam *adam = nullptr, const ClipRecord *clip = nullptr,
@@ -448,10 +446,6 @@ struct P2pArgs {
     unsigned long long *host_failed;           // host-mapped word: set when a wait of this exchange ended without its flag
 };
 void launch_p2p_allreduce(hipStream_t s, const P2pArgs &a);
-void launch_sgd(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, hipEvent_t done = nullptr);
-// the Adam step over a flat range (include/currennt_hip.h, cn_adam_update): m first moments, v second moments
-struct AdamScalars { float b1, omb1, b2, omb2, alpha_t, eps_t; };
-void launch_adam(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, hipEvent_t done = nullptr);
 void launch_accumulate(hipStream_t s, float *acc, const float *wu, size_t n, bool first);
 
 // ---- global gradient-norm clipping (include/currennt_hip.h, section Gradient clipping) ----
@@ -472,18 +466,21 @@ struct ClipRecord {
 };
 // one pass over g[0 .. n) (n a multiple of 4, g 16-byte aligned: the weightUpdates part of the arena); fills *rec
 void launch_grad_norm(hipStream_t s, const float *g, size_t n, float max_norm, ClipRecord *rec);
-// launch_sgd / launch_adam with the record in front of the rule: g' = scale * g on CLIP_SCALE, nothing touched on CLIP_SKIP
-void launch_sgd_clip(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, const ClipRecord *rec, hipEvent_t done = nullptr);
-void launch_adam_clip(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, const ClipRecord *rec, hipEvent_t done = nullptr);
 
-// ---- weight decay (include/currennt_hip.h, section Weight decay) ----
-// launch_sgd / launch_adam over ONE layer's flat range [0, n) with w0 = w - ld * w in front of the rule for the entries of
-// [0, a1) and [b0, b1) (the input weights and an LSTM layer's recurrent weights); rec (nullable): the clipping record as above
+// ---- the flat update: one launch over a range [0, n) of the arena (flat_update_kernel) ----
+// The range and momentum SGD's scalars: wd the weight deltas.  Under Adam (adam given) wd holds the first moments, and lr and mom
+// are not read: FlatAdam has the range's second moments and the step's scalars (one block, as adam_scalars forms them)
+struct FlatUpdate { float *w; const float *wu; float *wd; size_t n; float lr, mom; };
+struct AdamScalars { float b1, omb1, b2, omb2, alpha_t, eps_t; };      // (include/currennt_hip.h, cn_adam_update)
+struct FlatAdam { float *v; AdamScalars a; };
+// Weight decay (include/currennt_hip.h, section Weight decay): the range is ONE layer's, and w0 = w - ld * w is in front of the
+// rule for the entries of [0, a1) and [b0, b1) (the input weights and an LSTM layer's recurrent weights)
 struct DecayRanges { size_t a1, b0, b1; };
-void launch_sgd_decay(hipStream_t s, float *w, const float *wu, float *wd, size_t n, float lr, float mom, float ld, const DecayRanges &rg,
-                      const ClipRecord *rec = nullptr, hipEvent_t done = nullptr);
-void launch_adam_decay(hipStream_t s, float *w, const float *wu, float *m, float *v, size_t n, const AdamScalars &a, float ld, const DecayRanges &rg,
-                       const ClipRecord *rec = nullptr, hipEvent_t done = nullptr);
+struct FlatDecay { float ld; DecayRanges rg; };
+// adam, clip, decay (each nullable): the launch's features, as launch_pack_group's; clip: g' = scale * g on CLIP_SCALE, nothing
+// touched on CLIP_SKIP.  256 threads, min(ceil(n / 256), 2048) workgroups, nothing launched for n == 0; done rides on the launch.
+void launch_flat_update(hipStream_t s, const FlatUpdate &u, const FlatAdam *adam = nullptr, const ClipRecord *clip = nullptr,
+                        const FlatDecay *decay = nullptr, hipEvent_t done = nullptr);
 
 // ---- LAMB (include/currennt_hip.h, section LAMB; cn_lamb.hip) ----
 // The host scalars of the section, and the context's decay coefficient and trust bounds (max_ratio 0: no upper bound)

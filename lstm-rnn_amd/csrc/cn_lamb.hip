@@ -12,8 +12,9 @@ namespace cn {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// The direction of one entry, operation by operation as the header states it (the operators under contract(off): hipcc's __f*_rn
-// are the plain operators, which the backend would contract; sqrtf is the correctly rounded sequence, see adam_step).
+// The direction of one entry, operation by operation as the header states it.  The plain operators under contract(off), as the
+// steps of cn_elementwise.hip and for the reason stated there: the pragma is what keeps a product out of the sum that reads it
+// (hipcc's __f*_rn are the plain operators and promise nothing); sqrtf is the correctly rounded sequence, see adam_step.
 template <bool DEC>
 __device__ __forceinline__ float lamb_direction(float w, float g, float &m, float &v, const LambScalars &a)
 {
